@@ -17,6 +17,15 @@ Contract (one JSON line on rank 0):
   gpu_eager_baseline   the same step, same batch, with the oracle's eager layers on the SAME GPU (N = 1): the
                  op chain the path replaces, one box, one run.  Both are reported baselines, never the target.
 
+Runs: a plain run (`bench.py --gpus N --steps K --warmup W`) does only what metric/value need: set up, W warm-up
+steps, K timed steps, the outputs of --dump-outputs, the JSON line; the keys of the other legs are null there.
+`--full` adds every other leg as well: roofline, roofline_set, configs, gpu_eager_baseline and cpu_baseline (N = 1)
+and, at N > 1, data_parallel_check and the aewgs_allreduce_* figures.
+`--dump-outputs DIR` writes what the last timed step computed, after the timing (rank 0): loss.npy (the loss
+train_step returned), params.npy (every parameter of the student after the step's RAdam update, flattened in
+parameter order) and grads_sample.npy (the step's gradients of those parameters at a fixed, seeded sample of
+positions), all float32, 59 MB at most.  With the same arguments the inputs are the same in every run.
+
 Launch: python bench.py --gpus N          N = 1: this process.  N > 1 without WORLD_SIZE in the environment:
                                           this process starts N ranks itself (one per GPU, RCCL) through
                                           `python -m torch.distributed.run` BEFORE anything touches the GPU, relays
@@ -90,8 +99,9 @@ def seed_miopen_user_db():
     """cudnn.benchmark=True (what Lightning gives the reference) makes MIOpen search every convolution shape
     on first use: ~5 minutes on a fresh box for the 40-odd shapes of this step.  mhaq_amd/miopen_db/ holds the
     outcome of that search on an MI355X (MIOpen's own user find-db / perf-db text files: which MIOpen solver
-    won per shape); each process gets a private writable copy so the search is skipped.  The convolutions
-    themselves stay MIOpen's -- nothing here touches the fake-quant path.  MHAQ_NO_MIOPEN_DB=1 disables it."""
+    won per shape); each process gets a private writable copy, and main() reads the recorded winners through MIOpen's
+    immediate mode instead of searching again (see seeded_search_covers).  The convolutions themselves stay MIOpen's
+    -- nothing here touches the fake-quant path.  MHAQ_NO_MIOPEN_DB=1 disables it."""
     if os.environ.get("MHAQ_NO_MIOPEN_DB") == "1" or "MIOPEN_USER_DB_PATH" in os.environ:
         return None
     import glob
@@ -111,6 +121,12 @@ def seed_miopen_user_db():
 
 
 MIOPEN_DB_DIR = seed_miopen_user_db()      # before torch touches MIOpen
+
+
+def seeded_search_covers(batch, image):
+    """mhaq_amd/miopen_db/ holds the search of this step's workload -- ResNet-18 at batch 250 (calibration: 64) on 224 x 224
+    images, NCHW and channels_last, every convolution forward, backward-data and backward-weights -- and nothing else."""
+    return MIOPEN_DB_DIR is not None and batch == 250 and image == 224
 # dmabuf IPC: RCCL across processes needs it on this pool (the driver's environment exports it already; a rank started
 # by any other launcher must not depend on that).  Read when the HSA runtime initialises, i.e. at the first GPU call.
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -191,6 +207,9 @@ def parse():
                     help="quantize all weights in one launch per direction (single-GPU option)")
     ap.add_argument("--no-cudnn-benchmark", action="store_true",
                     help="disable torch.backends.cudnn.benchmark (MIOpen algorithm search; Lightning enables it)")
+    ap.add_argument("--cudnn-benchmark", action="store_true",
+                    help="search the convolution algorithms again in this process even where the seeded MIOpen find-db "
+                         "holds that search's outcome (~25 s at the first step; the default reads the outcome)"),
     ap.add_argument("--nchw", action="store_true",
                     help="keep the reference's NCHW memory format (default: channels_last, see docs/NOTEBOOK.md section 6, Memory format)")
     ap.add_argument("--no-teacher-overlap", action="store_true",
@@ -206,13 +225,22 @@ def parse():
                     help="replay forward + loss + backward as one hipGraph (single GPU).  auto: only if the host needs "
                          "> 80 %% of a step's wall time to enqueue it (the ResNet-18 batch-250 step is GPU-bound: "
                          "stays eager); see DESIGN.md section 6 / docs/NOTEBOOK.md section 6 \"hipGraph step\"")
-    ap.add_argument("--roofline-only", action="store_true", help="run only the kernel legs (PMC passes)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg other than the timed steps (roofline, roofline_set, configs, GPU eager and "
+                         "CPU baselines; at N > 1 the data-parallel check and the AEWGS exchange share); the --no-* "
+                         "options below leave out single legs of a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (loss, params, "
+                         "grads_sample)")
+    ap.add_argument("--roofline-only", action="store_true", help="run only the kernel legs (PMC passes; implies --full)")
     ap.add_argument("--no-roofline-set", action="store_true",
                     help="skip the 16-tensor activation-set leg (6.7 GB of buffers, ~2 s)")
     ap.add_argument("--no-configs", action="store_true",
                     help="skip the per-BASELINE-config quantizer-set legs (ResNet-20 b128 / b1000 per-tensor, RFDN "
                          "reference and stress shapes; ~10 s)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    args.full = args.full or args.roofline_only
+    return args
 
 
 # ------------------------------------------------------------------------------ roofline leg
@@ -713,6 +741,37 @@ def gpu_eager_baseline(args, dev, hip_ms_per_step):
     return out
 
 
+# ------------------------------------------------------------------------------ --dump-outputs
+DUMP_PARAM_ELEMS = 12 << 20     # params.npy: every element up to this many (ResNet-18: 11.7 M), a fixed sample beyond
+DUMP_GRAD_ELEMS = 2 << 20       # grads_sample.npy: 8 MiB of the step's gradients; 59 MB at most in all
+
+
+def _fixed_sample(flat, k, seed):
+    """`flat` itself when it has at most k elements, else k of its elements at seeded positions, in position order."""
+    import numpy as np
+    if flat.numel() <= k:
+        return flat
+    idx = np.sort(np.random.default_rng(seed).choice(flat.numel(), size=k, replace=False))
+    return flat[torch.from_numpy(idx).to(flat.device)]
+
+
+def dump_outputs(out_dir, net, loss):
+    """What the last timed step computed, as a caller of train_step holds it afterwards: the loss it returned, the
+    student's parameters after the optimizer step and the gradients of that step (float32 .npy files)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params = list(net.parameters())
+    flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+    flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                        for p in params])
+    arrays = {"loss": loss.detach().float().reshape(1),
+              "params": _fixed_sample(flat_p, DUMP_PARAM_ELEMS, seed=1),
+              "grads_sample": _fixed_sample(flat_g, DUMP_GRAD_ELEMS, seed=2)}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.cpu().numpy().astype(np.float32, copy=False))
+    return {name: int(t.numel()) for name, t in arrays.items()}
+
+
 # ------------------------------------------------------------------------------ main
 def claim_stdout():
     """stdout carries exactly one line, the result.  Libraries write there too (RCCL prints a five-line version
@@ -767,7 +826,7 @@ def main():
     from mhaq_amd.qat import QATConfig, QATTrainer
 
     roof = extra = None
-    if rank == 0:
+    if rank == 0 and args.full:
         log("kernel roofline leg")
         roof, extra = kernel_roofline(dev, args.kernel_reps)
         log(f"roofline: {roof['achieved']} GB/s; extra {extra}")
@@ -775,7 +834,7 @@ def main():
     rset = None
     # the 16-tensor set leg (6.7 GB of buffers, a graph capture, ~5 s) is an N = 1 measurement: at N > 1 the other
     # ranks would only wait for rank 0 in DDP's constructor, and a capture next to a live RCCL communicator buys nothing
-    if rank == 0 and world == 1 and not args.no_roofline_set:
+    if rank == 0 and world == 1 and args.full and not args.no_roofline_set:
         log("roofline over the whole ResNet-18 W4A4 activation set")
         try:
             rset = roofline_set(dev, args.batch if args.batch >= 250 else 250)
@@ -788,7 +847,7 @@ def main():
     # every other BASELINE configuration's quantizer set through the product path and the raw C ABI (the headline step
     # is configs[3] / [2]; roofline_set above is their ResNet-18 set): configs[0] on the GPU, configs[1], configs[4]
     cfgsets = None
-    if rank == 0 and world == 1 and not args.no_configs:
+    if rank == 0 and world == 1 and args.full and not args.no_configs:
         from tools.fq_sets import measure_config
         cfgsets = {}
         for key in ("resnet20_b128", "resnet20_b1000_pt", "rfdn_ref", "rfdn_stress"):
@@ -808,7 +867,12 @@ def main():
 
     # pl.Trainer(benchmark=None) turns cudnn.benchmark on unless deterministic (the reference's trainer.py:80-100
     # passes neither): MIOpen then searches for the fastest convolution algorithm per shape on first use
-    torch.backends.cudnn.benchmark = not args.no_cudnn_benchmark
+    # MIOpen's Find API (what cudnn.benchmark calls) searches again in every process even where the user find-db holds
+    # the record: it trusts a record only when all of its solvers' kernels are already built in the process (~25 s at
+    # the first step).  Where the seeded records hold that search's outcome, immediate mode (cudnn.benchmark off) reads
+    # the record and takes its fastest solution: the algorithm the search picks, without searching again.
+    torch.backends.cudnn.benchmark = not args.no_cudnn_benchmark and (
+        args.cudnn_benchmark or not seeded_search_covers(args.batch, args.image))
 
     torch.manual_seed(1234)          # identical initial weights on every rank
     ops.manual_seed(1234)
@@ -836,6 +900,8 @@ def main():
                          multi_tensor_weights=args.multi_tensor_weights and world == 1,
                          capture_graph=({"off": False, "on": True, "auto": "auto"}[args.capture_graph]
                                         if world == 1 else False))
+    if rank == 0:
+        log("model built and calibrated")
 
     if args.no_teacher_overlap:
         trainer.teacher_stream = None
@@ -861,12 +927,15 @@ def main():
     loss_val = float(loss)
     if rank == 0:
         log(f"timed {args.steps} steps: {dt / args.steps * 1e3:.2f} ms/step")
+        if args.dump_outputs:
+            n = dump_outputs(args.dump_outputs, trainer.net, loss)
+            log(f"outputs of the last timed step written to {args.dump_outputs}: {n}")
 
     # Data-parallel invariants after the timed steps, reported on the line (a real N-GPU run and the one-GPU rehearsals
     # alike): every rank holds the same parameters (replicated weights + all-reduced gradients), and every
     # rank draws its own random sign stream (the reference's ranks draw independent randint_like streams, gdnsq.py:54)
     dp_check = None
-    if dist.is_initialized() and world > 1:
+    if args.full and dist.is_initialized() and world > 1:
         with torch.no_grad():
             chk = torch.stack([p.detach().double().abs().sum() for p in trainer.net.parameters()]).sum().reshape(1)
         sums = [torch.zeros_like(chk) for _ in range(world)]
@@ -882,7 +951,7 @@ def main():
     # statistics all-reduce of each per-channel weight layer (issued from inside backward, in stream order).
     exchange_ms = None
     bufs = []
-    if dist.is_initialized() and world > 1 and args.qnmethod == "AEWGS":
+    if args.full and dist.is_initialized() and world > 1 and args.qnmethod == "AEWGS":
         # A secondary figure: it must not take the headline metric down with it -- and a rank that fails here (say,
         # out of memory for a buffer) must not leave the others blocked in a collective until the process-group
         # timeout.  So: allocate first, let all ranks AGREE that everyone succeeded (one int all-reduce), and only then
@@ -920,7 +989,7 @@ def main():
 
     n_weight_groups = len(trainer.weight_forward.groups) if trainer.weight_forward is not None else 0
     gpu_eager = None
-    if rank == 0 and n_gpus == 1 and not args.no_gpu_eager_baseline and not args.no_cpu_baseline:
+    if rank == 0 and n_gpus == 1 and args.full and not args.no_gpu_eager_baseline and not args.no_cpu_baseline:
         log("gpu eager baseline: the same step with the oracle's eager layers on this GPU")
         try:
             del trainer
@@ -931,7 +1000,7 @@ def main():
             gpu_eager = {"error": repr(e)[:500]}
             torch.cuda.empty_cache()
     cpu = None
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if rank == 0 and n_gpus == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
 
     if rank == 0:
@@ -941,7 +1010,7 @@ def main():
             "unit": "images/s",
             "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(dt / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "full": args.full,
             "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"ResNet-18 ImageNet-1k QAT step, {args.qnmethod} weights per-channel + STE "
                                    f"activations, {'Sym-KL distillation from FP teacher' if not args.no_distillation else 'CE'}"
@@ -949,7 +1018,8 @@ def main():
                        "per_gpu_batch": args.batch, "global_batch": args.batch * n_gpus,
                        "parallelism": f"dp{n_gpus}", "final_loss": round(loss_val, 5),
                        "sync_batchnorm": bool(cfg.sync_batchnorm and n_gpus > 1),
-                       "weight_backward_groups": n_weight_groups},
+                       "weight_backward_groups": n_weight_groups,
+                       "cudnn_benchmark": torch.backends.cudnn.benchmark},
             "roofline": roof, "cpu_baseline": cpu, "gpu_eager_baseline": gpu_eager,
             "roofline_set": rset,
             "configs": cfgsets,

@@ -37,8 +37,8 @@ def _check(out):
                                           "distinct_sign_streams": 2, "ranks": 2}
 
 
-ARGS = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8", "--image", "64", "--kernel-reps", "1", "--no-roofline-set",
-        "--no-cpu-baseline"]
+ARGS = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8", "--image", "64", "--full", "--kernel-reps", "1",
+        "--no-roofline-set", "--no-cpu-baseline"]
 
 
 def test_bench_gpus_2_starts_its_own_ranks():

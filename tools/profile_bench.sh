@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 R=${1:-r03}
 O=gpurun_out/prof_$R
 mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-roofline-set --no-configs > $O/bench_trace.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-roofline-set --no-configs > $O/bench_trace.log 2>&1
 echo "trace rc=$?"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python3 bench.py --roofline-only --no-roofline-set --no-configs --kernel-reps 5 > $O/bench_pmc_fetch.log 2>&1
 echo "fetch rc=$?"

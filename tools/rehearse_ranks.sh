@@ -9,4 +9,4 @@ cd /tmp && export TMPDIR=/tmp && cd ${GRAFT_REPO_ROOT:-$(dirname "$0")/..}
 N=${1:-5}
 export MHAQ_BENCH_BACKEND=gloo MHAQ_BENCH_SHARE_GPU=1 HSA_ENABLE_IPC_MODE_LEGACY=0
 exec timeout -k 10 500 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29533 \
-  bench.py --gpus $N --steps 3 --warmup 2 --batch 4 --image 64 --kernel-reps 1 --no-roofline-set --no-configs --no-cpu-baseline
+  bench.py --gpus $N --steps 3 --warmup 2 --batch 4 --image 64 --full --kernel-reps 1 --no-roofline-set --no-configs --no-cpu-baseline
