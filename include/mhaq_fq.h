@@ -68,7 +68,8 @@ extern "C" {
 #endif
 
 #define MHAQ_FQ_ABI_VERSION 4   /* v2: every backward entry point takes `offset_dev`; v3: sign stream layout (128 elements per Philox call);
-                                  v4 (additive): mhaq_fq_pc_quantize */
+                                  v4 (additive): mhaq_fq_pc_quantize; later additive entry points
+                                  (the 16-bit activation path, *_x16) keep v4 and are discovered by symbol */
 
 /* Estimator selector == QNMethod value (gdnsq_utils.py:9-13). */
 enum { MHAQ_FQ_STE = 0, MHAQ_FQ_EWGS = 1, MHAQ_FQ_AEWGS = 2, MHAQ_FQ_LSQ = 3 };
@@ -204,6 +205,37 @@ int mhaq_fq_act_bwd_partials(const float* x, const float* g, float* gx, int64_t 
                              int32_t* nparts_out, void* stream);
 int mhaq_fq_act_bwd_finalize_multi(const mhaq_act_finalize_desc* descs_device, int nquant,
                                    float* grads_out /* [nquant][3] */, void* stream);
+
+/* ------------------------------------------------------------------------
+ * 16-bit activations (mixed-precision training under torch.autocast: the convolution in front of a NoisyAct hands it a
+ * bf16 / fp16 tensor).  Additive to ABI v4 -- MHAQ_FQ_ABI_VERSION stays 4; a caller discovers these entry points by
+ * symbol.  They mirror mhaq_fq_act_fwd / _bwd / _bwd_partials with untyped data pointers and an element type:
+ *   x, y, g, gx   16-bit (dtype), contiguous in memory order, at least 2-byte aligned (else MHAQ_FQ_EALIGN);
+ *                 16-byte aligned pointers take the 8-elements-per-lane kernels, others an element kernel
+ *   params, grads, qstats, log_act_s / log_act_q / act_b   fp32, as in the fp32 entry points
+ *   dtype         MHAQ_FQ_DT_BF16 or MHAQ_FQ_DT_F16 (anything else: MHAQ_FQ_EINVAL)
+ * Arithmetic: every element is converted up exactly and runs the fp32 chain above; y and gx are rounded to nearest-even
+ * once.  y == RNE(y of mhaq_fq_act_fwd on the upcast x), gx == RNE(gx of mhaq_fq_act_bwd on the upcast x and g),
+ * element i draws the same random sign as the fp32 backward at the same (seed, offset, offset_dev), and the parameter
+ * gradients are the fp32 ones.
+ * Workspace rule: a call needs no more than the matching fp32 query returns -- mhaq_fq_pt_fwd_workspace_bytes(n) for
+ * the eval form of _fwd_x16 (qstats / flags non-NULL), mhaq_fq_act_bwd_workspace_bytes(n) for the backward; the 16-bit
+ * launch geometry never leaves more partial rows than the fp32 one (MHAQ_FQ_EWORKSPACE otherwise).  The partial rows
+ * of _bwd_partials_x16 have the layout of mhaq_fq_act_bwd_partials: mhaq_fq_act_bwd_finalize_multi reduces 16-bit and
+ * fp32 quantizers in the same launch.
+ * ---------------------------------------------------------------------- */
+enum { MHAQ_FQ_DT_BF16 = 1, MHAQ_FQ_DT_F16 = 2 };
+int mhaq_fq_act_fwd_x16(const void* x, void* y, int64_t n, int dtype,
+                        const float* log_act_s, const float* log_act_q, const float* act_b,
+                        float* params_out /* [5] */, float* qstats, int32_t* flags,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int mhaq_fq_act_bwd_x16(const void* x, const void* g, void* gx, int64_t n, int dtype, const float* params /* [5] */,
+                        int method, const int8_t* r_sign, uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
+                        float* grads /* [3] */, void* workspace, size_t workspace_bytes, void* stream);
+int mhaq_fq_act_bwd_partials_x16(const void* x, const void* g, void* gx, int64_t n, int dtype,
+                                 const float* params /* [5] */, int method, const int8_t* r_sign, uint64_t seed,
+                                 uint64_t offset, const uint64_t* offset_dev, void* workspace, size_t workspace_bytes,
+                                 int32_t* nparts_out, void* stream);
 
 /* Whole-tensor min / max (zero point of a PER_TENSOR weight quantizer,
  * gdnsq_conv2d.py:82-83; min/max observer, calib/minmaxobserver.py:19-36).

@@ -20,6 +20,10 @@ _u64 = C.c_uint64
 _sz = C.c_size_t
 _int = C.c_int
 
+# element types of the 16-bit entry points (include/mhaq_fq.h)
+DT_BF16 = 1
+DT_F16 = 2
+
 # name -> (restype, argtypes); must list every function declared in include/mhaq_fq.h
 # (tests/test_capi_symbols.py cross-checks this table against the header).
 SIGNATURES = {
@@ -38,6 +42,10 @@ SIGNATURES = {
     "mhaq_fq_act_bwd": (_int, [_p, _p, _p, _i64, _p, _int, _p, _u64, _u64, _p, _p, _p, _sz, _p]),
     "mhaq_fq_act_bwd_partials": (_int, [_p, _p, _p, _i64, _p, _int, _p, _u64, _u64, _p, _p, _sz, _p, _p]),
     "mhaq_fq_act_bwd_finalize_multi": (_int, [_p, _int, _p, _p]),
+    # 16-bit activations (additive, ABI v4 kept): `dtype` = MHAQ_FQ_DT_BF16 / MHAQ_FQ_DT_F16 after n
+    "mhaq_fq_act_fwd_x16": (_int, [_p, _p, _i64, _int, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "mhaq_fq_act_bwd_x16": (_int, [_p, _p, _p, _i64, _int, _p, _int, _p, _u64, _u64, _p, _p, _p, _sz, _p]),
+    "mhaq_fq_act_bwd_partials_x16": (_int, [_p, _p, _p, _i64, _int, _p, _int, _p, _u64, _u64, _p, _p, _sz, _p, _p]),
     "mhaq_fq_minmax_workspace_bytes": (_sz, [_i64]),
     "mhaq_fq_minmax": (_int, [_p, _i64, _p, _p, _sz, _p]),
     "mhaq_fq_row_minmax": (_int, [_p, _i64, _i64, _p, _p, _p]),

@@ -52,7 +52,7 @@ namespace {
   X(mhaq_fq_wlayer_aewgs_stats_group) X(mhaq_fq_wlayer_pt_fwd) X(mhaq_fq_wlayer_pt_bwd)                               \
   X(mhaq_fq_potential_loss_fwd) X(mhaq_fq_potential_loss_bwd) X(mhaq_fq_wlayer_ptl_workspace_bytes)                   \
   X(mhaq_fq_wlayer_ptl_fwd) X(mhaq_fq_wlayer_ptl_bwd) X(mhaq_fq_pt_aewgs_colstats_workspace_bytes)                     \
-  X(mhaq_fq_pt_aewgs_colstats)
+  X(mhaq_fq_pt_aewgs_colstats) X(mhaq_fq_act_fwd_x16) X(mhaq_fq_act_bwd_x16) X(mhaq_fq_act_bwd_partials_x16)
 
 struct Api {
 #define X(n) decltype(&::n) n = nullptr;
@@ -110,6 +110,15 @@ inline bool capturing() {
 inline const float* fptr(const Tensor& t) { return static_cast<const float*>(t.const_data_ptr()); }
 inline float* fptr_mut(const Tensor& t) { return static_cast<float*>(t.mutable_data_ptr()); }
 inline const float* fptr_or_null(const Tensor& t) { return t.defined() ? fptr(t) : nullptr; }
+
+// element type of a 16-bit activation for the *_x16 entry points; 0 = float32 (the fp32 entry points)
+inline int act_dtype(const Tensor& x) {
+  switch (x.scalar_type()) {
+    case at::kBFloat16: return MHAQ_FQ_DT_BF16;
+    case at::kHalf: return MHAQ_FQ_DT_F16;
+    default: return 0;
+  }
+}
 
 // the upstream gradient in the memory order of x (the kernels walk both as flat streams)
 inline Tensor like_layout(const Tensor& g, const Tensor& x) {
@@ -335,17 +344,24 @@ variable_list hub_begin(int64_t hub_id, const variable_list& params) { need_lib(
 
 // ------------------------------------------------------------------------------------------------ NoisyAct layer op
 // NoisyAct.forward from its learnable parameters (gdnsq_act.py:39-55): returns (y, params[5] = {s, zp, lo, hi, qr}).
+// x float32, or bf16 / fp16 (autocast; mhaq_amd/ops.py decides when): y and gx then have x's dtype, params and the
+// parameter gradients stay float32 (include/mhaq_fq.h, "16-bit activations").
 class ActLayerFn : public torch::autograd::Function<ActLayerFn> {
  public:
   static variable_list forward(AutogradContext* ctx, const Tensor& x, const Tensor& log_s, const Tensor& log_q,
                                const Tensor& b, int64_t method, const std::optional<Tensor>& r_sign, int64_t hub_id,
                                int64_t slot, int64_t rank) {
     Tensor y = at::empty_like(x);
-    Tensor params = at::empty({5}, x.options());
+    Tensor params = at::empty({5}, x.options().dtype(at::kFloat));
     const int64_t tl0 = now_ns();
-    check(A.mhaq_fq_act_fwd(fptr(x), fptr_mut(y), x.numel(), fptr(log_s), fptr(log_q), fptr(b), fptr_mut(params),
-                            nullptr, nullptr, nullptr, 0, cur_stream(x)),
-          "mhaq_fq_act_fwd");
+    if (const int dt = act_dtype(x))
+      check(A.mhaq_fq_act_fwd_x16(x.const_data_ptr(), y.mutable_data_ptr(), x.numel(), dt, fptr(log_s), fptr(log_q),
+                                  fptr(b), fptr_mut(params), nullptr, nullptr, nullptr, 0, cur_stream(x)),
+            "mhaq_fq_act_fwd_x16");
+    else
+      check(A.mhaq_fq_act_fwd(fptr(x), fptr_mut(y), x.numel(), fptr(log_s), fptr(log_q), fptr(b), fptr_mut(params),
+                              nullptr, nullptr, nullptr, 0, cur_stream(x)),
+            "mhaq_fq_act_fwd");
     tick(T_ACT_FWD_LAUNCH, tl0, now_ns());
     if (r_sign.has_value() && r_sign->defined()) ctx->save_for_backward({x, params, *r_sign});
     else ctx->save_for_backward({x, params});
@@ -365,6 +381,10 @@ class ActLayerFn : public torch::autograd::Function<ActLayerFn> {
     const std::vector<int64_t> ic = ctx->saved_data["i"].toIntVector();
     const int64_t method = ic[0], hub_id = ic[1], slot_i = ic[2], rank_i = ic[3];
     const int64_t t1 = now_ns();
+    const int dt = act_dtype(x);
+    // autograd hands the gradient over in y's dtype (= x's); a 16-bit kernel must not read a float32 stream as 16-bit
+    TORCH_CHECK(grads[0].scalar_type() == x.scalar_type(), "act_layer backward: the gradient is ",
+                grads[0].scalar_type(), ", the input ", x.scalar_type());
     Tensor g = like_layout(grads[0], x);
     Tensor gx = at::empty_like(x);
     const int64_t t2 = now_ns();
@@ -384,12 +404,18 @@ class ActLayerFn : public torch::autograd::Function<ActLayerFn> {
       Tensor ws = hub->workspace(slot, (int64_t)nb, x);
       int32_t nparts = 0;
       const int64_t t3 = now_ns();
-      check(A.mhaq_fq_act_bwd_partials(fptr(x), fptr(g), fptr_mut(gx), n, fptr(params), (int)method, r, d.seed, d.offset,
-                                       d.offset_dev, ws.mutable_data_ptr(), nb, &nparts, cur_stream(x)),
-            "mhaq_fq_act_bwd_partials");
+      if (dt)
+        check(A.mhaq_fq_act_bwd_partials_x16(x.const_data_ptr(), g.const_data_ptr(), gx.mutable_data_ptr(), n, dt,
+                                             fptr(params), (int)method, r, d.seed, d.offset, d.offset_dev,
+                                             ws.mutable_data_ptr(), nb, &nparts, cur_stream(x)),
+              "mhaq_fq_act_bwd_partials_x16");
+      else
+        check(A.mhaq_fq_act_bwd_partials(fptr(x), fptr(g), fptr_mut(gx), n, fptr(params), (int)method, r, d.seed,
+                                         d.offset, d.offset_dev, ws.mutable_data_ptr(), nb, &nparts, cur_stream(x)),
+              "mhaq_fq_act_bwd_partials");
       const int64_t t4 = now_ns();
       hub->pending.push_back(Hub::Pending{slot, nparts, ws});
-      Tensor ph = hub->placeholder(x);
+      Tensor ph = hub->placeholder(params);     // float32 like the parameters (x may be 16-bit)
       if (nx) out[0] = gx;
       if (ns) out[1] = ph;
       if (nq) out[2] = ph;
@@ -399,11 +425,17 @@ class ActLayerFn : public torch::autograd::Function<ActLayerFn> {
       tick(T_ACT_BWD, t0, now_ns());
       return out;
     }
-    Tensor gr = at::empty({3}, x.options());
+    Tensor gr = at::empty({3}, x.options().dtype(at::kFloat));
     Tensor ws = at::empty({(int64_t)nb}, x.options().dtype(at::kByte));
-    check(A.mhaq_fq_act_bwd(fptr(x), fptr(g), fptr_mut(gx), n, fptr(params), (int)method, r, d.seed, d.offset,
-                            d.offset_dev, fptr_mut(gr), ws.mutable_data_ptr(), nb, cur_stream(x)),
-          "mhaq_fq_act_bwd");
+    if (dt)
+      check(A.mhaq_fq_act_bwd_x16(x.const_data_ptr(), g.const_data_ptr(), gx.mutable_data_ptr(), n, dt, fptr(params),
+                                  (int)method, r, d.seed, d.offset, d.offset_dev, fptr_mut(gr), ws.mutable_data_ptr(), nb,
+                                  cur_stream(x)),
+            "mhaq_fq_act_bwd_x16");
+    else
+      check(A.mhaq_fq_act_bwd(fptr(x), fptr(g), fptr_mut(gx), n, fptr(params), (int)method, r, d.seed, d.offset,
+                              d.offset_dev, fptr_mut(gr), ws.mutable_data_ptr(), nb, cur_stream(x)),
+            "mhaq_fq_act_bwd");
     const auto shapes = ctx->saved_data["shapes"].to<std::vector<std::vector<int64_t>>>();
     if (nx) out[0] = gx;
     if (ns) out[1] = gr.narrow(0, 0, 1).view(shapes[0]);
@@ -420,7 +452,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> act_layer(const Tensor& x_in, const T
                                                      int64_t rank) {
   need_lib();
   MHAQ_ON_DEVICE_OF(x_in);
-  TORCH_CHECK(x_in.is_cuda() && x_in.scalar_type() == at::kFloat, "act_layer: x must be a float32 device tensor");
+  TORCH_CHECK(x_in.is_cuda() && (x_in.scalar_type() == at::kFloat || act_dtype(x_in) != 0),
+              "act_layer: x must be a float32, bfloat16 or float16 device tensor");
   TORCH_CHECK(log_s.numel() == 1 && log_q.numel() == 1 && b.numel() == 1 && log_s.is_cuda() && log_q.is_cuda() &&
                   b.is_cuda() && log_s.scalar_type() == at::kFloat && log_q.scalar_type() == at::kFloat &&
                   b.scalar_type() == at::kFloat,

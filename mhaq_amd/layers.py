@@ -71,6 +71,10 @@ class NoisyAct(nn.Module):
             Q._qm_seen = qm
         method = Q._qm_int
         if method == QNMethod.AEWGS.value:
+            if x.dtype is not torch.float32 and x.dtype in ops._X16:
+                # 16-bit input: the fp32 path on x.float(); under autocast y goes back to x's dtype (ops.autocast_x16)
+                y = self._forward_unfused_params(x.float())
+                return y.to(x.dtype) if ops.autocast_x16(x) else y
             return self._forward_unfused_params(x)
         # Hot path: the scalar chain s = 2^log_s, qr = 2^log_q, [b, b + qr - s] and its backward are
         # folded into the kernels (mhaq_fq_act_fwd / mhaq_fq_act_bwd): 2 launches per direction, one compiled
@@ -80,10 +84,10 @@ class NoisyAct(nn.Module):
             routed = None
             if ref is not None and ref.hub is not None:   # one finalize launch per backward pass for all quantizers
                 routed = ref.hub.take(ref.slot)           # (act_hub.py)
-            if routed is not None and x.is_cuda and x.dtype is torch.float32:
+            if routed is not None and x.is_cuda and (x.dtype is torch.float32 or ops.autocast_x16(x)):
                 # straight into the compiled node (its argument checks are the C++ ones): ~3 us less Python per call
                 y, params, s, hi = ops.act_layer_routed(x, routed, method, ref)
-            elif routed is not None:
+            elif routed is not None:      # (a 16-bit x outside autocast runs on x.float() there)
                 y, params, s, hi = ops._act_layer(x, routed[0], routed[1], routed[2], method, None, ref)
             else:
                 y, params, s, hi = ops._act_layer(x, self.log_act_s, self.log_act_q, self.act_b, method)

@@ -197,6 +197,21 @@ def _require_cuda_f32(t: torch.Tensor, name: str, any_dense_layout: bool = False
     return t.contiguous()
 
 
+_X16 = {torch.bfloat16: _lib.DT_BF16, torch.float16: _lib.DT_F16}
+
+
+def autocast_x16(x: torch.Tensor) -> bool:
+    """True when a 16-bit activation takes the 16-bit kernels (mhaq_fq_act_*_x16): torch.autocast is on for x's device
+    and x has the autocast dtype.  y then comes back in x's dtype -- the bits of the reference's fp32 y cast to it, which
+    is what the autocast convolution behind every NoisyAct (wrap.py) would cast it to.  Any other 16-bit x takes the fp32
+    kernels on x.float() and gets a float32 y, as the reference's op chain (clamp against fp32 bounds promotes) has it."""
+    dt = x.dtype
+    if dt is not torch.bfloat16 and dt is not torch.float16:
+        return False
+    kind = x.device.type
+    return torch.is_autocast_enabled(kind) and torch.get_autocast_dtype(kind) == dt
+
+
 def _is_dense(t: torch.Tensor) -> bool:
     """Non-overlapping and dense in SOME dimension order (contiguous, channels_last, ...)."""
     if t.is_contiguous() or t.dim() < 2:
@@ -433,7 +448,9 @@ def fake_quant_act_layer(x, log_act_s, log_act_q, act_b, method=QNMethod.STE, r_
     params[5] = {s, zp, lo, hi, qr}.  The autograd node is compiled (torch_binding.cpp: ActLayerFn): forward =
     mhaq_fq_act_fwd, backward = mhaq_fq_act_bwd -- or, with `hub_slot` = (ActGradHub, slot), mhaq_fq_act_bwd_partials,
     leaving the partial sums with the hub, whose single finalize launch serves every quantizer of the pass (act_hub.py).
-    AEWGS is not offered here (the reference never builds an AEWGS activation quantizer); use fake_quant_per_tensor."""
+    AEWGS is not offered here (the reference never builds an AEWGS activation quantizer); use fake_quant_per_tensor.
+    x: float32, or bf16 / fp16 -- under torch.autocast with x in the autocast dtype the node runs the 16-bit kernels
+    (mhaq_fq_act_*_x16) and y / x.grad have x's dtype (autocast_x16); otherwise a 16-bit x runs on x.float()."""
     return _act_layer(x, log_act_s, log_act_q, act_b, method, r_sign, hub_slot)[:2]
 
 
@@ -443,7 +460,13 @@ def _act_layer(x, log_act_s, log_act_q, act_b, method, r_sign=None, hub_slot=Non
     if m == QNMethod.AEWGS.value:
         raise NotImplementedError("AEWGS activations go through fake_quant_per_tensor")
     if not (x.is_cuda and x.dtype is torch.float32):
-        x = _require_cuda_f32(x, "x", any_dense_layout=True)        # raises (CPU tensor / wrong dtype)
+        if x.dtype in _X16 and x.is_cuda:
+            if not autocast_x16(x):
+                x = x.float()                                       # the reference's promotion: float32 y
+            elif not _is_dense(x):
+                x = x.contiguous()
+        else:
+            x = _require_cuda_f32(x, "x", any_dense_layout=True)    # raises (CPU tensor / wrong dtype)
     dev = x.device
     if not (torch.is_tensor(log_act_s) and log_act_s.is_cuda and log_act_s.dtype is torch.float32):
         log_act_s = _scalar(log_act_s, dev, "log_act_s")
@@ -479,7 +502,12 @@ def act_layer_routed(x, routed, method: int, ref):
 @_on_device
 @torch.no_grad()
 def fake_quant_act_layer_eval(x, log_act_s, log_act_q, act_b):
-    """Eval-mode NoisyAct in one launch (+ a tiny finalize): (y, params, qstats[2], flags[1])."""
+    """Eval-mode NoisyAct in one launch (+ a tiny finalize): (y, params, qstats[2], flags[1]).  A 16-bit x under autocast
+    (autocast_x16) takes mhaq_fq_act_fwd_x16 and gets y in its dtype; another 16-bit x runs on x.float()."""
+    if x.is_cuda and x.dtype in _X16:
+        if autocast_x16(x):
+            return _act_layer_eval_x16(x, log_act_s, log_act_q, act_b)
+        x = x.float()
     x = _require_cuda_f32(x, "x", any_dense_layout=True)
     dev = x.device
     L = _lib.lib()
@@ -493,6 +521,25 @@ def fake_quant_act_layer_eval(x, log_act_s, log_act_q, act_b):
                                  _scalar(log_act_q, dev, "q").data_ptr(), _scalar(act_b, dev, "b").data_ptr(),
                                  params.data_ptr(), qstats.data_ptr(), flags.data_ptr(), ws.data_ptr(), nb,
                                  _stream()), "mhaq_fq_act_fwd")
+    return y, params, qstats, flags
+
+
+def _act_layer_eval_x16(x, log_act_s, log_act_q, act_b):
+    """fake_quant_act_layer_eval for a 16-bit x (bf16 / fp16, any dense layout); the workspace is the fp32 query's."""
+    if not _is_dense(x):
+        x = x.contiguous()
+    dev = x.device
+    L = _lib.lib()
+    y = torch.empty_like(x)
+    params = torch.empty(5, dtype=torch.float32, device=dev)
+    qstats = torch.empty(2, dtype=torch.float32, device=dev)
+    flags = torch.empty(1, dtype=torch.int32, device=dev)
+    nb = L.mhaq_fq_pt_fwd_workspace_bytes(x.numel())
+    ws = _workspace(nb, dev)
+    _lib.check(L.mhaq_fq_act_fwd_x16(x.data_ptr(), y.data_ptr(), x.numel(), _X16[x.dtype],
+                                     _scalar(log_act_s, dev, "s").data_ptr(), _scalar(log_act_q, dev, "q").data_ptr(),
+                                     _scalar(act_b, dev, "b").data_ptr(), params.data_ptr(), qstats.data_ptr(),
+                                     flags.data_ptr(), ws.data_ptr(), nb, _stream()), "mhaq_fq_act_fwd_x16")
     return y, params, qstats, flags
 
 

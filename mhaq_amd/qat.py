@@ -13,9 +13,11 @@ PyTorch-Lightning, reduced to what BASELINE's images/sec metric needs (SURVEY.md
 """
 from __future__ import annotations
 
+import contextlib
 import copy
 import time
 from dataclasses import dataclass, field
+from typing import Optional
 
 import torch
 import torch.distributed as dist
@@ -54,6 +56,11 @@ class QATConfig:
     # group instead of per layer.  0 = every layer keeps its own backward launch.
     weight_backward_group_elems: int = 4 << 20
     criterion: nn.Module = field(default_factory=nn.CrossEntropyLoss)
+    # mixed precision (the reference trainer's `precision = "bf16-mixed"`, training/trainer.py:126): torch.bfloat16 runs
+    # the teacher and student forwards, the loss and validate_step's forward under torch.autocast; the activation
+    # quantizers then take the 16-bit kernels (mhaq_fq_act_*_x16), weights and quantizer parameters stay float32.
+    # None = float32 throughout.  torch.float16 would need loss scaling and is refused.
+    autocast_dtype: Optional[torch.dtype] = None
 
 
 # ----------------------------------------------------------------------------- calibration
@@ -184,6 +191,9 @@ class QATTrainer:
         (mhaq_amd/loss.py).  A CPU trainer is checker territory (tests, bench.py's cpu_baseline): it must bring its
         layers AND its loss (oracle/ref_layers.py, oracle/loss.py) -- the product has no CPU arithmetic."""
         self.cfg, self.device = cfg, torch.device(device)
+        if cfg.autocast_dtype is not None and cfg.autocast_dtype != torch.bfloat16:
+            raise ValueError(f"QATConfig.autocast_dtype: {cfg.autocast_dtype} is not supported (None or torch.bfloat16; "
+                             "float16 training needs loss scaling, which this trainer does not do)")
         self.distributed = ops._dist_active() if distributed is None else distributed
         net = net.to(self.device)
         self.teacher = copy.deepcopy(net).eval().requires_grad_(False) if cfg.distillation else None
@@ -314,6 +324,13 @@ class QATTrainer:
         self.optimizer = (optimizer_factory or torch.optim.RAdam)(self.net.parameters(), cfg.learning_rate)
         self.schedule = TemperatureSchedule(cfg.learning_rate, cfg.warmup, cfg.scale_lr, cfg.scale_t)
         self.schedule.start(self.optimizer)
+
+    def _autocast(self):
+        """torch.autocast over the step's forwards when cfg.autocast_dtype is set.  The weight-cast cache is off: it is
+        not capture-safe (a replayed graph would read casts of the weights as they were at capture time)."""
+        if self.cfg.autocast_dtype is None:
+            return contextlib.nullcontext()
+        return torch.autocast(self.device.type, dtype=self.cfg.autocast_dtype, cache_enabled=False)
 
     def _wrap_ddp(self):
         ids = [self.device.index] if self.device.type == "cuda" else None
@@ -557,20 +574,21 @@ class QATTrainer:
             # so that its kernels fill the gaps of the student's forward (45.7 -> 43.7 ms/step on ResNet-18)
             main = torch.cuda.current_stream()
             side.wait_stream(main)
-            with torch.cuda.stream(side), torch.no_grad():
+            with torch.cuda.stream(side), torch.no_grad(), self._autocast():
                 fp = self.teacher(x)
-        out = self.module(x)
-        if self.cfg.distillation:
-            if side is None:
-                with torch.no_grad():
-                    fp = self.teacher(x)
+        with self._autocast():
+            out = self.module(x)
+            if self.cfg.distillation:
+                if side is None:
+                    with torch.no_grad():
+                        fp = self.teacher(x)
+                else:
+                    main.wait_stream(side)
+                    if not torch.cuda.is_current_stream_capturing():   # a graph's private pool needs no such note
+                        fp.record_stream(main)
+                loss = self.loss(out, fp)
             else:
-                main.wait_stream(side)
-                if not torch.cuda.is_current_stream_capturing():   # a graph's private pool needs no such note
-                    fp.record_stream(main)
-            loss = self.loss(out, fp)
-        else:
-            loss = self.loss((self.cfg.criterion(out[0], y), *out[1:]))
+                loss = self.loss((self.cfg.criterion(out[0], y), *out[1:]))
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         return loss
@@ -585,7 +603,9 @@ class QATTrainer:
         from .gdnsq import check_model_integrity
         self.module.eval()
         try:
-            out = self.net(x)
+            with self._autocast():
+                out = self.net(x)
+            out = out.float()            # the statistics below in float32, as without autocast
             check_model_integrity(self.net)
         finally:
             self.module.train()
