@@ -22,12 +22,11 @@
 namespace mhaq {
 namespace io16 {
 
-#ifndef MHAQ_X16_BWD_U
-#define MHAQ_X16_BWD_U 2   // big tensors: 2 x 16 B per lane per stream, the bytes in flight per lane of the fp32 kernel
-#endif
 constexpr int kFwdU = 1;             // training forward: 2048 elements per block
 constexpr int kFwdStatsU = 2;        // eval forward: 4096 elements per block (fq_pt.hip's kFwdStatsU = 4 on float4)
-constexpr int kBwdU = MHAQ_X16_BWD_U;  // the small-tensor form takes 1: at the 8-wave bound (64 VGPRs) 2 spilled
+// big tensors: 2 x 16 B per lane per stream, the bytes in flight per lane of the fp32 kernel; the small-tensor form
+// takes 1: at the 8-wave bound (64 VGPRs) 2 spilled
+constexpr int kBwdU = 2;
 constexpr int bwd_u(bool big) { return big ? kBwdU : 1; }
 constexpr int64_t kFwdPlainLoadElems = 16ll << 20;     // as fq_pt.hip: non-temporal loads above this size
 constexpr int64_t kBwdBigElems = 20ll << 20;           // as fq_pt.hip (a lower threshold would never give more rows)

@@ -39,26 +39,6 @@ __device__ unsigned long long mhaq_trace_buf[8 * kTraceBlocks];
 #else
 #define MHAQ_TRACE_AT(k, WAIT) do { } while (0)
 #endif
-// A/B knob (tools/variants.sh): the SECOND half of a model-wide grid starts its rows NS nanoseconds late.  The dispatcher deals
-// workgroups round robin over XCDs and CUs, so the second half of the grid is the later half of EVERY CU's resident
-// workgroups: the first half gets the memory system to itself and is computing by the time the second half's rows arrive.
-// Measured (profiles/r06_pc_multi_stagger.txt): 1.5-3.5 us never pays for itself -- backward groups 13.0 / 12.9 / 7.3 -> 13.2 / 13.4 / 8.0 us
-// at 1.5 us, forward 17.3 -> 17.6; a 3 us delay of half the grid costs the 19 MB groups only 0.3 us (the overlap is real, the gain is not).  0 = off.
-#ifndef MHAQ_FWD_STAGGER_NS
-#define MHAQ_FWD_STAGGER_NS 0
-#endif
-#ifndef MHAQ_BWD_STAGGER_NS
-#define MHAQ_BWD_STAGGER_NS 0
-#endif
-template <int NS>
-__device__ __forceinline__ void stagger_second_half() {
-  if constexpr (NS > 0) {
-    if (2 * blockIdx.x >= gridDim.x) {
-      const unsigned long long t0 = wall_clock64();            // 100 MHz
-      while (wall_clock64() - t0 < (unsigned long long)(NS / 10)) __builtin_amdgcn_s_sleep(16);
-    }
-  }
-}
 // Sign tile of one row (sign stream v3, fq_common.hpp): the Philox calls covering the row's elements, computed once by the
 // workgroup.  296 calls = 37,888 elements: every row the staged / register-resident kernels take (<= 36 K floats) at any
 // alignment of its first element inside a call; longer rows draw call by call (philox_nibble / philox_r).
@@ -217,48 +197,9 @@ struct WLayerDesc {            // mirrors mhaq_wlayer_desc in include/mhaq_fq.h
 // 20 us launch --: slower, ResNet-18 forward 23.5 -> 26.8 us cold, gpurun_out/r04e_pc_multi.txt: with every CU starting on
 // 4608-float rows at once the workgroups run their load and compute phases in lock step.  With the row loads no longer
 // serialized (second half of the round) the order stopped mattering: last-first 21.7 vs 21.9 us; both ends towards the middle
-// (=2) puts all long rows on four of the eight XCDs, which the dispatcher deals workgroups to round robin -- those finish at
-// 19.5 us, the others at 14.5 --; in runs of 8 workgroups (=3) -0.35 us forward, +0.7 us backward.  -DMHAQ_MULTI_REVERSE=1/2/3
-// keep them as A/B knobs for tools/variants.sh.)
-#ifndef MHAQ_PACKED
-#define MHAQ_PACKED 1         // A/B knob: 0 = the scalar per-element code in the AEWGS backward
-#endif
-#ifndef MHAQ_PACKED_STE
-#define MHAQ_PACKED_STE 1     // the packed-fp32 element pair (ste_pair) in the STE / LSQ backward on rows of more than 4 float4 per thread: the
-                              // compute phase of a 19 MB group is all resident waves contending for the VALUs (profiles/r06_pc_multi_stagger.txt);
-                              // 15 instead of 30 fp32 operations per pair, the same bits, two VGPRs fewer.  ResNet-18 STE set 50.2 -> 49.3-49.6 us
-                              // cold, 43.9 -> 43.1-43.6 warm, groups 12.15 / 13.11 -> 11.85 / 12.85; LSQ 50.3 -> 49.4-50.0; nothing slower
-                              // (profiles/r06_pc_multi_packed_ste.txt).  0 = the scalar element (A/B).
-#endif
-#ifndef MHAQ_PACKED_FWD
-#define MHAQ_PACKED_FWD 1         // the packed-fp32 pair in the register-resident forward (quant_core_w + dequant, the same bits): with streaming
-                                  // stores the model-wide forward's compute + store phase is what the pair shortens -- 17.5 -> 17.1 us cold, 14.45 -> 14.0
-                                  // warm (round 4, with the output's write-back behind it, measured no gain); 0 = the scalar element (A/B)
-#endif
-#ifndef MHAQ_PACKED_AEWGS_MULTI
-#define MHAQ_PACKED_AEWGS_MULTI 1   // the packed AEWGS element at <= 4 float4 per thread inside the model-wide launches (0: A/B)
-#endif
-#ifndef MHAQ_PACKED_STE_ALL
-#define MHAQ_PACKED_STE_ALL 1 // the packed pair at every row length (unlike AEWGS, whose kept quotients compete for the registers at <= 4 float4 per
-                              // thread, the STE / LSQ pair needs none more: 60 VGPRs instead of 63): the 6 MB group 7.4 -> 7.1 us cold, 6.9-7.2 -> 6.55 warm,
-                              // the ResNet-18 set 43.3 -> 42.4 warm, [4096,4096] backward 37.0 -> 36.4; 0 = only above 4 float4 per thread (A/B)
-#endif
-#ifndef MHAQ_MULTI_REVERSE
-#define MHAQ_MULTI_REVERSE 0
-#endif
-#ifndef MHAQ_MULTI_REG
-#define MHAQ_MULTI_REG 1      // A/B knob: 0 = the LDS-staged bodies for every row of the multi-tensor launches
-#endif
-__device__ __forceinline__ int64_t multi_channel() {
-  const int64_t b = blockIdx.x, n = gridDim.x;
-  if (MHAQ_MULTI_REVERSE == 2) return (b & 1) ? (b >> 1) : n - 1 - (b >> 1);      // both ends towards the middle
-  if (MHAQ_MULTI_REVERSE == 3) {      // ... in runs of 8 workgroups (one per XCD: the dispatcher deals them round robin)
-    const int64_t g = b >> 3, i = ((g >> 1) << 3) + (b & 7);
-    const int64_t c = (g & 1) ? i : n - 1 - i;
-    return (c >= 0 && c < n && (n & 15) == 0) ? c : b;      // (grids that are not whole pairs of runs keep the identity)
-  }
-  return MHAQ_MULTI_REVERSE ? n - 1 - b : b;
-}
+// puts all long rows on four of the eight XCDs, which the dispatcher deals workgroups to round robin -- those finish at
+// 19.5 us, the others at 14.5 --; in runs of 8 workgroups -0.35 us forward, +0.7 us backward.)
+__device__ __forceinline__ int64_t multi_channel() { return blockIdx.x; }
 
 // The layer whose [chan_offset, chan_offset + co) range holds channel b: binary search over the descriptor table (the
 // offsets ascend).  Wave-uniform scalar loads, each a dependent round trip in front of the workgroup's first data load:
@@ -270,11 +211,8 @@ __device__ __forceinline__ int64_t multi_channel() {
 // dependent scalar loads + the descriptor) in front of a row whose loads take 2.  (Sixteen independent SCALAR loads issued back
 // to back and a count, for tables of <= 16 layers: slower -- descriptor phase 0.7 -> 2.0 us median, forward 20.7 -> 21.4 us;
 // gpurun_out/r04f_trace_scalar.txt.)
-#ifndef MHAQ_FIND_BALLOT
-#define MHAQ_FIND_BALLOT 1
-#endif
 __device__ __forceinline__ int find_layer(const WLayerDesc* __restrict__ d, int n, int64_t b) {
-  if (MHAQ_FIND_BALLOT && n <= 64) {
+  if (n <= 64) {
     const int lane = threadIdx.x & 63;
     const int64_t off = gptr(d)[lane < n ? lane : n - 1].chan_offset;
     const unsigned long long m = __ballot(off <= b);
@@ -289,7 +227,6 @@ __device__ __forceinline__ int find_layer(const WLayerDesc* __restrict__ d, int 
   return lo;
 }
 
-template <bool STAGE>
 __global__ void pc_fwd_multi_kernel(const WLayerDesc* __restrict__ descs, int nlayers, float* __restrict__ wq_all,
                                     float* __restrict__ aux_all /* [4][total_co]: s, zp, mx, lwq */,
                                     int64_t total_co) {
@@ -301,10 +238,10 @@ __global__ void pc_fwd_multi_kernel(const WLayerDesc* __restrict__ descs, int nl
   // are then read back to back, not the pointers after the branch on the offsets)
   if ((c < 0) | (c >= d.co) | (d.w == nullptr)) return;
   if (vec_ok(d.row, d.w, wq))     // per layer, workgroup-uniform
-    pc_fwd_body<STAGE, false, true, true>(d.w, wq, a + total_co, nullptr, d.log_s, d.row, a, a + 2 * total_co,
+    pc_fwd_body<false, false, true, true>(d.w, wq, a + total_co, nullptr, d.log_s, d.row, a, a + 2 * total_co,
                                           a + 3 * total_co, c);
   else
-    pc_fwd_body<STAGE, false, true, false>(d.w, wq, a + total_co, nullptr, d.log_s, d.row, a, a + 2 * total_co,
+    pc_fwd_body<false, false, true, false>(d.w, wq, a + total_co, nullptr, d.log_s, d.row, a, a + 2 * total_co,
                                            a + 3 * total_co, c);
 }
 
@@ -648,16 +585,14 @@ __device__ __forceinline__ void exact_quot4(vf2 a, vf2 b, const BwdCtx& k, float
 // The layers of a training step (<= 9.4 MB each) keep the default policy: the convolution that consumes wq and the
 // optimizer that consumes gW find them in the Infinity Cache.
 constexpr int64_t kPcNtBytes = 32ll << 20;
-#ifndef MHAQ_PC_SMALL_NT
-#define MHAQ_PC_SMALL_NT 3     // cache policy of the per-layer launches below kPcNtBytes (codes: see MHAQ_FWD_MULTI_NT): streaming
-                               // STORES, like the model-wide launches and for the same reason -- [512,4608] backward 9.6-9.9 -> 8.8-9.0 us,
-                               // forward 8.6-8.9 -> 8.3-8.5 (tools/pc_bench.py, profiles/r06_pc_multi_final.txt)
-#endif
+constexpr int kPcSmallNt = 3;     // cache policy of the per-layer launches below kPcNtBytes (codes: see kMultiNt): streaming
+                                  // STORES, like the model-wide launches and for the same reason -- [512,4608] backward 9.6-9.9 -> 8.8-9.0 us,
+                                  // forward 8.6-8.9 -> 8.3-8.5 (tools/pc_bench.py, profiles/r06_pc_multi_final.txt)
+// Row loads are non-temporal under policy 1; stores are non-temporal under both policies.
 // (global memory by contract, whatever the pointer's origin: see gptr in fq_common.hpp)
 template <bool NT>
 __device__ __forceinline__ vf4 pc_ld(const vf4* p) { return NT ? __builtin_nontemporal_load(gptr(p)) : *gptr(p); }
-template <bool NT>
-__device__ __forceinline__ void pc_st(vf4* p, vf4 v) { if (NT) __builtin_nontemporal_store(v, gptr(p)); else *gptr(p) = v; }
+__device__ __forceinline__ void pc_st(vf4* p, vf4 v) { __builtin_nontemporal_store(v, gptr(p)); }
 
 template <bool WRITE_Q, bool LAYER, int NV, int NT>
 __device__ __forceinline__ void pc_fwd_reg_body(
@@ -673,7 +608,7 @@ __device__ __forceinline__ void pc_fwd_reg_body(
     // unconditional, index clamped into the row (items >= 1): a load under `if (j < items)` ends in a register copy at the
     // join, and the copy in an s_waitcnt per load -- the row's loads would go out one round trip after the other
     const int j = threadIdx.x + k * T;
-    v[k] = pc_ld<(NT == 1 || NT == 2)>(wrow + (j < items ? j : items - 1));
+    v[k] = pc_ld<NT == 1>(wrow + (j < items ? j : items - 1));
   }
   // the channel's (log-)scale goes out under the row loads: behind the barrier of the row reduction its round trip
   // would sit on the workgroup's critical path
@@ -709,7 +644,10 @@ __device__ __forceinline__ void pc_fwd_reg_body(
     if (j < items) {
       const float e[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
       float o[4], qv[4];
-      if (MHAQ_PACKED_FWD && kx.fast_div) {       // two elements per instruction (quant_core_w + dequant, operation by operation)
+      // two elements per instruction (quant_core_w + dequant, operation by operation, the same bits): with streaming stores the
+      // model-wide forward's compute + store phase is what the pair shortens -- 17.5 -> 17.1 us cold, 14.45 -> 14.0 warm (round 4,
+      // with the output's write-back behind it, measured no gain)
+      if (kx.fast_div) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const vf2 vv = exact_v2(vf2{e[2 * h], e[2 * h + 1]}, sc, kx.rs, zp);
@@ -727,8 +665,8 @@ __device__ __forceinline__ void pc_fwd_reg_body(
           qv[q] = qc.q;
         }
       }
-      pc_st<(NT == 1 || NT == 3)>(orow + j, vf4{o[0], o[1], o[2], o[3]});
-      if (WRITE_Q) pc_st<(NT == 1 || NT == 3)>(qrow + j, vf4{qv[0], qv[1], qv[2], qv[3]});
+      pc_st(orow + j, vf4{o[0], o[1], o[2], o[3]});
+      if (WRITE_Q) pc_st(qrow + j, vf4{qv[0], qv[1], qv[2], qv[3]});
     }
   }
   // the channel's scalars last: thread 0's log2 does not hold back its wave's share of the row
@@ -761,9 +699,9 @@ __global__ __launch_bounds__(64 * kMaxWaves) void pc_fwd_reg_kernel(
 // cold, 27.7 -> 20.9 in the training step; STE backward groups 21.9 / 21.1 -> 19.4 / 19.4 cold.
 // TB = threads per workgroup: 256, or 1024 for models whose rows are whole tensors (multi_threads(): PER_TENSOR layers riding
 // the launch as one channel each, e.g. ResNet-20 with `qscheme: 0`, rows up to 36,864 floats = NV 9 at 1024 threads).
-// Cache policy of the model-wide launches' row accesses: 0 default, 1 non-temporal, 2 non-temporal LOADS only, 3 non-temporal
-// STORES only.  Round 6: 3 for both directions.  Stores that allocate in L2 leave the launch's whole output dirty there --
-// 19 MB for a backward group of ResNet-18, 44 MB for the model-wide forward against 32 MB of L2 -- and the end-of-kernel
+// Cache policy of the model-wide launches' row accesses (the NT codes): 0 default, 1 non-temporal, 2 non-temporal LOADS only,
+// 3 non-temporal STORES only; the library builds 1 and 3.  Round 6: 3 for both directions.  Stores that allocate in L2 leave
+// the launch's whole output dirty there -- 19 MB for a backward group of ResNet-18, 44 MB for the model-wide forward against 32 MB of L2 -- and the end-of-kernel
 // write-back drains it AFTER the last workgroup has retired: the phase stamps (profiles/r06_pc_multi_trace.txt) end
 // 2.4-2.8 us before the launch does on these launches and 0.5 us before it on the 6 MB group.  Streaming stores drain while
 // the rows are still being computed.  Loads keep the default policy: with streaming stores it beats streaming loads in both
@@ -773,28 +711,20 @@ __global__ __launch_bounds__(64 * kMaxWaves) void pc_fwd_reg_kernel(
 //   backward groups    policy 2 (r5)  13.3 13.5 7.7 / 11.9 11.8 7.1    1  12.8 13.4 7.5 / 11.3 12.6 7.1    3  12.2 12.3 7.3 / 10.7 10.7 6.5
 //   forward + grouped backward    r5  55.3 / 46.2 us  ->  49.5 / 42.1
 // (wq and gW are re-read within the step by the convolutions / the optimizer out of the memory-side Infinity Cache, which
-// the L2 policy does not bypass.)  Its 8 waves per SIMD are all needed (a cap at 6 / 4 / 2 waves: 21.7 -> 22.2 / 23.1 /
-// 28.5 us cold): the launch is bound by the latency of a row's round trips, not by HBM.
-// (A/B knobs for tools/variants.sh.)
-#ifndef MHAQ_BWD_MULTI_NT
-#define MHAQ_BWD_MULTI_NT 3
-#endif
-#ifndef MHAQ_FWD_MULTI_NT
-#define MHAQ_FWD_MULTI_NT 3
-#endif
-#ifndef MHAQ_FWD_MULTI_TB128
-#define MHAQ_FWD_MULTI_TB128 1
-#endif
-#ifndef MHAQ_FWD_MULTI_MAXW
-#define MHAQ_FWD_MULTI_MAXW 8
-#endif
+// the L2 policy does not bypass.)
+constexpr int kMultiNt = 3;
+// Its 8 waves per SIMD are all needed (a cap at 6 / 4 / 2 waves: 21.7 -> 22.2 / 23.1 / 28.5 us cold): the launch is bound by
+// the latency of a row's round trips, not by HBM.
+constexpr int kFwdMultiWaves = 8;
+// (Measured and not adopted, round 6: the second half of a model-wide grid starting its rows 1.5-3.5 us late, so that the first
+// half -- the earlier half of every CU's resident workgroups -- gets the memory system to itself.  It never pays for itself:
+// backward groups 13.0 / 12.9 / 7.3 -> 13.2 / 13.4 / 8.0 us at 1.5 us, forward 17.3 -> 17.6; profiles/r06_pc_multi_stagger.txt.)
 template <int NV, int TB>
-__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(((TB == 128 || TB == kBlock) ? (MHAQ_FWD_MULTI_MAXW < 8 ? 1 : 8) : 1), ((TB == 128 || TB == kBlock) ? MHAQ_FWD_MULTI_MAXW : 8))))
+__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(((TB == 128 || TB == kBlock) ? kFwdMultiWaves : 1), 8)))
 void pc_fwd_multi_reg_kernel(
     const WLayerDesc* __restrict__ descs, int nlayers, float* __restrict__ wq_all, float* __restrict__ aux_all,
     int64_t total_co) {
   MHAQ_TRACE_AT(0, false);
-  stagger_second_half<MHAQ_FWD_STAGGER_NS>();
   const WLayerDesc d = descs[find_layer(descs, nlayers, multi_channel())];
   float* a = aux_all + d.chan_offset;
   float* wq = wq_all + d.elem_offset;
@@ -808,8 +738,8 @@ void pc_fwd_multi_reg_kernel(
   // loads of that body with a clamped index.  Sending rows of <= 2 / <= 4 float4 per thread to the NV = 2 / 4 bodies inside
   // the same kernel, and a forward NV = 5: ResNet-18 forward + grouped backward 58.8 -> 59.3 us, gpurun_out/r04d_pc_multi.txt.)
   if (vec && (d.row >> 2) <= (int64_t)NV * TB)
-    pc_fwd_reg_body<false, true, NV, MHAQ_FWD_MULTI_NT>(d.w, wq, a + total_co, nullptr, d.log_s, d.row, a, a + 2 * total_co,
-                                                        a + 3 * total_co, c);
+    pc_fwd_reg_body<false, true, NV, kMultiNt>(d.w, wq, a + total_co, nullptr, d.log_s, d.row, a, a + 2 * total_co,
+                                               a + 3 * total_co, c);
   else if (vec)
     pc_fwd_body<false, false, true, true>(d.w, wq, a + total_co, nullptr, d.log_s, d.row, a, a + 2 * total_co,
                                           a + 3 * total_co, c);
@@ -838,8 +768,8 @@ __device__ __forceinline__ void pc_bwd_reg_body(
   for (int k = 0; k < NV; ++k) {
     const int j = threadIdx.x + k * T;
     const int jc = j < items ? j : items - 1;          // unconditional loads, clamped index: see pc_fwd_reg_body
-    xv[k] = pc_ld<(NT == 1 || NT == 2)>(wrow + jc);
-    gv4[k] = pc_ld<(NT == 1 || NT == 2)>(grow + jc);
+    xv[k] = pc_ld<NT == 1>(wrow + jc);
+    gv4[k] = pc_ld<NT == 1>(grow + jc);
   }
   __builtin_amdgcn_sched_barrier(0);
   // the channel's parameters go out under the row loads and in front of the sign tile's barrier (see pc_fwd_reg_body)
@@ -868,7 +798,7 @@ __device__ __forceinline__ void pc_bwd_reg_body(
   // (MULTI: inside the model-wide launches the packed element also pays at <= 4 float4 per thread -- 256-thread rows, 93 VGPRs, the
   // 5 waves per SIMD the 6 MB group needs: 10.1 -> 9.6 us cold, 9.6 -> 9.2 warm --; the per-layer launches of such rows keep the scalar
   // element: [50257,768] loses 4 % with it.  profiles/r06_pc_multi_packed_ste.txt, last section)
-  constexpr bool PACKED = (METHOD == MHAQ_FQ_AEWGS) && MHAQ_PACKED && (NV > 4 || (MULTI && MHAQ_PACKED_AEWGS_MULTI));
+  constexpr bool PACKED = (METHOD == MHAQ_FQ_AEWGS) && (NV > 4 || MULTI);
   float vkeep[KEEP_V ? 4 * NV : 1];
   const bool have_v = KEEP_V && !stats;
   float delta = 0.f;
@@ -959,7 +889,13 @@ __device__ __forceinline__ void pc_bwd_reg_body(
           if (LAYER) cnt_max += (xe[q] == rmx) ? 1 : 0;
         }
       }
-      constexpr bool PACKED_SL = (METHOD == MHAQ_FQ_STE || METHOD == MHAQ_FQ_LSQ) && MHAQ_PACKED_STE && (NV > 4 || MHAQ_PACKED_STE_ALL);
+      // STE / LSQ take the packed pair (ste_pair) at every row length: the compute phase of a 19 MB group is all resident waves
+      // contending for the VALUs (profiles/r06_pc_multi_stagger.txt); 15 instead of 30 fp32 operations per pair, the same bits,
+      // two VGPRs fewer.  Above 4 float4 per thread: ResNet-18 STE set 50.2 -> 49.3-49.6 us cold, 43.9 -> 43.1-43.6 warm, groups
+      // 12.15 / 13.11 -> 11.85 / 12.85; LSQ 50.3 -> 49.4-50.0; nothing slower (profiles/r06_pc_multi_packed_ste.txt).  At <= 4
+      // (unlike AEWGS, whose kept quotients compete for the registers there, the pair needs none more: 60 VGPRs instead of 63):
+      // the 6 MB group 7.4 -> 7.1 us cold, 6.9-7.2 -> 6.55 warm, the ResNet-18 set 43.3 -> 42.4 warm, [4096,4096] 37.0 -> 36.4.
+      constexpr bool PACKED_SL = (METHOD == MHAQ_FQ_STE || METHOD == MHAQ_FQ_LSQ);
       const bool packed = (PACKED || PACKED_SL) && kx.fast_div;
       if (PACKED_SL && packed) {                  // two elements per instruction: the same bits (see ste_pair)
 #pragma unroll
@@ -1026,7 +962,7 @@ __device__ __forceinline__ void pc_bwd_reg_body(
         slot_k = k; slot_x = xv[k]; slot_p = p4;
       } else {
         if (extreme) deferred |= 1u << k;
-        pc_st<(NT == 1 || NT == 3)>(orow + j, p4);
+        pc_st(orow + j, p4);
       }
     }
   }
@@ -1063,13 +999,13 @@ __device__ __forceinline__ void pc_bwd_reg_body(
     }
     return vf4{o[0], o[1], o[2], o[3]};
   };
-  if (slot_k >= 0) pc_st<(NT == 1 || NT == 3)>(orow + (threadIdx.x + slot_k * T), with_shares(slot_x, slot_p));
+  if (slot_k >= 0) pc_st(orow + (threadIdx.x + slot_k * T), with_shares(slot_x, slot_p));
   if (deferred) {
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       const int j = threadIdx.x + k * T;
       if (deferred & (1u << k))                                             // same-thread read-after-write on gW
-        pc_st<(NT == 1 || NT == 3)>(orow + j, with_shares(pc_ld<false>(wrow + j), pc_ld<false>(orow + j)));
+        pc_st(orow + j, with_shares(pc_ld<false>(wrow + j), pc_ld<false>(orow + j)));
     }
   }
   MHAQ_TRACE_AT(4, false);
@@ -1080,13 +1016,12 @@ __device__ __forceinline__ void pc_bwd_reg_body(
 // float4 is stored in pass 1), so the estimators fit 64 VGPRs up to 4 float4 per thread -- two 1024-thread workgroups per CU,
 // in different phases, instead of one ([1024,16384] rows) -- and AEWGS, whose statistics walk keeps the quotients, 80.
 // Each setting below compiles without scratch (tools/kernel_regs.py fq_pc.hip pc_bwd_reg_kernel).
-#ifndef MHAQ_PCREG_MINW
-#define MHAQ_PCREG_MINW(METHOD, NV)                                                  \
-  ((METHOD) == MHAQ_FQ_AEWGS ? ((NV) <= 2 ? 6 : ((NV) <= 4 ? 5 : 4))                 \
-                             : ((NV) <= 4 ? (((METHOD) == MHAQ_FQ_EWGS && (NV) == 4) ? 6 : 8) : 4))
-#endif
+constexpr int pc_reg_min_waves(int method, int nv) {
+  return method == MHAQ_FQ_AEWGS ? (nv <= 2 ? 6 : (nv <= 4 ? 5 : 4))
+                                 : (nv <= 4 ? ((method == MHAQ_FQ_EWGS && nv == 4) ? 6 : 8) : 4);
+}
 template <int METHOD, bool RSIGN, bool LAYER, int NV, int NT>
-__global__ __launch_bounds__(64 * kMaxWaves, MHAQ_PCREG_MINW(METHOD, NV)) void pc_bwd_reg_kernel(
+__global__ __launch_bounds__(64 * kMaxWaves, pc_reg_min_waves(METHOD, NV)) void pc_bwd_reg_kernel(
     const float* __restrict__ w, const float* __restrict__ G, float* __restrict__ gw, float* __restrict__ g_s,
     const float* __restrict__ s, const float* __restrict__ zp, int64_t co, int64_t row,
     const float* __restrict__ stats, const float* __restrict__ gzp_extra, const int8_t* __restrict__ r_sign,
@@ -1104,15 +1039,13 @@ __global__ __launch_bounds__(64 * kMaxWaves, MHAQ_PCREG_MINW(METHOD, NV)) void p
 // ([4096,4096] 40.0 us at 256 x 4 against 43.4 at 128 x 8; [1024,16384] 42.1 at 1024 x 4 against 44.5 at 512 x 8).
 // AEWGS backward makes two row reductions (statistics, then sums): wide workgroups pay for both barriers, so its
 // plan stops growing at 256 threads and takes 8 float4 per thread beyond ([1024,16384]: 68 us at 512 x 8, 85 at 1024 x 4).
-#ifndef MHAQ_AEWGS_CAP
-#define MHAQ_AEWGS_CAP 256    // A/B knob (tools/variants.sh): widest workgroup the two-reduction AEWGS rows grow to at 4 float4 per thread
-#endif
+constexpr int kAewgsCap = 256;    // widest workgroup the two-reduction AEWGS rows grow to at 4 float4 per thread
 static inline int reg_plan(int64_t row, bool vec, int* threads, bool backward = false, bool two_reductions = false) {
   if (!vec) return 0;
   const int64_t items = row >> 2;
   int t;
   if (backward) {
-    const int cap = two_reductions ? MHAQ_AEWGS_CAP : 64 * kMaxWaves;
+    const int cap = two_reductions ? kAewgsCap : 64 * kMaxWaves;
     t = 64;
     while (t < cap && items > (int64_t)t * 4) t *= 2;
     while (t < 64 * kMaxWaves && items > (int64_t)t * 8) t *= 2;
@@ -1130,7 +1063,7 @@ static inline int reg_plan(int64_t row, bool vec, int* threads, bool backward = 
 // Multi-tensor backward: aux_all is the forward's [4][total_co] slab; gw_all / g_log_s_all are slabs laid out
 // like wq_all / one aux row.  stats_all: nullable [3][total_co] AEWGS statistics (after the all-reduce).
 // The sign stream of layer L is the single-layer stream shifted by the layer's element offset.
-template <int METHOD, bool STAGE>
+template <int METHOD>
 __global__ void pc_bwd_multi_kernel(const WLayerDesc* __restrict__ descs, int nlayers,
                                     const float* __restrict__ aux_all, int64_t aux_stride,
                                     float* __restrict__ gw_all, float* __restrict__ g_log_s_all,
@@ -1149,11 +1082,11 @@ __global__ void pc_bwd_multi_kernel(const WLayerDesc* __restrict__ descs, int nl
   if ((c < 0) | (c >= d.co) | (d.w == nullptr)) return;
   __shared__ BwdLdsOf<METHOD, false> lds;
   if (vec_ok(d.row, d.w, d.G, gw) && (d.elem_offset & 3) == 0)     // per layer, workgroup-uniform
-    pc_bwd_body<METHOD, false, STAGE, true, true>(d.w, d.G, gw, g_log_s_all + d.chan_offset, a, a + aux_stride, sco,
+    pc_bwd_body<METHOD, false, false, true, true>(d.w, d.G, gw, g_log_s_all + d.chan_offset, a, a + aux_stride, sco,
                                                   d.row, st, nullptr, nullptr, seed, offset, a + 2 * aux_stride,
                                                   d.g_lwq, c, d.elem_offset, lds);
   else
-    pc_bwd_body<METHOD, false, STAGE, true, false>(d.w, d.G, gw, g_log_s_all + d.chan_offset, a, a + aux_stride, sco,
+    pc_bwd_body<METHOD, false, false, true, false>(d.w, d.G, gw, g_log_s_all + d.chan_offset, a, a + aux_stride, sco,
                                                    d.row, st, nullptr, nullptr, seed, offset, a + 2 * aux_stride,
                                                    d.g_lwq, c, d.elem_offset, lds);
 }
@@ -1162,18 +1095,17 @@ __global__ void pc_bwd_multi_kernel(const WLayerDesc* __restrict__ descs, int nl
 // float4 per thread take pc_bwd_reg_body -- one HBM read of W and G, stores of the non-extreme float4 before the row
 // reduction --, the others the staged body.  Same element -> thread mapping per row, fp64 row sums: the per-layer bits.
 // (min waves per SIMD as for pc_bwd_reg_kernel; this kernel also carries the staged bodies: 7 where that one has 8)
-#ifndef MHAQ_PCMULTI_MINW
-#define MHAQ_PCMULTI_MINW(METHOD, NV)                                                \
-  ((METHOD) == MHAQ_FQ_AEWGS ? ((NV) <= 2 ? 6 : ((NV) <= 5 ? 5 : 4))                 \
-                             : ((NV) <= 4 ? (((METHOD) == MHAQ_FQ_EWGS && (NV) == 4) ? 6 : 7) : ((NV) == 5 ? ((METHOD) == MHAQ_FQ_EWGS ? 5 : 6) : 4)))
-#endif
+constexpr int pc_multi_min_waves(int method, int nv) {
+  return method == MHAQ_FQ_AEWGS ? (nv <= 2 ? 6 : (nv <= 5 ? 5 : 4))
+                                 : (nv <= 4 ? ((method == MHAQ_FQ_EWGS && nv == 4) ? 6 : 7)
+                                            : (nv == 5 ? (method == MHAQ_FQ_EWGS ? 5 : 6) : 4));
+}
 template <int METHOD, int NV, int TB>
-__global__ __launch_bounds__(TB, (TB != kBlock ? 1 : MHAQ_PCMULTI_MINW(METHOD, NV))) void pc_bwd_multi_reg_kernel(
+__global__ __launch_bounds__(TB, (TB != kBlock ? 1 : pc_multi_min_waves(METHOD, NV))) void pc_bwd_multi_reg_kernel(
     const WLayerDesc* __restrict__ descs, int nlayers, const float* __restrict__ aux_all, int64_t aux_stride,
     float* __restrict__ gw_all, float* __restrict__ g_log_s_all, const float* __restrict__ stats_all,
     int64_t stats_stride, uint64_t seed, uint64_t offset, const uint64_t* __restrict__ offset_dev) {
   MHAQ_TRACE_AT(0, false);
-  stagger_second_half<MHAQ_BWD_STAGGER_NS>();
   offset = stream_offset(offset, offset_dev);
   const WLayerDesc d = descs[find_layer(descs, nlayers, multi_channel())];
   const float* a = aux_all + d.chan_offset;
@@ -1187,7 +1119,7 @@ __global__ __launch_bounds__(TB, (TB != kBlock ? 1 : MHAQ_PCMULTI_MINW(METHOD, N
   MHAQ_TRACE_AT(1, true);
   __shared__ BwdLdsOf<METHOD, false> lds;
   if (vec && (d.row >> 2) <= (int64_t)NV * TB)
-    pc_bwd_reg_body<METHOD, false, true, NV, MHAQ_BWD_MULTI_NT, true>(d.w, d.G, gw, g_log_s_all + d.chan_offset, a, a + aux_stride, sco,
+    pc_bwd_reg_body<METHOD, false, true, NV, kMultiNt, true>(d.w, d.G, gw, g_log_s_all + d.chan_offset, a, a + aux_stride, sco,
                                                     d.row, st, nullptr, nullptr, seed, offset, a + 2 * aux_stride,
                                                     d.g_lwq, c, d.elem_offset, lds);
   else if (vec)
@@ -1663,8 +1595,7 @@ static inline int opt_in_lds(K kernel, size_t lds) {
                                   (int)lds);
 }
 
-constexpr int64_t kMultiStageFloats = 12 * 1024;   // the multi-tensor grids stage rows up to 48 KiB
-// ... and run 256 threads per row -- except where a model's rows are WHOLE TENSORS (PER_TENSOR layers riding the
+// The multi-tensor grids run 256 threads per row -- except where a model's rows are WHOLE TENSORS (PER_TENSOR layers riding the
 // model-wide launches as one channel each: ResNet-20 with `qscheme: 0`, rows up to 36,864 floats on 18 workgroups): a row
 // of 8 K floats and more gets a full 1024-thread workgroup (measured on that set, tools/pc_multi_bench.py STE resnet20_pt:
 // forward 21.9 -> 12.4 us, backward 37.4 -> 17.1; profiles/r04_pc_multi_pmc.txt) and, up to 36,864 floats, the
@@ -1674,14 +1605,10 @@ constexpr int64_t kMultiStageFloats = 12 * 1024;   // the multi-tensor grids sta
 // inputs and more, a 3x3 convolution on 1024 channels -- stays at 256 threads: its thousands of short rows would otherwise
 // run 16 waves through two 16-wave barriers and issue 9 (18) clamped, redundant float4 loads per thread, and only its long
 // rows take the unstaged body of the 256-thread grid.
-// (-DMHAQ_MULTI_WIDE_ANY=1: the round-4 rule -- any launch whose longest row has 8 K floats -- as an A/B knob for
-// tools/variants.sh; measured on VGG-16's convolutions + a [64, 25088] Linear, tools/pc_multi_bench.py STE vggfc:
-// profiles/r05_ab_logs.txt)
-#ifndef MHAQ_MULTI_WIDE_ANY
-#define MHAQ_MULTI_WIDE_ANY 0
-#endif
+// (Measured and not adopted: the round-4 rule -- any launch whose longest row has 8 K floats --, on VGG-16's convolutions + a
+// [64, 25088] Linear, tools/pc_multi_bench.py STE vggfc: profiles/r05_ab_logs.txt)
 static inline int multi_threads(int64_t max_row, int64_t total_co, int nlayers) {
-  return (max_row >= 8192 && (MHAQ_MULTI_WIDE_ANY || total_co <= 2 * (int64_t)nlayers)) ? 64 * kMaxWaves : kBlock;
+  return (max_row >= 8192 && total_co <= 2 * (int64_t)nlayers) ? 64 * kMaxWaves : kBlock;
 }
 // float4 per thread of the register-resident multi-tensor bodies for a model whose longest row is max_row floats
 // (256 threads): 2, 4, 5 (4608-float rows: ResNet-18 / -34 / -50 3x3 layers) or 8.
@@ -1690,7 +1617,6 @@ static inline int multi_threads(int64_t max_row, int64_t total_co, int nlayers) 
 // rows that fit stay single-pass, the long ones take the unstaged body of the same grid.
 static inline int multi_reg_nv(int64_t max_row, bool backward) {
   const int64_t per = ((max_row + 3) / 4 + kBlock - 1) / kBlock;
-  if (MHAQ_MULTI_WIDE_ANY && per > 8) return 0;      // (the round-4 rule of the A/B knob above)
   return per <= 2 ? 2 : (per <= 4 ? 4 : ((per <= 5 && backward) ? 5 : 8));
 }
 
@@ -1710,7 +1636,7 @@ static int launch_pc_bwd(const float* w, const float* G, float* gw, float* g_s, 
 #define MHAQ_LAUNCH_PCR_(RS, LY, NV, NT)                                                                            \
   MHAQ_LAUNCH((pc_bwd_reg_kernel<METHOD, RS, LY, NV, NT>), dim3((unsigned)co), dim3(rt), 0, st, w, G, gw, g_s, \
                      s, zp, co, row, stats, gzp_extra, r_sign, seed, offset, offset_dev, mx, g_lwq)
-#define MHAQ_LAUNCH_PCR(RS, LY, NV) do { if (nt) MHAQ_LAUNCH_PCR_(RS, LY, NV, 1); else MHAQ_LAUNCH_PCR_(RS, LY, NV, MHAQ_PC_SMALL_NT); } while (0)
+#define MHAQ_LAUNCH_PCR(RS, LY, NV) do { if (nt) MHAQ_LAUNCH_PCR_(RS, LY, NV, 1); else MHAQ_LAUNCH_PCR_(RS, LY, NV, kPcSmallNt); } while (0)
 #define MHAQ_LAUNCH_PCR_NV(RS, LY)                                                                              \
   do { if (nv == 2) MHAQ_LAUNCH_PCR(RS, LY, 2); else if (nv == 4) MHAQ_LAUNCH_PCR(RS, LY, 4);                   \
        else MHAQ_LAUNCH_PCR(RS, LY, 8); } while (0)
@@ -1752,11 +1678,8 @@ static int launch_pc_bwd_multi(const WLayerDesc* d, int nlayers, const float* au
                                int64_t aux_stride, int64_t max_row, float* gw_all, float* g_log_s_all,
                                const float* stats_all, uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
                                hipStream_t st) {
-  const bool stage = 2 * max_row <= kMultiStageFloats;
-  const size_t lds = stage ? (size_t)max_row * 2 * sizeof(float) : 0;
   // the statistics slab is [3][total_co] of THIS launch (a group's own), the aux slab may be a window of a wider one
   const int threads = multi_threads(max_row, total_co, nlayers);
-  const int nv = MHAQ_MULTI_REG ? multi_reg_nv(max_row, true) : 0;
   // (no dynamic LDS: the few rows of such a launch that are not whole aligned float4s -- a first convolution's 27-float
   // rows -- take the unstaged body and read their row a second time from L2.  The staged fallback had every workgroup of the
   // launch reserve 2 x max_row floats it never touched: 37 KB for ResNet-18's last group, 3 workgroups per CU instead of
@@ -1766,20 +1689,21 @@ static int launch_pc_bwd_multi(const WLayerDesc* d, int nlayers, const float* au
                      nlayers, aux_all, aux_stride, gw_all, g_log_s_all, stats_all, total_co, seed, offset, offset_dev)
   // (128-thread workgroups, which the forward takes, measured slower here: ResNet-18 groups 13.5 / 13.6 / 7.8 -> 15.2 / 15.4 /
   // 8.6 us cold at 109 VGPRs and 9 float4 of W and of G per thread; gpurun_out/r04f_whatif.txt)
-  if (nv && threads == kBlock) {
+  if (threads == kBlock) {
+    const int nv = multi_reg_nv(max_row, true);
     if (nv == 2) MHAQ_LAUNCH_MBR(2, kBlock); else if (nv == 4) MHAQ_LAUNCH_MBR(4, kBlock);
     else if (nv == 5) MHAQ_LAUNCH_MBR(5, kBlock); else MHAQ_LAUNCH_MBR(8, kBlock);
     return launch_status();
   }
   // whole-tensor rows (1024 threads): rows up to 36,864 floats keep their data in registers (9 float4 of W and of G per
   // thread); longer ones, odd lengths and unaligned tensors take the unstaged body of the same grid
-  if (MHAQ_MULTI_REG && threads != kBlock && (max_row + 3) / 4 <= 9 * (int64_t)(64 * kMaxWaves)) {
+  if ((max_row + 3) / 4 <= 9 * (int64_t)(64 * kMaxWaves)) {
     MHAQ_LAUNCH_MBR(9, 64 * kMaxWaves);
     return launch_status();
   }
 #undef MHAQ_LAUNCH_MBR
-  if (stage) MHAQ_LAUNCH((pc_bwd_multi_kernel<METHOD, true>), dim3((unsigned)total_co), dim3(threads), lds, st, d, nlayers, aux_all, aux_stride, gw_all, g_log_s_all, stats_all, total_co, seed, offset, offset_dev);
-  else MHAQ_LAUNCH((pc_bwd_multi_kernel<METHOD, false>), dim3((unsigned)total_co), dim3(threads), 0, st, d, nlayers, aux_all, aux_stride, gw_all, g_log_s_all, stats_all, total_co, seed, offset, offset_dev);
+  MHAQ_LAUNCH((pc_bwd_multi_kernel<METHOD>), dim3((unsigned)total_co), dim3(threads), 0, st, d, nlayers, aux_all, aux_stride,
+              gw_all, g_log_s_all, stats_all, total_co, seed, offset, offset_dev);
   return launch_status();
 }
 
@@ -1807,7 +1731,7 @@ static int launch_pc_fwd(const float* w, float* wq, float* zp_out, float* q_out,
 #define MHAQ_LAUNCH_PCFR_(WQ, LY, NV, NT)                                                                        \
   MHAQ_LAUNCH((pc_fwd_reg_kernel<WQ, LY, NV, NT>), dim3((unsigned)co), dim3(rt), 0, st, w, wq, zp_out, q_out, \
                      s, row, s_out, mx_out, lwq_out)
-#define MHAQ_LAUNCH_PCFR(WQ, LY, NV) do { if (nt) MHAQ_LAUNCH_PCFR_(WQ, LY, NV, 1); else MHAQ_LAUNCH_PCFR_(WQ, LY, NV, MHAQ_PC_SMALL_NT); } while (0)
+#define MHAQ_LAUNCH_PCFR(WQ, LY, NV) do { if (nt) MHAQ_LAUNCH_PCFR_(WQ, LY, NV, 1); else MHAQ_LAUNCH_PCFR_(WQ, LY, NV, kPcSmallNt); } while (0)
 #define MHAQ_LAUNCH_PCFR_NV(WQ, LY)                                                                          \
   do { if (nv == 2) MHAQ_LAUNCH_PCFR(WQ, LY, 2); else if (nv == 4) MHAQ_LAUNCH_PCFR(WQ, LY, 4);              \
        else MHAQ_LAUNCH_PCFR(WQ, LY, 8); } while (0)
@@ -1926,34 +1850,31 @@ int mhaq_fq_wlayer_fwd_multi(const mhaq_wlayer_desc* descs_device, int nlayers, 
   if (total_co > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   const WLayerDesc* d = reinterpret_cast<const WLayerDesc*>(descs_device);
-  const bool stage = max_row <= kMultiStageFloats;
-  const size_t lds = stage ? (size_t)max_row * sizeof(float) : 0;
   const int threads = multi_threads(max_row, total_co, nlayers);
-  const int nv = MHAQ_MULTI_REG ? multi_reg_nv(max_row, false) : 0;
   // (no dynamic LDS, unstaged fallback for odd rows: see launch_pc_bwd_multi)
 #define MHAQ_LAUNCH_MFR(NV, TB)                                                                                      \
   MHAQ_LAUNCH((pc_fwd_multi_reg_kernel<NV, TB>), dim3((unsigned)total_co), dim3(TB), 0, st, d, nlayers,        \
                      wq_all, aux_all, total_co)
   // Rows up to 4608 floats (every 3x3 layer up to 512 input channels): 128-thread workgroups, up to 9 float4 per thread.  The
-  // launch is bound by the latency of a row's round trips (see MHAQ_FWD_MULTI_MAXW), and at the same registers -- the same
+  // launch is bound by the latency of a row's round trips (see kFwdMultiWaves), and at the same registers -- the same
   // bytes in flight -- per CU, sixteen two-wave rows overlap their phases better than eight four-wave ones: ResNet-18 forward
   // 21.9 -> 20.7 us cold, 17.2 -> 15.1 warm (one wave per row, 18 float4 per thread, 4 waves per SIMD: 22.1 / 16.5).
   const int64_t per128 = ((max_row + 3) / 4 + 127) / 128;
-  if (MHAQ_FWD_MULTI_TB128 && nv && threads == kBlock && per128 <= 9) {
+  if (threads == kBlock && per128 <= 9) {
     if (per128 <= 2) MHAQ_LAUNCH_MFR(2, 128); else if (per128 <= 4) MHAQ_LAUNCH_MFR(4, 128); else MHAQ_LAUNCH_MFR(9, 128);
     return launch_status();
   }
-  if (nv && threads == kBlock) {
+  if (threads == kBlock) {
+    const int nv = multi_reg_nv(max_row, false);
     if (nv == 2) MHAQ_LAUNCH_MFR(2, kBlock); else if (nv == 4) MHAQ_LAUNCH_MFR(4, kBlock); else MHAQ_LAUNCH_MFR(8, kBlock);
     return launch_status();
   }
-  if (MHAQ_MULTI_REG && threads != kBlock && (max_row + 3) / 4 <= 9 * (int64_t)(64 * kMaxWaves)) {   // whole-tensor rows
+  if ((max_row + 3) / 4 <= 9 * (int64_t)(64 * kMaxWaves)) {   // whole-tensor rows
     MHAQ_LAUNCH_MFR(9, 64 * kMaxWaves);
     return launch_status();
   }
 #undef MHAQ_LAUNCH_MFR
-  if (stage) MHAQ_LAUNCH((pc_fwd_multi_kernel<true>), dim3((unsigned)total_co), dim3(threads), lds, st, d, nlayers, wq_all, aux_all, total_co);
-  else MHAQ_LAUNCH((pc_fwd_multi_kernel<false>), dim3((unsigned)total_co), dim3(threads), 0, st, d, nlayers, wq_all, aux_all, total_co);
+  MHAQ_LAUNCH(pc_fwd_multi_kernel, dim3((unsigned)total_co), dim3(threads), 0, st, d, nlayers, wq_all, aux_all, total_co);
   return launch_status();
 }
 

@@ -19,35 +19,15 @@ namespace mhaq {
 // launch and is larger than the caches at BASELINE sizes, so loads and stores are
 // non-temporal: measured on MI355X a float4 copy runs 6.0-6.1 TB/s with nt vs 5.5-5.7 TB/s
 // without (tools/kbench.hip).
-// The MHAQ_* knobs below exist for tools/variants.sh (A/B builds of the library); defaults are the
-// measured optimum on MI355X.
-#ifndef MHAQ_FWD_NT_LD
-#define MHAQ_FWD_NT_LD 1
-#endif
-#ifndef MHAQ_FWD_NT_ST
-#define MHAQ_FWD_NT_ST 1
-#endif
-#ifndef MHAQ_FWD_U
-#define MHAQ_FWD_U 1   // float4 per lane (forward): block = 256*U float4 (U=1: 6.6 TB/s, U=4: 6.1)
-#endif
-#ifndef MHAQ_BWD_U
-#define MHAQ_BWD_U 2   // float4 per lane per stream (x and g) in backward (measured: U=1 127 us, U=2 96, U=4 100-102 at 50 M)
-#endif
-#ifndef MHAQ_BWD_NT_LD
-#define MHAQ_BWD_NT_LD 1
-#endif
-#ifndef MHAQ_BWD_NT_ST
-#define MHAQ_BWD_NT_ST 1
-#endif
+constexpr int kFwdU = 1;   // float4 per lane (forward): block = 256*U float4 (U=1: 6.6 TB/s, U=4: 6.1)
+constexpr int kBwdU = 2;   // float4 per lane per stream (x and g) in backward (measured: U=1 127 us, U=2 96, U=4 100-102 at 50 M)
 template <bool NT>
 __device__ inline vf4 ld4(const float* p, int64_t vidx) {
   const vf4* q = reinterpret_cast<const vf4*>(p) + vidx;
   return NT ? __builtin_nontemporal_load(q) : *q;
 }
-template <bool NT>
 __device__ inline void st4(float* p, int64_t vidx, vf4 v) {
-  vf4* q = reinterpret_cast<vf4*>(p) + vidx;
-  if (NT) __builtin_nontemporal_store(v, q); else *q = v;
+  __builtin_nontemporal_store(v, reinterpret_cast<vf4*>(p) + vidx);
 }
 
 static inline int64_t blocks_for(int64_t n, int u) {
@@ -72,9 +52,6 @@ __device__ inline float fwd_elem(float x, float s, float zp, float lo, float hi,
     // like (q == floor(q)) | (q == ceil(q)))
     st.qmin = fminf(st.qmin, c.q);
     st.qmax = fmaxf(st.qmax, c.q);
-#if MHAQ_FWD_STATS_RINT
-    if (!(c.q == rintf(c.q))) st.flags |= MHAQ_FQ_FLAG_NOT_INTEGER;
-#else
     // q = v + (rne(v) - v) IS rne(v) for every finite v (the subtraction is exact: |rne(v) - v| <= 1/2 and the two are
     // within a factor of two of each other, or rne(v) = 0; the sum is then the representable integer itself) and NaN for
     // v = NaN / +-inf (inf - inf).  So "q is not an integer" -- (q == floor(q)) | (q == ceil(q)) false, gdnsq.py:213-214 --
@@ -82,7 +59,6 @@ __device__ inline float fwd_elem(float x, float s, float zp, float lo, float hi,
     // spent rintf + compare + select + or per element on it; pinned by test_eval_flag_word_equals_the_three_reference_asserts
     // and the special-value tests)
     st.bad |= (c.q != c.q);
-#endif
   }
   return dequant(c.q, s, zp);
 }
@@ -102,21 +78,9 @@ constexpr int64_t kFwdPlainLoadElems = 16ll << 20;
 // that box): U = 4 70.3 us with the finalize, U = 2 71.8, U = 1 84.3 (49 000 blocks each ending in a barrier and a serial
 // tail of one thread); with the barrier replaced by an LDS ticket (the last wave to arrive combines, the others retire)
 // U = 1 / 2 / 4: 88.5 / 73.4 / 72.3.  4 stays.  The finalize launch is ~3.5 us of the 70.
-#ifndef MHAQ_FWD_STATS_U
-#define MHAQ_FWD_STATS_U 4
-#endif
-#ifndef MHAQ_FWD_STATS_RINT
-#define MHAQ_FWD_STATS_RINT 0      // A/B knob: 1 = the rounds 2-5 integrality test (q == rne(q))
-#endif
-constexpr int kFwdStatsU = MHAQ_FWD_STATS_U;
-// (-DMHAQ_FWD_MAXWAVES=n: an A/B knob for tools/variants.sh, an upper bound on the resident waves per SIMD)
-#ifdef MHAQ_FWD_MAXWAVES
-#define MHAQ_FWD_OCC __attribute__((amdgpu_waves_per_eu(1, MHAQ_FWD_MAXWAVES))) __launch_bounds__(kBlock)
-#else
-#define MHAQ_FWD_OCC __launch_bounds__(kBlock)
-#endif
+constexpr int kFwdStatsU = 4;
 template <bool WRITE_Q, bool STATS, bool ALIGNED, bool LOGP, bool NTLD, int FU>
-__global__ MHAQ_FWD_OCC void pt_fwd_kernel(
+__global__ __launch_bounds__(kBlock) void pt_fwd_kernel(
     const float* __restrict__ x, float* __restrict__ y, float* __restrict__ q_out, int64_t n,
     const float* __restrict__ ps, const float* __restrict__ pzp, const float* __restrict__ plo,
     const float* __restrict__ phi, float* __restrict__ partials /* [grid][3] */,
@@ -167,8 +131,8 @@ __global__ MHAQ_FWD_OCC void pt_fwd_kernel(
         o.y = fwd_elem<WRITE_Q, STATS>(a[u].y, s, zp, lo, hi, qlo, qhi, q1, st);
         o.z = fwd_elem<WRITE_Q, STATS>(a[u].z, s, zp, lo, hi, qlo, qhi, q2, st);
         o.w = fwd_elem<WRITE_Q, STATS>(a[u].w, s, zp, lo, hi, qlo, qhi, q3, st);
-        st4<MHAQ_FWD_NT_ST>(y, idx, o);
-        if (WRITE_Q) { vf4 qq = {q0, q1, q2, q3}; st4<MHAQ_FWD_NT_ST>(q_out, idx, qq); }
+        st4(y, idx, o);
+        if (WRITE_Q) { vf4 qq = {q0, q1, q2, q3}; st4(q_out, idx, qq); }
       }
     }
     // scalar tail (n % 4 elements)
@@ -395,22 +359,10 @@ __device__ inline void publish_act_scales(float* __restrict__ partials, const fl
 // gpurun_out/r04i_ab.txt).  Hence: at most 6 waves per SIMD from 20 Mi elements up, at least 8 below.  No instantiation
 // spills under either bound.
 constexpr int64_t kBwdBigElems = 20ll << 20;
-#ifndef MHAQ_BWD_MINWAVES
-#define MHAQ_BWD_MINWAVES 8
-#endif
-#ifndef MHAQ_BWD_BIG_MAXWAVES
-#define MHAQ_BWD_BIG_MAXWAVES 6
-#endif
-// (-DMHAQ_BWD_MAXWAVES=n: an A/B knob for tools/variants.sh, the same cap on every instantiation)
-#ifdef MHAQ_BWD_MAXWAVES
-#define MHAQ_BWD_OCC __attribute__((amdgpu_waves_per_eu(1, MHAQ_BWD_MAXWAVES))) __launch_bounds__(kBlock)
-#else
-#define MHAQ_BWD_OCC                                                                                              \
-  __attribute__((amdgpu_waves_per_eu((BIG ? 1 : MHAQ_BWD_MINWAVES), (BIG ? MHAQ_BWD_BIG_MAXWAVES : MHAQ_BWD_MINWAVES)))) \
-  __launch_bounds__(kBlock)
-#endif
+constexpr int kBwdMinWaves = 8, kBwdBigMaxWaves = 6;
 template <int METHOD, bool RSIGN, bool ALIGNED, bool COUNT, bool ACT, bool BIG>
-__global__ MHAQ_BWD_OCC void pt_bwd_kernel(
+__global__ __attribute__((amdgpu_waves_per_eu((BIG ? 1 : kBwdMinWaves), (BIG ? kBwdBigMaxWaves : kBwdMinWaves))))
+__launch_bounds__(kBlock) void pt_bwd_kernel(
     const float* __restrict__ x, const float* __restrict__ g, float* __restrict__ gx, int64_t n,
     const float* __restrict__ ps, const float* __restrict__ pzp, const float* __restrict__ plo,
     const float* __restrict__ phi, const float* __restrict__ col_stats, int64_t period,
@@ -419,24 +371,24 @@ __global__ MHAQ_BWD_OCC void pt_bwd_kernel(
   constexpr bool NEED_R = (METHOD != MHAQ_FQ_LSQ);
   constexpr bool FAST_METHOD = (METHOD == MHAQ_FQ_STE || METHOD == MHAQ_FQ_LSQ);
   constexpr int K = COUNT ? kNAcc : kNAcc - 1;     // live accumulators
-  constexpr int kTileCalls = 8 * MHAQ_BWD_U;       // 1024 * U elements per block / 128 per call
+  constexpr int kTileCalls = 8 * kBwdU;            // 1024 * U elements per block / 128 per call
   float acc[kNAcc] = {0.f, 0.f, 0.f, 0.f, 0.f};   // <= 4*U (+1) terms per thread in the aligned path
   // data loads first, parameters under them (see pt_fwd_kernel)
   const int64_t nvec = n >> 2;
-  const int64_t base = (int64_t)blockIdx.x * (kBlock * MHAQ_BWD_U) + threadIdx.x;
-  const bool full = ((int64_t)blockIdx.x + 1) * (kBlock * MHAQ_BWD_U) <= nvec;
-  vf4 a[MHAQ_BWD_U], b[MHAQ_BWD_U];
-  uint32_t rs[MHAQ_BWD_U];
+  const int64_t base = (int64_t)blockIdx.x * (kBlock * kBwdU) + threadIdx.x;
+  const bool full = ((int64_t)blockIdx.x + 1) * (kBlock * kBwdU) <= nvec;
+  vf4 a[kBwdU], b[kBwdU];
+  uint32_t rs[kBwdU];
   if (ALIGNED) {
     // unconditional loads (lanes past the end of a ragged last block re-read the last float4 and drop it): straight-line
     // code, all 2*U loads in flight before anything waits -- a load under `if (idx < nvec)` made the register allocator
     // wait for the first pair before issuing the second.  The launcher sends n < 4 to the dword kernel (nvec >= 1 here).
 #pragma unroll
-    for (int u = 0; u < MHAQ_BWD_U; ++u) {
+    for (int u = 0; u < kBwdU; ++u) {
       const int64_t idx = base + u * kBlock;
       const int64_t idc = (full || idx < nvec) ? idx : nvec - 1;
-      a[u] = ld4<MHAQ_BWD_NT_LD>(x, idc);
-      b[u] = ld4<MHAQ_BWD_NT_LD>(g, idc);
+      a[u] = ld4<true>(x, idc);
+      b[u] = ld4<true>(g, idc);
       if (NEED_R && RSIGN) rs[u] = reinterpret_cast<const uint32_t*>(r_sign)[idc];
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -454,9 +406,9 @@ __global__ MHAQ_BWD_OCC void pt_bwd_kernel(
 
   if (ALIGNED) {
     // this lane's sign nibbles: float4 u*256 + t of the block = bits [4*(u*256 + t), +4) of the tile, inverted once
-    uint32_t nb[MHAQ_BWD_U];
+    uint32_t nb[kBwdU];
 #pragma unroll
-    for (int u = 0; u < MHAQ_BWD_U; ++u) {
+    for (int u = 0; u < kBwdU; ++u) {
       nb[u] = 0;
       if (NEED_R && !RSIGN) nb[u] = ~(stile[(u * kBlock + (int)threadIdx.x) >> 3] >> (((int)threadIdx.x & 7) * 4));
     }
@@ -464,7 +416,7 @@ __global__ MHAQ_BWD_OCC void pt_bwd_kernel(
     if (FAST_METHOD && fast) {
       const float hcs = (MHAQ_INV_SQRT3 * k.s) * 0.5f;
 #pragma unroll
-      for (int u = 0; u < MHAQ_BWD_U; ++u) {
+      for (int u = 0; u < kBwdU; ++u) {
         const int64_t idx = base + u * kBlock;
         if (full || idx < nvec) {
           float rc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -478,12 +430,12 @@ __global__ MHAQ_BWD_OCC void pt_bwd_kernel(
           o.y = bwd_elem_fast<METHOD, COUNT>(a[u].y, b[u].y, rc[1], k, acc);
           o.z = bwd_elem_fast<METHOD, COUNT>(a[u].z, b[u].z, rc[2], k, acc);
           o.w = bwd_elem_fast<METHOD, COUNT>(a[u].w, b[u].w, rc[3], k, acc);
-          st4<MHAQ_BWD_NT_ST>(gx, idx, o);
+          st4(gx, idx, o);
         }
       }
     } else {
 #pragma unroll
-      for (int u = 0; u < MHAQ_BWD_U; ++u) {
+      for (int u = 0; u < kBwdU; ++u) {
         const int64_t idx = base + u * kBlock;
         if (full || idx < nvec) {
           float r0 = 0.f, r1 = 0.f, r2 = 0.f, r3 = 0.f;
@@ -512,7 +464,7 @@ __global__ MHAQ_BWD_OCC void pt_bwd_kernel(
           o.y = bwd_elem<METHOD, COUNT>(a[u].y, b[u].y, r1, col_delta_at<METHOD>(col_stats, period, j1), k, acc);
           o.z = bwd_elem<METHOD, COUNT>(a[u].z, b[u].z, r2, col_delta_at<METHOD>(col_stats, period, j2), k, acc);
           o.w = bwd_elem<METHOD, COUNT>(a[u].w, b[u].w, r3, col_delta_at<METHOD>(col_stats, period, j3), k, acc);
-          st4<MHAQ_BWD_NT_ST>(gx, idx, o);
+          st4(gx, idx, o);
         }
       }
     }
@@ -936,13 +888,13 @@ static int pt_fwd_impl(const float* x, float* y, int64_t n, const float* s, cons
   if (stats && (!workspace || workspace_bytes < mhaq_fq_pt_fwd_workspace_bytes(n))) return MHAQ_FQ_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const bool al = aligned16(x) && aligned16(y) && (!q_out || aligned16(q_out));
-  const int64_t grid64 = al ? blocks_for(n, stats ? kFwdStatsU : MHAQ_FWD_U) : simple_grid(n);
+  const int64_t grid64 = al ? blocks_for(n, stats ? kFwdStatsU : kFwdU) : simple_grid(n);
   if (grid64 > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
   const int grid = (int)grid64;
   float* parts = (float*)workspace;
-  const bool ntld = MHAQ_FWD_NT_LD && n > kFwdPlainLoadElems;
+  const bool ntld = n > kFwdPlainLoadElems;
 #define MHAQ_LAUNCH_FWD_(WQ, ST, AL, LP, NL)                                                                 \
-  MHAQ_LAUNCH((pt_fwd_kernel<WQ, ST, AL, LP, NL, (ST ? kFwdStatsU : MHAQ_FWD_U)>), dim3(grid), dim3(kBlock), 0, \
+  MHAQ_LAUNCH((pt_fwd_kernel<WQ, ST, AL, LP, NL, (ST ? kFwdStatsU : kFwdU)>), dim3(grid), dim3(kBlock), 0, \
                      st, x, y, q_out, n, s, zp, lo, hi, parts, params_out)
 #define MHAQ_LAUNCH_FWD(WQ, ST, AL)                                                                          \
   do {                                                                                                       \
@@ -987,7 +939,7 @@ int mhaq_fq_act_fwd(const float* x, float* y, int64_t n, const float* log_s, con
 // from there up and in the dword kernel of unaligned views
 static inline int64_t bwd_partial_rows(int64_t n, bool aligned) {
   if (!aligned) return simple_grid(n);
-  const int64_t blocks = blocks_for(n, MHAQ_BWD_U);
+  const int64_t blocks = blocks_for(n, kBwdU);
   return n >= kBwdBigElems ? blocks : blocks * (kBlock / 64);
 }
 size_t mhaq_fq_pt_bwd_workspace_bytes(int64_t n) {
@@ -1008,7 +960,7 @@ int mhaq_fq_pt_bwd_partials(const float* x, const float* g, float* gx, int64_t n
   if (!workspace || workspace_bytes < mhaq_fq_pt_bwd_workspace_bytes(n)) return MHAQ_FQ_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const bool al = n >= 4 && aligned16(x) && aligned16(g) && aligned16(gx) && (!r_sign || aligned4(r_sign));
-  const int64_t grid64 = al ? blocks_for(n, MHAQ_BWD_U) : simple_grid(n);
+  const int64_t grid64 = al ? blocks_for(n, kBwdU) : simple_grid(n);
   if (grid64 > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
   const int grid = (int)grid64;
   float* parts = (float*)workspace;
@@ -1055,7 +1007,7 @@ int mhaq_fq_act_bwd_partials(const float* x, const float* g, float* gx, int64_t 
   if (!workspace || workspace_bytes < mhaq_fq_pt_bwd_workspace_bytes(n)) return MHAQ_FQ_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const bool al = n >= 4 && aligned16(x) && aligned16(g) && aligned16(gx) && (!r_sign || aligned4(r_sign));
-  const int64_t grid64 = al ? blocks_for(n, MHAQ_BWD_U) : simple_grid(n);
+  const int64_t grid64 = al ? blocks_for(n, kBwdU) : simple_grid(n);
   if (grid64 > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
   const int grid = (int)grid64;
   float* parts = (float*)workspace;
