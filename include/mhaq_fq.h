@@ -237,6 +237,31 @@ int mhaq_fq_act_bwd_partials_x16(const void* x, const void* g, void* gx, int64_t
                                  uint64_t offset, const uint64_t* offset_dev, void* workspace, size_t workspace_bytes,
                                  int32_t* nparts_out, void* stream);
 
+/* ------------------------------------------------------------------------
+ * NoisyAct behind a ReLU (and a residual add), in the quantizer's own launches.  Additive to ABI v4 --
+ * MHAQ_FQ_ABI_VERSION stays 4; a caller discovers these entry points by symbol.  fp32; STE, LSQ or EWGS.
+ *   relu_fwd:  a = relu(z + addend) (addend nullable: a = relu(z)), y = fake_quant(a) as mhaq_fq_act_fwd computes it,
+ *              params_out[5] as there; a is written to a_out when that is non-NULL.  relu = torch.relu: NaN passes.
+ *              z, addend, y, a_out must not overlap.
+ *   relu_bwd:  z = the ReLU's input OR its output (a = relu(z) either way), g_y = dL/dy, g_a = the gradient reaching a
+ *              from its other consumers (nullable):  gx = (z <= 0) ? 0 : (gx of mhaq_fq_act_bwd(a, g_y) + g_a).
+ *              The partial rows (count, layout, values, {s, qr} behind them), the workspace rule, the random signs at
+ *              (seed, offset, offset_dev) and grads[3] are those of mhaq_fq_act_bwd_partials / mhaq_fq_act_bwd on
+ *              (a, g_y): mhaq_fq_act_bwd_finalize_multi serves both kinds of launch.
+ * Pointers at least 4-byte aligned (MHAQ_FQ_EALIGN); 16-byte aligned ones take the float4 kernels.
+ * ---------------------------------------------------------------------- */
+int mhaq_fq_act_relu_fwd(const float* z, const float* addend, float* y, float* a_out, int64_t n,
+                         const float* log_act_s, const float* log_act_q, const float* act_b,
+                         float* params_out /* [5] */, void* stream);
+int mhaq_fq_act_relu_bwd(const float* z, const float* g_y, const float* g_a, float* gx, int64_t n,
+                         const float* params /* [5] */, int method, uint64_t seed, uint64_t offset,
+                         const uint64_t* offset_dev, float* grads /* [3] */, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int mhaq_fq_act_relu_bwd_partials(const float* z, const float* g_y, const float* g_a, float* gx, int64_t n,
+                                  const float* params /* [5] */, int method, uint64_t seed, uint64_t offset,
+                                  const uint64_t* offset_dev, void* workspace, size_t workspace_bytes,
+                                  int32_t* nparts_out, void* stream);
+
 /* Whole-tensor min / max (zero point of a PER_TENSOR weight quantizer,
  * gdnsq_conv2d.py:82-83; min/max observer, calib/minmaxobserver.py:19-36).
  * out[0] = min, out[1] = max. */

@@ -598,6 +598,196 @@ __global__ __launch_bounds__(kFinalThreads) void act_finalize_multi_kernel(const
   }
 }
 
+// =============================================================== ReLU (+ residual add) fused into the NoisyAct kernels
+// A NoisyAct behind a ReLU -- mid-block bn -> relu -> quantizer, block end relu(bn + identity) -> next quantizer -- used to
+// be two or three full passes per direction (torch's add, clamp_min, threshold_backward and autograd's gradient
+// accumulation next to ours).  These kernels take the ReLU's INPUT: a = relu(z [+ addend]) is formed in registers, y =
+// fake_quant(a) as in pt_fwd_kernel, and a itself is written only for a caller that has another consumer for it (the
+// residual branch).  Same element bodies, same load-first structure, same partial rows as the kernels above; every value
+// is the one the separate launches produce (ReLU, a two-term fp32 add and a mask are exact elementwise operations).
+// torch.relu is clamp_min(x, 0): NaN passes through, x <= 0 (-0 included) gives 0.
+__device__ __forceinline__ float relu_elem(float x) { return (x <= 0.f) ? 0.f : x; }
+
+template <bool HAS_ADD, bool WRITE_A, bool ALIGNED, bool NTLD>
+__global__ __launch_bounds__(kBlock) void pt_fwd_relu_kernel(
+    const float* __restrict__ z, const float* __restrict__ addend, float* __restrict__ y, float* __restrict__ a_out,
+    int64_t n, const float* __restrict__ ps, const float* __restrict__ pzp, const float* __restrict__ plo,
+    float* __restrict__ params_out) {
+  // data loads first, parameters under them (see pt_fwd_kernel)
+  const int64_t nvec = n >> 2;
+  const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  vf4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
+  if (ALIGNED) {
+    if (idx < nvec) {
+      a = ld4<NTLD>(z, idx);
+      if (HAS_ADD) b = ld4<NTLD>(addend, idx);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  const float s = exp2f(*ps);
+  const float qr = exp2f(*pzp);
+  const float zp = *plo, lo = zp;
+  const float hi = (zp + qr) - s;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    params_out[0] = s; params_out[1] = zp; params_out[2] = lo; params_out[3] = hi; params_out[4] = qr;
+  }
+  FwdStats st{INFINITY, -INFINITY, 0, false};
+  float qq = 0.f;
+  if (ALIGNED) {
+    if (idx < nvec) {
+      if (HAS_ADD) a = a + b;
+      a.x = relu_elem(a.x); a.y = relu_elem(a.y); a.z = relu_elem(a.z); a.w = relu_elem(a.w);
+      vf4 o;
+      o.x = fwd_elem<false, false>(a.x, s, zp, lo, hi, 0.f, 0.f, qq, st);
+      o.y = fwd_elem<false, false>(a.y, s, zp, lo, hi, 0.f, 0.f, qq, st);
+      o.z = fwd_elem<false, false>(a.z, s, zp, lo, hi, 0.f, 0.f, qq, st);
+      o.w = fwd_elem<false, false>(a.w, s, zp, lo, hi, 0.f, 0.f, qq, st);
+      st4(y, idx, o);
+      if (WRITE_A) st4(a_out, idx, a);
+    }
+    const int64_t t = (nvec << 2) + threadIdx.x;      // n % 4 tail elements
+    if (blockIdx.x == 0 && t < n) {
+      const float av = relu_elem(HAS_ADD ? z[t] + addend[t] : z[t]);
+      y[t] = fwd_elem<false, false>(av, s, zp, lo, hi, 0.f, 0.f, qq, st);
+      if (WRITE_A) a_out[t] = av;
+    }
+  } else {
+    // unaligned pointers (tensor views): plain coalesced dword accesses
+    for (int64_t i = idx; i < n; i += (int64_t)gridDim.x * kBlock) {
+      const float av = relu_elem(HAS_ADD ? z[i] + addend[i] : z[i]);
+      y[i] = fwd_elem<false, false>(av, s, zp, lo, hi, 0.f, 0.f, qq, st);
+      if (WRITE_A) a_out[i] = av;
+    }
+  }
+}
+
+// Backward of the same: a = relu(z) is recomputed (z may be the ReLU's input or its output: relu is idempotent), the
+// quantizer's element body runs on (a, g_y) exactly as in pt_bwd_kernel<METHOD, false, ., false, true, .> -- same sign
+// tile, same accumulators, same partial rows, so the finalize kernels and the hub serve both -- and the ReLU's other
+// consumers' gradient g_a and its mask are applied to the elementwise output only:
+//   gx = (z <= 0) ? 0 : fq_bwd(a, g_y) [+ g_a]        (threshold_backward: a NaN z passes the gradient on)
+// Three input streams per unrolled step where pt_bwd_kernel has two; no instantiation spills under either occupancy bound.
+template <int METHOD, bool ALIGNED, bool HAS_GA, bool BIG>
+__global__ __attribute__((amdgpu_waves_per_eu((BIG ? 1 : kBwdMinWaves), (BIG ? kBwdBigMaxWaves : kBwdMinWaves))))
+__launch_bounds__(kBlock) void pt_bwd_relu_kernel(
+    const float* __restrict__ z, const float* __restrict__ g, const float* __restrict__ ga, float* __restrict__ gx,
+    int64_t n, const float* __restrict__ params, uint64_t seed, uint64_t offset,
+    const uint64_t* __restrict__ offset_dev, float* __restrict__ partials) {
+  constexpr bool NEED_R = (METHOD != MHAQ_FQ_LSQ);
+  constexpr bool FAST_METHOD = (METHOD == MHAQ_FQ_STE || METHOD == MHAQ_FQ_LSQ);
+  constexpr int K = kNAcc - 1;
+  constexpr int kTileCalls = 8 * kBwdU;
+  float acc[kNAcc] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  const int64_t nvec = n >> 2;
+  const int64_t base = (int64_t)blockIdx.x * (kBlock * kBwdU) + threadIdx.x;
+  const bool full = ((int64_t)blockIdx.x + 1) * (kBlock * kBwdU) <= nvec;
+  vf4 a[kBwdU], b[kBwdU], c[kBwdU];
+  if (ALIGNED) {
+    // unconditional, clamped loads: all 3*U in flight before anything waits (see pt_bwd_kernel; nvec >= 1 here)
+#pragma unroll
+    for (int u = 0; u < kBwdU; ++u) {
+      const int64_t idx = base + u * kBlock;
+      const int64_t idc = (full || idx < nvec) ? idx : nvec - 1;
+      a[u] = ld4<true>(z, idc);
+      b[u] = ld4<true>(g, idc);
+      if (HAS_GA) c[u] = ld4<true>(ga, idc);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  offset = stream_offset(offset, offset_dev);
+  const float p_s = params[0], p_zp = params[1], p_lo = params[2], p_hi = params[3];
+  __shared__ __align__(16) uint32_t stile[4 * kTileCalls];
+  if (ALIGNED && NEED_R) {
+    sign_tile_fill(stile, (int64_t)blockIdx.x * kTileCalls, kTileCalls, seed, offset);
+    __syncthreads();
+  }
+  const BwdCtx k = make_bwd_ctx(p_s, p_zp, p_lo, p_hi);
+
+  if (ALIGNED) {
+    uint32_t nb[kBwdU];
+#pragma unroll
+    for (int u = 0; u < kBwdU; ++u) {
+      nb[u] = 0;
+      if (NEED_R) nb[u] = ~(stile[(u * kBlock + (int)threadIdx.x) >> 3] >> (((int)threadIdx.x & 7) * 4));
+    }
+    const bool fast = FAST_METHOD && k.fast_div && (k.lo < k.hi) && (k.s > 0.f);      // wave-uniform
+    const float hcs = (MHAQ_INV_SQRT3 * k.s) * 0.5f;
+#pragma unroll
+    for (int u = 0; u < kBwdU; ++u) {
+      const int64_t idx = base + u * kBlock;
+      if (full || idx < nvec) {
+        const float zz[4] = {a[u].x, a[u].y, a[u].z, a[u].w};
+        const float gg[4] = {b[u].x, b[u].y, b[u].z, b[u].w};
+        float o[4];
+        if (FAST_METHOD && fast) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float rc = NEED_R ? signed_half_scale(nb[u], q, hcs) : 0.f;
+            o[q] = bwd_elem_fast<METHOD, false>(relu_elem(zz[q]), gg[q], rc, k, acc);
+          }
+        } else {
+          const uint32_t nib = ~nb[u];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float r = NEED_R ? (((nib >> q) & 1u) ? 0.5f : -0.5f) : 0.f;
+            o[q] = bwd_elem<METHOD, false>(relu_elem(zz[q]), gg[q], r, 0.f, k, acc);
+          }
+        }
+        if (HAS_GA) { o[0] = o[0] + c[u].x; o[1] = o[1] + c[u].y; o[2] = o[2] + c[u].z; o[3] = o[3] + c[u].w; }
+        vf4 ov;
+        ov.x = (zz[0] <= 0.f) ? 0.f : o[0];
+        ov.y = (zz[1] <= 0.f) ? 0.f : o[1];
+        ov.z = (zz[2] <= 0.f) ? 0.f : o[2];
+        ov.w = (zz[3] <= 0.f) ? 0.f : o[3];
+        st4(gx, idx, ov);
+      }
+    }
+    const int64_t t = (nvec << 2) + threadIdx.x;
+    if (blockIdx.x == 0 && t < n) {   // n % 4 tail elements
+      const float zz = z[t];
+      const float r = NEED_R ? philox_r(t, seed, offset) : 0.f;
+      float v = bwd_elem<METHOD, false>(relu_elem(zz), g[t], r, 0.f, k, acc);
+      if (HAS_GA) v = v + ga[t];
+      gx[t] = (zz <= 0.f) ? 0.f : v;
+    }
+    if (BIG) {
+      __shared__ float smf[K * (kBlock / 64)];
+      float live[K];
+#pragma unroll
+      for (int q = 0; q < K; ++q) live[q] = acc[q];
+      double tot[K];
+      block_sum_f32<K>(live, tot, smf);
+      if (threadIdx.x == 0) write_partials<true, K>(partials, tot, (int64_t)gridDim.x, (int64_t)blockIdx.x);
+      publish_act_scales(partials, params, (int64_t)gridDim.x);
+    } else {
+      float wsum[K];
+#pragma unroll
+      for (int q = 0; q < K; ++q) wsum[q] = wave_sum_dpp(acc[q]);
+      const int64_t nrows = (int64_t)gridDim.x * (kBlock / 64);
+      if ((threadIdx.x & 63) == 0)
+        write_partials<true, K>(partials, wsum, nrows, (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6));
+      publish_act_scales(partials, params, nrows);
+    }
+  } else {
+    // unaligned tensor views: dword accesses, grid-stride, fp64 per-thread accumulators
+    double dacc[kNAcc] = {0, 0, 0, 0, 0};
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+      const float zz = z[i];
+      const float r = NEED_R ? philox_r(i, seed, offset) : 0.f;
+      float a1[kNAcc] = {0.f, 0.f, 0.f, 0.f, 0.f};
+      float v = bwd_elem<METHOD, false>(relu_elem(zz), g[i], r, 0.f, k, a1);
+      if (HAS_GA) v = v + ga[i];
+      gx[i] = (zz <= 0.f) ? 0.f : v;
+#pragma unroll
+      for (int q = 0; q < kNAcc; ++q) dacc[q] += (double)a1[q];
+    }
+    __shared__ double sm[kNAcc * (kBlock / 64)];
+    block_sum<kNAcc>(dacc, sm);
+    if (threadIdx.x == 0) write_partials<true, kNAcc>(partials, dacc, (int64_t)gridDim.x, (int64_t)blockIdx.x);
+    publish_act_scales(partials, params, (int64_t)gridDim.x);
+  }
+}
+
 // =============================================================== min / max
 template <bool ALIGNED>
 __global__ __launch_bounds__(kBlock) void minmax_kernel(const float* __restrict__ x, int64_t n,
@@ -851,6 +1041,26 @@ static int launch_pt_bwd(const float* x, const float* g, float* gx, int64_t n, c
   return launch_status();
 }
 
+template <int METHOD>
+static int launch_pt_bwd_relu(const float* z, const float* g, const float* ga, float* gx, int64_t n,
+                              const float* params, uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
+                              float* parts, int grid, bool al, hipStream_t st) {
+  const bool big = al && n >= kBwdBigElems;
+#define MHAQ_LAUNCH_RBWD_(AL, GA, BG)                                                                        \
+  MHAQ_LAUNCH((pt_bwd_relu_kernel<METHOD, AL, GA, BG>), dim3(grid), dim3(kBlock), 0, st, z, g, ga, gx, n,    \
+              params, seed, offset, offset_dev, parts)
+#define MHAQ_LAUNCH_RBWD(GA)                                                                                 \
+  do {                                                                                                       \
+    if (!al) MHAQ_LAUNCH_RBWD_(false, GA, false);                                                            \
+    else if (big) MHAQ_LAUNCH_RBWD_(true, GA, true);                                                         \
+    else MHAQ_LAUNCH_RBWD_(true, GA, false);                                                                 \
+  } while (0)
+  if (ga) MHAQ_LAUNCH_RBWD(true); else MHAQ_LAUNCH_RBWD(false);
+#undef MHAQ_LAUNCH_RBWD
+#undef MHAQ_LAUNCH_RBWD_
+  return launch_status();
+}
+
 extern "C" {
 
 int mhaq_fq_abi_version(void) { return MHAQ_FQ_ABI_VERSION; }
@@ -1041,6 +1251,71 @@ int mhaq_fq_act_bwd_finalize_multi(const mhaq_act_finalize_desc* descs_device, i
   if (nquant == 0) return 0;
   MHAQ_LAUNCH(act_finalize_multi_kernel, dim3(3 * (unsigned)nquant), dim3(kFinalThreads), 0,
                      (hipStream_t)stream, (const ActFinalizeDesc*)descs_device, grads_out);
+  return launch_status();
+}
+
+// ---- ReLU (+ residual add) fused into the NoisyAct launches (pt_fwd_relu_kernel / pt_bwd_relu_kernel)
+int mhaq_fq_act_relu_fwd(const float* z, const float* addend, float* y, float* a_out, int64_t n, const float* log_s,
+                         const float* log_q, const float* b, float* params_out, void* stream) {
+  if (n < 0 || !log_s || !log_q || !b || !params_out || (n > 0 && (!z || !y))) return MHAQ_FQ_EINVAL;
+  if (!aligned4(z) || !aligned4(addend) || !aligned4(y) || !aligned4(a_out)) return MHAQ_FQ_EALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  const bool al = aligned16(z) && aligned16(y) && (!addend || aligned16(addend)) && (!a_out || aligned16(a_out));
+  const int64_t grid64 = al ? blocks_for(n, kFwdU) : simple_grid(n);
+  if (grid64 > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
+  const int grid = (int)grid64;
+  const bool ntld = n > kFwdPlainLoadElems;
+#define MHAQ_LAUNCH_RFWD_(HA, WA, AL, NL)                                                                    \
+  MHAQ_LAUNCH((pt_fwd_relu_kernel<HA, WA, AL, NL>), dim3(grid), dim3(kBlock), 0, st, z, addend, y, a_out, n, \
+              log_s, log_q, b, params_out)
+#define MHAQ_LAUNCH_RFWD(HA, WA)                                                                             \
+  do {                                                                                                       \
+    if (!al) MHAQ_LAUNCH_RFWD_(HA, WA, false, false);                                                        \
+    else if (ntld) MHAQ_LAUNCH_RFWD_(HA, WA, true, true);                                                    \
+    else MHAQ_LAUNCH_RFWD_(HA, WA, true, false);                                                             \
+  } while (0)
+  if (addend) { if (a_out) MHAQ_LAUNCH_RFWD(true, true); else MHAQ_LAUNCH_RFWD(true, false); }
+  else        { if (a_out) MHAQ_LAUNCH_RFWD(false, true); else MHAQ_LAUNCH_RFWD(false, false); }
+#undef MHAQ_LAUNCH_RFWD
+#undef MHAQ_LAUNCH_RFWD_
+  return launch_status();
+}
+
+int mhaq_fq_act_relu_bwd_partials(const float* z, const float* g_y, const float* g_a, float* gx, int64_t n,
+                                  const float* params, int method, uint64_t seed, uint64_t offset,
+                                  const uint64_t* offset_dev, void* workspace, size_t workspace_bytes,
+                                  int32_t* nparts_out, void* stream) {
+  if (n < 0 || !params || (n > 0 && (!z || !g_y || !gx))) return MHAQ_FQ_EINVAL;
+  if (method != MHAQ_FQ_STE && method != MHAQ_FQ_LSQ && method != MHAQ_FQ_EWGS)
+    return (method == MHAQ_FQ_AEWGS) ? MHAQ_FQ_EUNSUPPORTED : MHAQ_FQ_EINVAL;
+  if (!aligned4(z) || !aligned4(g_y) || !aligned4(g_a) || !aligned4(gx)) return MHAQ_FQ_EALIGN;
+  if (!workspace || workspace_bytes < mhaq_fq_pt_bwd_workspace_bytes(n)) return MHAQ_FQ_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const bool al = n >= 4 && aligned16(z) && aligned16(g_y) && aligned16(gx) && (!g_a || aligned16(g_a));
+  const int64_t grid64 = al ? blocks_for(n, kBwdU) : simple_grid(n);
+  if (grid64 > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
+  const int grid = (int)grid64;
+  float* parts = (float*)workspace;
+  const int64_t rows64 = bwd_partial_rows(n, al);
+  if (rows64 > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
+  if (nparts_out) *nparts_out = (int32_t)rows64;
+  switch (method) {
+    case MHAQ_FQ_STE: return launch_pt_bwd_relu<MHAQ_FQ_STE>(z, g_y, g_a, gx, n, params, seed, offset, offset_dev, parts, grid, al, st);
+    case MHAQ_FQ_EWGS: return launch_pt_bwd_relu<MHAQ_FQ_EWGS>(z, g_y, g_a, gx, n, params, seed, offset, offset_dev, parts, grid, al, st);
+    default: return launch_pt_bwd_relu<MHAQ_FQ_LSQ>(z, g_y, g_a, gx, n, params, seed, offset, offset_dev, parts, grid, al, st);
+  }
+}
+
+int mhaq_fq_act_relu_bwd(const float* z, const float* g_y, const float* g_a, float* gx, int64_t n,
+                         const float* params, int method, uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
+                         float* grads, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!grads) return MHAQ_FQ_EINVAL;
+  int32_t nparts = 0;
+  int rc = mhaq_fq_act_relu_bwd_partials(z, g_y, g_a, gx, n, params, method, seed, offset, offset_dev, workspace,
+                                         workspace_bytes, &nparts, stream);
+  if (rc) return rc;
+  MHAQ_LAUNCH(act_finalize_kernel, dim3(3), dim3(kFinalThreads), 0, (hipStream_t)stream,
+                     (const float*)workspace, (int)nparts, params, grads);
   return launch_status();
 }
 

@@ -52,7 +52,8 @@ namespace {
   X(mhaq_fq_wlayer_aewgs_stats_group) X(mhaq_fq_wlayer_pt_fwd) X(mhaq_fq_wlayer_pt_bwd)                               \
   X(mhaq_fq_potential_loss_fwd) X(mhaq_fq_potential_loss_bwd) X(mhaq_fq_wlayer_ptl_workspace_bytes)                   \
   X(mhaq_fq_wlayer_ptl_fwd) X(mhaq_fq_wlayer_ptl_bwd) X(mhaq_fq_pt_aewgs_colstats_workspace_bytes)                     \
-  X(mhaq_fq_pt_aewgs_colstats) X(mhaq_fq_act_fwd_x16) X(mhaq_fq_act_bwd_x16) X(mhaq_fq_act_bwd_partials_x16)
+  X(mhaq_fq_pt_aewgs_colstats) X(mhaq_fq_act_fwd_x16) X(mhaq_fq_act_bwd_x16) X(mhaq_fq_act_bwd_partials_x16)                    \
+  X(mhaq_fq_act_relu_fwd) X(mhaq_fq_act_relu_bwd) X(mhaq_fq_act_relu_bwd_partials)
 
 struct Api {
 #define X(n) decltype(&::n) n = nullptr;
@@ -463,6 +464,131 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> act_layer(const Tensor& x_in, const T
   auto out = ActLayerFn::apply(x, log_s, log_q, b, method, r_sign, hub_id, slot, rank);
   const Tensor& params = out[1];
   std::tuple<Tensor, Tensor, Tensor, Tensor> res{out[0], params, params.narrow(0, 0, 1), params.narrow(0, 3, 1)};
+  tick(T_ACT_FWD, t0, now_ns());
+  return res;
+}
+
+// ------------------------------------------------------------------------------------------------ ReLU + NoisyAct
+// The NoisyAct behind a ReLU, with the ReLU (and the residual add in front of it) inside the quantizer's launches
+// (mhaq_fq_act_relu_fwd / _bwd, mhaq_amd/fused_blocks.py): a = relu(z [+ addend]), y = fake_quant(a).  Outputs (y, params)
+// or, when a has another consumer (the residual branch), (y, params, a).  The backward receives dL/dy and dL/da together
+// and returns ONE gradient, which both z and addend take -- where the separate nodes ran autograd's accumulation of the
+// two gradients of a, threshold_backward and the quantizer's backward.  One sign-stream offset per backward, partials
+// registered with the hub: exactly as ActLayerFn.
+class ActReluFn : public torch::autograd::Function<ActReluFn> {
+ public:
+  static variable_list forward(AutogradContext* ctx, const Tensor& z, const std::optional<Tensor>& addend,
+                               const Tensor& log_s, const Tensor& log_q, const Tensor& b, int64_t method, bool want_act,
+                               int64_t hub_id, int64_t slot, int64_t rank) {
+    const bool has_add = addend.has_value() && addend->defined();
+    Tensor y = at::empty_like(z);
+    Tensor a = want_act ? at::empty_like(z) : Tensor();
+    Tensor params = at::empty({5}, z.options());
+    const int64_t tl0 = now_ns();
+    check(A.mhaq_fq_act_relu_fwd(fptr(z), has_add ? fptr(*addend) : nullptr, fptr_mut(y), want_act ? fptr_mut(a) : nullptr,
+                                 z.numel(), fptr(log_s), fptr(log_q), fptr(b), fptr_mut(params), cur_stream(z)),
+          "mhaq_fq_act_relu_fwd");
+    tick(T_ACT_FWD_LAUNCH, tl0, now_ns());
+    // relu is idempotent: the backward recomputes a from the ReLU's input (mid-block) or from a itself
+    ctx->save_for_backward({want_act ? a : z, params});
+    ctx->saved_data["i"] = std::vector<int64_t>{method, hub_id, slot, rank, (int64_t)want_act, (int64_t)has_add};
+    if (hub_id <= 0)
+      ctx->saved_data["shapes"] = std::vector<std::vector<int64_t>>{log_s.sizes().vec(), log_q.sizes().vec(), b.sizes().vec()};
+    ctx->set_materialize_grads(false);
+    ctx->mark_non_differentiable({params});
+    if (want_act) return {y, params, a};
+    return {y, params};
+  }
+
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    const int64_t t0 = now_ns();
+    auto saved = ctx->get_saved_variables();
+    const Tensor& z = saved[0];
+    const Tensor& params = saved[1];
+    const std::vector<int64_t> ic = ctx->saved_data["i"].toIntVector();
+    const int64_t method = ic[0], hub_id = ic[1], slot_i = ic[2], rank_i = ic[3];
+    const bool has_a = ic[4] != 0;
+    variable_list out(10);
+    const bool g_y_def = grads[0].defined(), g_a_def = has_a && grads.size() > 2 && grads[2].defined();
+    if (!g_y_def && !g_a_def) return out;
+    const int64_t t1 = now_ns();
+    // (a y nobody used: the quantizer's terms are those of a zero gradient)
+    Tensor g = g_y_def ? like_layout(grads[0], z) : at::zeros_like(z);
+    Tensor ga = g_a_def ? like_layout(grads[2], z) : Tensor();
+    Tensor gx = at::empty_like(z);
+    const int64_t t2 = now_ns();
+    tick(T_ACT_BWD_SAVED, t0, t1);
+    tick(T_ACT_BWD_ALLOC, t1, t2);
+    const int64_t n = z.numel();
+    const size_t nb = A.mhaq_fq_act_bwd_workspace_bytes(n);
+    const Draw d = draw_signs(false, method, rank_i, z);
+    // (needs_input_grad counts the tensor inputs that were present: an absent addend takes no slot)
+    const size_t e = ic[5] != 0 ? 1 : 0;
+    const bool nz = ctx->needs_input_grad(0), nadd = e && ctx->needs_input_grad(1), ns = ctx->needs_input_grad(1 + e),
+               nq = ctx->needs_input_grad(2 + e), nbias = ctx->needs_input_grad(3 + e);
+    if (hub_id > 0) {
+      auto hub = hub_get(hub_id);
+      std::lock_guard<std::mutex> lk(hub->mu);
+      Tensor ws = hub->workspace(slot_i, (int64_t)nb, z);
+      int32_t nparts = 0;
+      const int64_t t3 = now_ns();
+      check(A.mhaq_fq_act_relu_bwd_partials(fptr(z), fptr(g), fptr_or_null(ga), fptr_mut(gx), n, fptr(params), (int)method,
+                                            d.seed, d.offset, d.offset_dev, ws.mutable_data_ptr(), nb, &nparts,
+                                            cur_stream(z)),
+            "mhaq_fq_act_relu_bwd_partials");
+      const int64_t t4 = now_ns();
+      hub->pending.push_back(Hub::Pending{slot_i, nparts, ws});
+      Tensor ph = hub->placeholder(params);
+      if (nz) out[0] = gx;
+      if (nadd) out[1] = gx;
+      if (ns) out[2] = ph;
+      if (nq) out[3] = ph;
+      if (nbias) out[4] = ph;
+      tick(T_ACT_BWD_HUB, t2, t3);
+      tick(T_ACT_BWD_LAUNCH, t3, t4);
+      tick(T_ACT_BWD, t0, now_ns());
+      return out;
+    }
+    Tensor gr = at::empty({3}, z.options());
+    Tensor ws = at::empty({(int64_t)nb}, z.options().dtype(at::kByte));
+    check(A.mhaq_fq_act_relu_bwd(fptr(z), fptr(g), fptr_or_null(ga), fptr_mut(gx), n, fptr(params), (int)method, d.seed,
+                                 d.offset, d.offset_dev, fptr_mut(gr), ws.mutable_data_ptr(), nb, cur_stream(z)),
+          "mhaq_fq_act_relu_bwd");
+    const auto shapes = ctx->saved_data["shapes"].to<std::vector<std::vector<int64_t>>>();
+    if (nz) out[0] = gx;
+    if (nadd) out[1] = gx;
+    if (ns) out[2] = gr.narrow(0, 0, 1).view(shapes[0]);
+    if (nq) out[3] = gr.narrow(0, 1, 1).view(shapes[1]);
+    if (nbias) out[4] = gr.narrow(0, 2, 1).view(shapes[2]);
+    return out;
+  }
+};
+
+// (y, a or None, params, s = params[0:1], hi = params[3:4])
+std::tuple<Tensor, std::optional<Tensor>, Tensor, Tensor, Tensor> act_relu_layer(
+    const Tensor& z, const std::optional<Tensor>& addend, const Tensor& log_s, const Tensor& log_q, const Tensor& b,
+    int64_t method, bool want_act, int64_t hub_id, int64_t slot, int64_t rank) {
+  need_lib();
+  MHAQ_ON_DEVICE_OF(z);
+  TORCH_CHECK(z.is_cuda() && z.scalar_type() == at::kFloat && z.is_non_overlapping_and_dense(),
+              "act_relu_layer: z must be a dense float32 device tensor");
+  const bool has_add = addend.has_value() && addend->defined();
+  TORCH_CHECK(!has_add || (addend->device() == z.device() && addend->scalar_type() == at::kFloat &&
+                           addend->sizes() == z.sizes() && addend->strides() == z.strides()),
+              "act_relu_layer: addend must have z's device, dtype, shape and strides");
+  TORCH_CHECK(!has_add || want_act, "act_relu_layer: with an addend the ReLU output is an output of the op (want_act)");
+  TORCH_CHECK(method == MHAQ_FQ_STE || method == MHAQ_FQ_LSQ || method == MHAQ_FQ_EWGS,
+              "act_relu_layer: STE, LSQ or EWGS");
+  TORCH_CHECK(log_s.numel() == 1 && log_q.numel() == 1 && b.numel() == 1 && log_s.is_cuda() && log_q.is_cuda() &&
+                  b.is_cuda() && log_s.scalar_type() == at::kFloat && log_q.scalar_type() == at::kFloat &&
+                  b.scalar_type() == at::kFloat,
+              "act_relu_layer: log_act_s / log_act_q / act_b must be one-element float32 device tensors");
+  const int64_t t0 = now_ns();
+  auto out = ActReluFn::apply(z, addend, log_s, log_q, b, method, want_act, hub_id, slot, rank);
+  const Tensor& params = out[1];
+  std::tuple<Tensor, std::optional<Tensor>, Tensor, Tensor, Tensor> res{
+      out[0], want_act ? std::optional<Tensor>(out[2]) : std::nullopt, params, params.narrow(0, 0, 1),
+      params.narrow(0, 3, 1)};
   tick(T_ACT_FWD, t0, now_ns());
   return res;
 }
@@ -1183,6 +1309,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("method"), py::arg("r_sign") = py::none(), py::arg("hub") = 0, py::arg("slot") = 0, py::arg("rank") = 0);
 
   // weight layers
+  m.def("act_relu_layer", &act_relu_layer, py::arg("z"), py::arg("addend"), py::arg("log_act_s"), py::arg("log_act_q"),
+        py::arg("act_b"), py::arg("method"), py::arg("want_act"), py::arg("hub") = 0, py::arg("slot") = 0,
+        py::arg("rank") = 0);
   m.def("weight_layer", &weight_layer, py::arg("w"), py::arg("log_wght_s"), py::arg("method"),
         py::arg("r_sign") = py::none(), py::arg("zp_grad") = false, py::arg("pre") = py::none(), py::arg("rank") = 0);
   m.def("weight_layer_pt", &weight_layer_pt, py::arg("w"), py::arg("log_wght_s"), py::arg("method"),

@@ -105,6 +105,47 @@ class NoisyAct(nn.Module):
             y, _ = ops.fake_quant_act_layer(x, self.log_act_s, self.log_act_q, self.act_b, method)
         return y
 
+    def can_fuse_relu(self, z, addend=None) -> bool:
+        """True when forward_fused serves this call: training mode, the STE / LSQ / EWGS hot path, dense float32 device
+        tensors (addend with z's strides) and no hook on this module (a hook must see the module's own forward)."""
+        if not self.training or self.disable or type(self) is not NoisyAct:
+            return False
+        if self._forward_hooks or self._forward_pre_hooks or self._backward_hooks or self._backward_pre_hooks:
+            return False
+        if not (z.is_cuda and z.dtype is torch.float32 and ops._is_dense(z)):
+            return False
+        if addend is not None and not (addend.dtype is torch.float32 and addend.device == z.device
+                                       and addend.shape == z.shape and addend.stride() == z.stride()):
+            return False
+        try:
+            return ops._method_value(self.Q.qnmethod) != QNMethod.AEWGS.value
+        except AttributeError:
+            return False
+
+    def forward_fused(self, z, addend=None, want_act=False):
+        """forward(relu(z [+ addend])) with the ReLU and the add inside the quantizer's kernels (ops.act_relu_layer):
+        returns (y, a) -- a = relu(z [+ addend]) when want_act (always with an addend), else None.  The training hot path
+        of forward(): same hub routing, same published Quantizer attributes.  Call only when can_fuse_relu() holds."""
+        Q = self.Q
+        qm = Q.qnmethod
+        if qm is not Q.__dict__.get("_qm_seen"):
+            Q._qm_int = ops._method_value(qm)
+            Q._qm_seen = qm
+        method = Q._qm_int
+        want_act = bool(want_act or addend is not None)
+        ref = self.__dict__.get("_hub")
+        routed = None
+        if ref is not None and ref.hub is not None:
+            routed = ref.hub.take(ref.slot)
+        if routed is not None:
+            y, a, params, s, hi = ops.act_relu_layer(z, addend, routed[0], routed[1], routed[2], method, want_act, ref)
+        else:
+            y, a, params, s, hi = ops.act_relu_layer(z, addend, self.log_act_s, self.log_act_q, self.act_b, method,
+                                                     want_act)
+        Q.scale, Q.max_val = s, hi
+        Q.zero_point = Q.min_val = self._parameters["act_b"]
+        return y, a
+
     def _publish(self, params):
         """Keep the Quantizer's public attributes current for side consumers (model_stats, observers)."""
         self.Q.scale = params[0:1]

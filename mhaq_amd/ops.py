@@ -499,6 +499,22 @@ def act_layer_routed(x, routed, method: int, ref):
     return _E.act_layer(x, routed[0], routed[1], routed[2], method, None, ref.hub.id, ref.slot, _rank())
 
 
+def act_relu_layer(z, addend, log_act_s, log_act_q, act_b, method: int, want_act: bool, hub_slot=None):
+    """relu -> NoisyAct (mid-block) and add -> relu -> NoisyAct (block end) in the quantizer's own launches
+    (mhaq_fq_act_relu_fwd / _bwd; compiled node ActReluFn): a = relu(z [+ addend]), y = fake_quant(a).  Returns
+    (y, a or None, params, params[0:1], params[3:4]); `a` (the ReLU output, for its other consumers) only with want_act.
+    Every value equals what torch.relu / torch.add + fake_quant_act_layer + autograd give.  z: a dense float32 device
+    tensor, addend with z's strides; method STE / LSQ / EWGS as an integer (the caller -- NoisyAct.forward_fused,
+    fused_blocks.py -- has checked all of this: anything else raises here)."""
+    global _seeded, _E
+    if not _seeded:
+        rng.ensure_seeded()
+        _seeded = True
+        _E = _ext()
+    hub, slot = (hub_slot[0].id, hub_slot[1]) if hub_slot is not None else (0, 0)
+    return _E.act_relu_layer(z, addend, log_act_s, log_act_q, act_b, method, want_act, hub, slot, _rank())
+
+
 @_on_device
 @torch.no_grad()
 def fake_quant_act_layer_eval(x, log_act_s, log_act_q, act_b):

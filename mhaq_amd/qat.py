@@ -55,6 +55,9 @@ class QATConfig:
     # model (multi.py): one launch -- and, for AEWGS under data parallelism, one packed statistics all-reduce -- per
     # group instead of per layer.  0 = every layer keeps its own backward launch.
     weight_backward_group_elems: int = 4 << 20
+    # ReLU and residual add of nets.BasicBlock / the nets.ResNet18 stem inside the activation quantizer's kernels
+    # (fused_blocks.py; value-identical to the separate modules).  MHAQ_FUSE_BLOCKS=0 in the environment switches it off.
+    fuse_blocks: bool = True
     criterion: nn.Module = field(default_factory=nn.CrossEntropyLoss)
     # mixed precision (the reference trainer's `precision = "bf16-mixed"`, training/trainer.py:126): torch.bfloat16 runs
     # the teacher and student forwards, the loss and validate_step's forward under torch.autocast; the activation
@@ -206,6 +209,10 @@ class QATTrainer:
             calibrate_activations(net, calib_batches, cfg.calib_act_bit, minmax_fn=minmax_fn)
         if self.distributed and cfg.sync_batchnorm and self.device.type == "cuda":
             net = nn.SyncBatchNorm.convert_sync_batchnorm(net)
+        if cfg.fuse_blocks and layers is None and self.device.type == "cuda":
+            from . import fused_blocks
+            if fused_blocks.enabled_by_env():
+                fused_blocks.install(net)
         self.net = net
         self.teacher_stream = None
         if cfg.distillation and cfg.overlap_teacher and self.device.type == "cuda":
