@@ -178,26 +178,97 @@ Draw draw_signs(bool has_r_sign, int64_t method, int64_t rank, const Tensor& lik
   return d;
 }
 
+// ------------------------------------------------------------------------------------------------ handles and tables
+// Hubs and plans are handed to Python as integer ids.  A registry is never destroyed (heap-allocated, see its two
+// instances): a static map would free device tensors and HIP events from a static destructor, after the HIP runtime and
+// the interpreter are gone.
+template <class T>
+struct Registry {
+  const char* const what;
+  std::mutex mu;
+  std::unordered_map<int64_t, std::shared_ptr<T>> items;
+  int64_t next = 1;
+  explicit Registry(const char* w) : what(w) {}
+
+  std::shared_ptr<T> get(int64_t id) {
+    std::lock_guard<std::mutex> g(mu);
+    auto it = items.find(id);
+    if (it == items.end()) throw MhaqError(std::string(what) + " " + std::to_string(id) + " no longer exists");
+    return it->second;
+  }
+  int64_t add(std::shared_ptr<T> item) { std::lock_guard<std::mutex> g(mu); items[next] = std::move(item); return next++; }
+  void erase(int64_t id) { std::lock_guard<std::mutex> g(mu); items.erase(id); }
+};
+
+// pinned staging + async copy on the current stream; the caching host allocator keeps `host` until the copy has run
+std::pair<Tensor, Tensor> upload(const void* bytes, size_t nbytes, const Tensor& like) {
+  Tensor host = at::empty({(int64_t)nbytes}, at::TensorOptions().dtype(at::kByte).pinned_memory(true));
+  std::memcpy(host.mutable_data_ptr(), bytes, nbytes);
+  Tensor dev = host.to(like.device(), /*non_blocking=*/true);
+  return {dev, host};
+}
+
+// Device descriptor tables keyed by the pointers they hold, allocated and uploaded on a miss.  A table handed out WHILE
+// A CAPTURE WAS ACTIVE is held until release_captured() -- a captured hipGraph has baked its address into its launches;
+// eager tables live in a small LRU (a table the stream still reads stays valid: the allocator orders reuse).  Not
+// thread-safe: the owner's mutex guards it.
+// (Two mechanisms on purpose: the keys here repeat step after step, so a miss may allocate.  TablePool below serves keys
+// that change every step -- its entries are allocated up front and refilled in place behind an event.)
+struct TableCache {
+  struct Entry { Tensor dev, host; bool captured = false; uint64_t stamp = 0; };
+  std::map<std::vector<int64_t>, Entry> entries;
+  uint64_t clock = 0;
+
+  // `make_descs()` -> std::vector of descriptors: the bytes to upload, built only on a miss
+  template <class MakeDescs>
+  Tensor get(const std::vector<int64_t>& key, size_t eager_capacity, const Tensor& like, MakeDescs make_descs) {
+    const bool cap = capturing();
+    auto it = entries.find(key);
+    if (it == entries.end()) {
+      const auto descs = make_descs();
+      auto up = upload(descs.data(), descs.size() * sizeof(descs[0]), like);
+      if (!cap) {
+        size_t eager = entries.size() - captured();
+        while (eager >= eager_capacity) {
+          auto victim = entries.end();
+          for (auto jt = entries.begin(); jt != entries.end(); ++jt)
+            if (!jt->second.captured && (victim == entries.end() || jt->second.stamp < victim->second.stamp)) victim = jt;
+          entries.erase(victim);
+          --eager;
+        }
+      }
+      it = entries.emplace(key, Entry{up.first, up.second, cap, 0}).first;
+    }
+    it->second.captured = it->second.captured || cap;
+    it->second.stamp = ++clock;
+    return it->second.dev;
+  }
+
+  void release_captured() {
+    for (auto it = entries.begin(); it != entries.end();) it = it->second.captured ? entries.erase(it) : std::next(it);
+  }
+  size_t captured() const {
+    return std::count_if(entries.begin(), entries.end(), [](auto& kv) { return kv.second.captured; });
+  }
+};
+
 // ------------------------------------------------------------------------------------------------ activation hub
 // One finalize launch for every NoisyAct quantizer of a backward pass (mhaq_amd/act_hub.py describes the scheme).
-// Lifetime rules for device memory a captured hipGraph may have baked into its launches: a descriptor table or
-// workspace that was handed out WHILE A CAPTURE WAS ACTIVE is held until release_captured(); everything else is
-// ordinary caching-allocator memory -- eager tables live in a small LRU, an outgrown eager workspace is simply
-// dropped (the allocator orders its reuse behind the kernels that read it).
+// Its workspaces follow the lifetime rule of its descriptor tables (TableCache): one handed out WHILE A CAPTURE WAS ACTIVE
+// is held until release_captured() (outgrown: in `retired`); an outgrown eager workspace is simply dropped (the allocator
+// orders its reuse behind the kernels that read it).
 struct Hub {
   struct Pending { int64_t slot, nparts; Tensor ws; };
-  struct Table { Tensor dev, host; bool captured = false; uint64_t stamp = 0; };
   std::mutex mu;
   int64_t n = 0;
   std::vector<Tensor> ws;
   std::vector<char> ws_captured;
   std::vector<Pending> pending;
-  std::map<std::vector<int64_t>, Table> tables;
+  TableCache tables;
   std::vector<Tensor> retired;
   std::vector<std::vector<int64_t>> shapes;   // parameter shapes of this step's begin()
   std::unordered_map<int, Tensor> placeholders;
   Tensor last_table;
-  uint64_t clock = 0;
   static constexpr size_t kEagerTables = 4;
 
   Tensor workspace(int64_t slot, int64_t nbytes, const Tensor& like) {
@@ -222,44 +293,18 @@ struct Hub {
     std::lock_guard<std::mutex> g(mu);
     retired.clear();
     std::fill(ws_captured.begin(), ws_captured.end(), 0);
-    for (auto it = tables.begin(); it != tables.end();) it = it->second.captured ? tables.erase(it) : std::next(it);
+    tables.release_captured();
   }
 };
 
-// The registries are never destroyed (heap-allocated on first use): a static map would free device tensors and HIP events
-// from a static destructor, after the HIP runtime and the interpreter are gone.
-std::mutex g_hub_mu;
-std::unordered_map<int64_t, std::shared_ptr<Hub>>& g_hubs = *new std::unordered_map<int64_t, std::shared_ptr<Hub>>();
-int64_t g_next_hub = 1;
-
-std::shared_ptr<Hub> hub_get(int64_t id) {
-  std::lock_guard<std::mutex> g(g_hub_mu);
-  auto it = g_hubs.find(id);
-  if (it == g_hubs.end()) throw MhaqError("ActGradHub " + std::to_string(id) + " no longer exists");
-  return it->second;
-}
+Registry<Hub>& g_hubs = *new Registry<Hub>("ActGradHub");
 
 int64_t hub_create(int64_t n) {
   auto h = std::make_shared<Hub>();
   h->n = n;
   h->ws.resize(n);
   h->ws_captured.assign(n, 0);
-  std::lock_guard<std::mutex> g(g_hub_mu);
-  g_hubs[g_next_hub] = h;
-  return g_next_hub++;
-}
-
-void hub_destroy(int64_t id) {
-  std::lock_guard<std::mutex> g(g_hub_mu);
-  g_hubs.erase(id);
-}
-
-// pinned staging + async copy on the current stream; the caching host allocator keeps `host` until the copy has run
-std::pair<Tensor, Tensor> upload(const void* bytes, size_t nbytes, const Tensor& like) {
-  Tensor host = at::empty({(int64_t)nbytes}, at::TensorOptions().dtype(at::kByte).pinned_memory(true));
-  std::memcpy(host.mutable_data_ptr(), bytes, nbytes);
-  Tensor dev = host.to(like.device(), /*non_blocking=*/true);
-  return {dev, host};
+  return g_hubs.add(std::move(h));
 }
 
 class HubFn : public torch::autograd::Function<HubFn> {
@@ -267,7 +312,7 @@ class HubFn : public torch::autograd::Function<HubFn> {
   static variable_list forward(AutogradContext* ctx, int64_t hub_id, at::TensorList params) {
     ctx->saved_data["hub"] = hub_id;
     ctx->set_materialize_grads(false);
-    auto hub = hub_get(hub_id);
+    auto hub = g_hubs.get(hub_id);
     std::lock_guard<std::mutex> g(hub->mu);
     hub->pending.clear();
     hub->shapes.clear();
@@ -282,7 +327,7 @@ class HubFn : public torch::autograd::Function<HubFn> {
 
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
     struct Scope { int64_t t0 = now_ns(); ~Scope() { tick(T_HUB_BWD, t0, now_ns()); } } scope;
-    auto hub = hub_get(ctx->saved_data["hub"].toInt());
+    auto hub = g_hubs.get(ctx->saved_data["hub"].toInt());
     std::lock_guard<std::mutex> g(hub->mu);
     variable_list out(1 + grads.size());
     std::vector<Hub::Pending> pending;
@@ -296,31 +341,14 @@ class HubFn : public torch::autograd::Function<HubFn> {
       key.push_back(p.nparts);
       key.push_back((int64_t)(uintptr_t)p.ws.const_data_ptr());
     }
-    const bool cap = capturing();
-    auto it = hub->tables.find(key);
-    if (it == hub->tables.end()) {
+    hub->last_table = hub->tables.get(key, Hub::kEagerTables, like, [&] {
       std::vector<mhaq_act_finalize_desc> descs(pending.size());
       for (size_t j = 0; j < pending.size(); ++j)
         descs[j] = mhaq_act_finalize_desc{static_cast<const float*>(pending[j].ws.const_data_ptr()), pending[j].nparts};
-      auto up = upload(descs.data(), descs.size() * sizeof(descs[0]), like);
-      if (!cap) {   // eager tables: a small LRU (a table the stream still reads stays valid: the allocator orders reuse)
-        size_t eager = 0;
-        for (auto& kv : hub->tables) eager += !kv.second.captured;
-        while (eager >= Hub::kEagerTables) {
-          auto victim = hub->tables.end();
-          for (auto jt = hub->tables.begin(); jt != hub->tables.end(); ++jt)
-            if (!jt->second.captured && (victim == hub->tables.end() || jt->second.stamp < victim->second.stamp)) victim = jt;
-          hub->tables.erase(victim);
-          --eager;
-        }
-      }
-      it = hub->tables.emplace(key, Hub::Table{up.first, up.second, cap, 0}).first;
-    }
-    it->second.captured = it->second.captured || cap;
-    it->second.stamp = ++hub->clock;
-    hub->last_table = it->second.dev;
+      return descs;
+    });
     Tensor slab = at::empty({(int64_t)pending.size(), 3}, like.options().dtype(at::kFloat));
-    check(A.mhaq_fq_act_bwd_finalize_multi(static_cast<const mhaq_act_finalize_desc*>(it->second.dev.const_data_ptr()),
+    check(A.mhaq_fq_act_bwd_finalize_multi(static_cast<const mhaq_act_finalize_desc*>(hub->last_table.const_data_ptr()),
                                            (int)pending.size(), fptr_mut(slab), cur_stream(slab)),
           "mhaq_fq_act_bwd_finalize_multi");
     // one unbind makes all 3n one-element views (0.15 us each; select + narrow + view per gradient cost 1.2 us)
@@ -343,6 +371,110 @@ class HubFn : public torch::autograd::Function<HubFn> {
 // (the parameters go in as an at::TensorList: Function<T>::apply only unpacks that list type into autograd inputs)
 variable_list hub_begin(int64_t hub_id, const variable_list& params) { need_lib(); return HubFn::apply(hub_id, at::TensorList(params)); }      // (no launch: aliases only)
 
+// ------------------------------------------------------------------------------------------------ shared node pieces
+// save_for_backward of `tensors` plus the explicit sign tensor when there is one (then the LAST saved tensor)
+void save_with_sign(AutogradContext* ctx, variable_list tensors, const std::optional<Tensor>& r_sign) {
+  if (r_sign.has_value() && r_sign->defined()) tensors.push_back(*r_sign);
+  ctx->save_for_backward(std::move(tensors));
+}
+
+// ... and what the three weight nodes keep besides
+void weight_save_ctx(AutogradContext* ctx, variable_list tensors, const std::optional<Tensor>& r_sign, int64_t method,
+                     int64_t rank, const Tensor& log_s) {
+  save_with_sign(ctx, std::move(tensors), r_sign);
+  ctx->saved_data["method"] = method;
+  ctx->saved_data["rank"] = rank;
+  ctx->saved_data["ls_shape"] = log_s.sizes().vec();
+  ctx->set_materialize_grads(false);
+}
+
+// the explicit signs saved behind `k` tensors, or null (then draw_signs decides)
+inline const int8_t* saved_sign(const variable_list& saved, size_t k) {
+  return saved.size() > k ? static_cast<const int8_t*>(saved[k].const_data_ptr()) : nullptr;
+}
+
+// the scale gradient in the shape of the log_wght_s the weight node saved as "ls_shape"
+inline Tensor ls_view(AutogradContext* ctx, const Tensor& gls) {
+  return gls.view(ctx->saved_data["ls_shape"].toIntVector());
+}
+
+void check_act_params(const char* who, const Tensor& log_s, const Tensor& log_q, const Tensor& b) {
+  TORCH_CHECK(log_s.numel() == 1 && log_q.numel() == 1 && b.numel() == 1 && log_s.is_cuda() && log_q.is_cuda() &&
+                  b.is_cuda() && log_s.scalar_type() == at::kFloat && log_q.scalar_type() == at::kFloat &&
+                  b.scalar_type() == at::kFloat,
+              who, ": log_act_s / log_act_q / act_b must be one-element float32 device tensors");
+}
+
+// what both activation nodes leave for act_backward: ints = {method, hub, slot, rank, ...node's own}
+void act_save_ctx(AutogradContext* ctx, std::vector<int64_t> ints, const Tensor& log_s, const Tensor& log_q,
+                  const Tensor& b, const Tensor& params) {
+  if (ints[1] <= 0)            // the hub path hands out placeholders: no shapes needed
+    ctx->saved_data["shapes"] = std::vector<std::vector<int64_t>>{log_s.sizes().vec(), log_q.sizes().vec(), b.sizes().vec()};
+  ctx->saved_data["i"] = std::move(ints);       // one map entry instead of four
+  ctx->mark_non_differentiable({params});
+}
+
+// One activation backward launch as the node's callable sees it.  hub: the *_partials entry point, which leaves the
+// partial rows in ws for the hub's finalize and their count in *nparts; else the full backward, which finishes the three
+// parameter gradients into gr[3].
+struct ActBwdLaunch {
+  const Tensor &x, &g, &ga, &gx, &params;    // ga: undefined unless the node passed one
+  int64_t n; int method; const Draw& d;
+  void* ws; size_t nb; bool hub; float* gr; int32_t* nparts; void* stream;
+};
+struct ActGrads { Tensor gx, gp[3]; };      // gp: dL/dlog_act_s, dL/dlog_act_q, dL/dact_b
+
+// The backward of ActLayerFn and ActReluFn behind their own input checks: x = saved[0], params = saved[1], ic = the
+// node's saved integers, gy / ga the incoming gradients as autograd handed them over (gy undefined: a y nobody used, the
+// quantizer's terms are those of a zero gradient), need0 = needs_input_grad index of log_act_s.  One sign-stream draw
+// (draw_signs: none for explicit signs / LSQ), taken before the hub's lock; `launch(const ActBwdLaunch&)` runs the node's
+// entry point.  With a hub the parameter gradients are its placeholder (HubFn::backward delivers the real ones).
+// t0 / t1: the node's clock at its start and after it has read its saved state (T_ACT_BWD_SAVED).
+template <class Launch>
+ActGrads act_backward(AutogradContext* ctx, int64_t t0, int64_t t1, const variable_list& saved,
+                      const std::vector<int64_t>& ic, const Tensor& gy, const Tensor& ga_in, bool has_r, size_t need0,
+                      Launch launch) {
+  const Tensor& x = saved[0];
+  const Tensor& params = saved[1];
+  const int64_t method = ic[0], hub_id = ic[1], slot = ic[2], rank = ic[3];
+  Tensor g = gy.defined() ? like_layout(gy, x) : at::zeros_like(x);
+  Tensor ga = ga_in.defined() ? like_layout(ga_in, x) : Tensor();
+  ActGrads out;
+  out.gx = at::empty_like(x);
+  const int64_t t2 = now_ns();
+  tick(T_ACT_BWD_SAVED, t0, t1);
+  tick(T_ACT_BWD_ALLOC, t1, t2);
+  const int64_t n = x.numel();
+  const size_t nb = A.mhaq_fq_act_bwd_workspace_bytes(n);
+  const Draw d = draw_signs(has_r, method, rank, x);
+  if (hub_id > 0) {
+    auto hub = g_hubs.get(hub_id);
+    std::lock_guard<std::mutex> lk(hub->mu);
+    Tensor ws = hub->workspace(slot, (int64_t)nb, x);
+    int32_t nparts = 0;
+    const int64_t t3 = now_ns();
+    launch(ActBwdLaunch{x, g, ga, out.gx, params, n, (int)method, d, ws.mutable_data_ptr(), nb, true, nullptr, &nparts,
+                        cur_stream(x)});
+    const int64_t t4 = now_ns();
+    hub->pending.push_back(Hub::Pending{slot, nparts, ws});
+    const Tensor ph = hub->placeholder(params);     // float32 like the parameters (x may be 16-bit)
+    for (int c = 0; c < 3; ++c)
+      if (ctx->needs_input_grad(need0 + c)) out.gp[c] = ph;
+    tick(T_ACT_BWD_HUB, t2, t3);
+    tick(T_ACT_BWD_LAUNCH, t3, t4);
+    tick(T_ACT_BWD, t0, now_ns());
+    return out;
+  }
+  Tensor gr = at::empty({3}, x.options().dtype(at::kFloat));
+  Tensor ws = at::empty({(int64_t)nb}, x.options().dtype(at::kByte));
+  launch(ActBwdLaunch{x, g, ga, out.gx, params, n, (int)method, d, ws.mutable_data_ptr(), nb, false, fptr_mut(gr), nullptr,
+                      cur_stream(x)});
+  const auto shapes = ctx->saved_data["shapes"].to<std::vector<std::vector<int64_t>>>();
+  for (int c = 0; c < 3; ++c)
+    if (ctx->needs_input_grad(need0 + c)) out.gp[c] = gr.narrow(0, c, 1).view(shapes[c]);
+  return out;
+}
+
 // ------------------------------------------------------------------------------------------------ NoisyAct layer op
 // NoisyAct.forward from its learnable parameters (gdnsq_act.py:39-55): returns (y, params[5] = {s, zp, lo, hi, qr}).
 // x float32, or bf16 / fp16 (autocast; mhaq_amd/ops.py decides when): y and gx then have x's dtype, params and the
@@ -364,84 +496,47 @@ class ActLayerFn : public torch::autograd::Function<ActLayerFn> {
                               nullptr, nullptr, nullptr, 0, cur_stream(x)),
             "mhaq_fq_act_fwd");
     tick(T_ACT_FWD_LAUNCH, tl0, now_ns());
-    if (r_sign.has_value() && r_sign->defined()) ctx->save_for_backward({x, params, *r_sign});
-    else ctx->save_for_backward({x, params});
-    ctx->saved_data["i"] = std::vector<int64_t>{method, hub_id, slot, rank};       // one map entry instead of four
-    if (hub_id <= 0)            // the hub path hands out placeholders: no shapes needed
-      ctx->saved_data["shapes"] = std::vector<std::vector<int64_t>>{log_s.sizes().vec(), log_q.sizes().vec(), b.sizes().vec()};
-    ctx->mark_non_differentiable({params});
+    save_with_sign(ctx, {x, params}, r_sign);
+    act_save_ctx(ctx, {method, hub_id, slot, rank}, log_s, log_q, b, params);
     return {y, params};
   }
 
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
     const int64_t t0 = now_ns();
     auto saved = ctx->get_saved_variables();
-    const Tensor& x = saved[0];
-    const Tensor& params = saved[1];
-    const bool has_r = saved.size() > 2;
     const std::vector<int64_t> ic = ctx->saved_data["i"].toIntVector();
-    const int64_t method = ic[0], hub_id = ic[1], slot_i = ic[2], rank_i = ic[3];
     const int64_t t1 = now_ns();
-    const int dt = act_dtype(x);
+    const Tensor& x = saved[0];
     // autograd hands the gradient over in y's dtype (= x's); a 16-bit kernel must not read a float32 stream as 16-bit
     TORCH_CHECK(grads[0].scalar_type() == x.scalar_type(), "act_layer backward: the gradient is ",
                 grads[0].scalar_type(), ", the input ", x.scalar_type());
-    Tensor g = like_layout(grads[0], x);
-    Tensor gx = at::empty_like(x);
-    const int64_t t2 = now_ns();
-    tick(T_ACT_BWD_SAVED, t0, t1);
-    tick(T_ACT_BWD_ALLOC, t1, t2);
-    const int64_t n = x.numel();
-    const size_t nb = A.mhaq_fq_act_bwd_workspace_bytes(n);
-    const Draw d = draw_signs(has_r, method, rank_i, x);
-    const int8_t* r = has_r ? static_cast<const int8_t*>(saved[2].const_data_ptr()) : nullptr;
-    variable_list out(9);
-    const bool nx = ctx->needs_input_grad(0), ns = ctx->needs_input_grad(1), nq = ctx->needs_input_grad(2),
-               nbias = ctx->needs_input_grad(3);
-    if (hub_id > 0) {
-      auto hub = hub_get(hub_id);
-      std::lock_guard<std::mutex> lk(hub->mu);
-      const int64_t slot = slot_i;
-      Tensor ws = hub->workspace(slot, (int64_t)nb, x);
-      int32_t nparts = 0;
-      const int64_t t3 = now_ns();
-      if (dt)
-        check(A.mhaq_fq_act_bwd_partials_x16(x.const_data_ptr(), g.const_data_ptr(), gx.mutable_data_ptr(), n, dt,
-                                             fptr(params), (int)method, r, d.seed, d.offset, d.offset_dev,
-                                             ws.mutable_data_ptr(), nb, &nparts, cur_stream(x)),
+    const int dt = act_dtype(x);
+    const int8_t* r = saved_sign(saved, 2);
+    ActGrads res = act_backward(ctx, t0, t1, saved, ic, grads[0], Tensor(), /*has_r=*/saved.size() > 2, /*need0=*/1,
+                               [&](const ActBwdLaunch& a) {
+      const void *xp = a.x.const_data_ptr(), *gp = a.g.const_data_ptr();
+      void* gxp = a.gx.mutable_data_ptr();
+      const float* pp = fptr(a.params);
+      if (a.hub && dt)
+        check(A.mhaq_fq_act_bwd_partials_x16(xp, gp, gxp, a.n, dt, pp, a.method, r, a.d.seed, a.d.offset, a.d.offset_dev,
+                                             a.ws, a.nb, a.nparts, a.stream),
               "mhaq_fq_act_bwd_partials_x16");
-      else
-        check(A.mhaq_fq_act_bwd_partials(fptr(x), fptr(g), fptr_mut(gx), n, fptr(params), (int)method, r, d.seed,
-                                         d.offset, d.offset_dev, ws.mutable_data_ptr(), nb, &nparts, cur_stream(x)),
+      else if (a.hub)
+        check(A.mhaq_fq_act_bwd_partials(fptr(a.x), fptr(a.g), fptr_mut(a.gx), a.n, pp, a.method, r, a.d.seed, a.d.offset,
+                                         a.d.offset_dev, a.ws, a.nb, a.nparts, a.stream),
               "mhaq_fq_act_bwd_partials");
-      const int64_t t4 = now_ns();
-      hub->pending.push_back(Hub::Pending{slot, nparts, ws});
-      Tensor ph = hub->placeholder(params);     // float32 like the parameters (x may be 16-bit)
-      if (nx) out[0] = gx;
-      if (ns) out[1] = ph;
-      if (nq) out[2] = ph;
-      if (nbias) out[3] = ph;
-      tick(T_ACT_BWD_HUB, t2, t3);
-      tick(T_ACT_BWD_LAUNCH, t3, t4);
-      tick(T_ACT_BWD, t0, now_ns());
-      return out;
-    }
-    Tensor gr = at::empty({3}, x.options().dtype(at::kFloat));
-    Tensor ws = at::empty({(int64_t)nb}, x.options().dtype(at::kByte));
-    if (dt)
-      check(A.mhaq_fq_act_bwd_x16(x.const_data_ptr(), g.const_data_ptr(), gx.mutable_data_ptr(), n, dt, fptr(params),
-                                  (int)method, r, d.seed, d.offset, d.offset_dev, fptr_mut(gr), ws.mutable_data_ptr(), nb,
-                                  cur_stream(x)),
-            "mhaq_fq_act_bwd_x16");
-    else
-      check(A.mhaq_fq_act_bwd(fptr(x), fptr(g), fptr_mut(gx), n, fptr(params), (int)method, r, d.seed, d.offset,
-                              d.offset_dev, fptr_mut(gr), ws.mutable_data_ptr(), nb, cur_stream(x)),
-            "mhaq_fq_act_bwd");
-    const auto shapes = ctx->saved_data["shapes"].to<std::vector<std::vector<int64_t>>>();
-    if (nx) out[0] = gx;
-    if (ns) out[1] = gr.narrow(0, 0, 1).view(shapes[0]);
-    if (nq) out[2] = gr.narrow(0, 1, 1).view(shapes[1]);
-    if (nbias) out[3] = gr.narrow(0, 2, 1).view(shapes[2]);
+      else if (dt)
+        check(A.mhaq_fq_act_bwd_x16(xp, gp, gxp, a.n, dt, pp, a.method, r, a.d.seed, a.d.offset, a.d.offset_dev, a.gr, a.ws,
+                                    a.nb, a.stream),
+              "mhaq_fq_act_bwd_x16");
+      else
+        check(A.mhaq_fq_act_bwd(fptr(a.x), fptr(a.g), fptr_mut(a.gx), a.n, pp, a.method, r, a.d.seed, a.d.offset,
+                                a.d.offset_dev, a.gr, a.ws, a.nb, a.stream),
+              "mhaq_fq_act_bwd");
+    });
+    variable_list out(9);
+    if (ctx->needs_input_grad(0)) out[0] = std::move(res.gx);
+    for (int c = 0; c < 3; ++c) out[1 + c] = std::move(res.gp[c]);
     return out;
   }
 };
@@ -455,10 +550,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> act_layer(const Tensor& x_in, const T
   MHAQ_ON_DEVICE_OF(x_in);
   TORCH_CHECK(x_in.is_cuda() && (x_in.scalar_type() == at::kFloat || act_dtype(x_in) != 0),
               "act_layer: x must be a float32, bfloat16 or float16 device tensor");
-  TORCH_CHECK(log_s.numel() == 1 && log_q.numel() == 1 && b.numel() == 1 && log_s.is_cuda() && log_q.is_cuda() &&
-                  b.is_cuda() && log_s.scalar_type() == at::kFloat && log_q.scalar_type() == at::kFloat &&
-                  b.scalar_type() == at::kFloat,
-              "act_layer: log_act_s / log_act_q / act_b must be one-element float32 device tensors");
+  check_act_params("act_layer", log_s, log_q, b);
   const int64_t t0 = now_ns();
   const Tensor x = x_in.is_non_overlapping_and_dense() ? x_in : x_in.contiguous();
   auto out = ActLayerFn::apply(x, log_s, log_q, b, method, r_sign, hub_id, slot, rank);
@@ -491,11 +583,8 @@ class ActReluFn : public torch::autograd::Function<ActReluFn> {
     tick(T_ACT_FWD_LAUNCH, tl0, now_ns());
     // relu is idempotent: the backward recomputes a from the ReLU's input (mid-block) or from a itself
     ctx->save_for_backward({want_act ? a : z, params});
-    ctx->saved_data["i"] = std::vector<int64_t>{method, hub_id, slot, rank, (int64_t)want_act, (int64_t)has_add};
-    if (hub_id <= 0)
-      ctx->saved_data["shapes"] = std::vector<std::vector<int64_t>>{log_s.sizes().vec(), log_q.sizes().vec(), b.sizes().vec()};
+    act_save_ctx(ctx, {method, hub_id, slot, rank, (int64_t)want_act, (int64_t)has_add}, log_s, log_q, b, params);
     ctx->set_materialize_grads(false);
-    ctx->mark_non_differentiable({params});
     if (want_act) return {y, params, a};
     return {y, params};
   }
@@ -503,63 +592,29 @@ class ActReluFn : public torch::autograd::Function<ActReluFn> {
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
     const int64_t t0 = now_ns();
     auto saved = ctx->get_saved_variables();
-    const Tensor& z = saved[0];
-    const Tensor& params = saved[1];
     const std::vector<int64_t> ic = ctx->saved_data["i"].toIntVector();
-    const int64_t method = ic[0], hub_id = ic[1], slot_i = ic[2], rank_i = ic[3];
-    const bool has_a = ic[4] != 0;
     variable_list out(10);
-    const bool g_y_def = grads[0].defined(), g_a_def = has_a && grads.size() > 2 && grads[2].defined();
+    const bool g_y_def = grads[0].defined(), g_a_def = ic[4] /*want_act*/ != 0 && grads.size() > 2 && grads[2].defined();
     if (!g_y_def && !g_a_def) return out;
     const int64_t t1 = now_ns();
-    // (a y nobody used: the quantizer's terms are those of a zero gradient)
-    Tensor g = g_y_def ? like_layout(grads[0], z) : at::zeros_like(z);
-    Tensor ga = g_a_def ? like_layout(grads[2], z) : Tensor();
-    Tensor gx = at::empty_like(z);
-    const int64_t t2 = now_ns();
-    tick(T_ACT_BWD_SAVED, t0, t1);
-    tick(T_ACT_BWD_ALLOC, t1, t2);
-    const int64_t n = z.numel();
-    const size_t nb = A.mhaq_fq_act_bwd_workspace_bytes(n);
-    const Draw d = draw_signs(false, method, rank_i, z);
     // (needs_input_grad counts the tensor inputs that were present: an absent addend takes no slot)
     const size_t e = ic[5] != 0 ? 1 : 0;
-    const bool nz = ctx->needs_input_grad(0), nadd = e && ctx->needs_input_grad(1), ns = ctx->needs_input_grad(1 + e),
-               nq = ctx->needs_input_grad(2 + e), nbias = ctx->needs_input_grad(3 + e);
-    if (hub_id > 0) {
-      auto hub = hub_get(hub_id);
-      std::lock_guard<std::mutex> lk(hub->mu);
-      Tensor ws = hub->workspace(slot_i, (int64_t)nb, z);
-      int32_t nparts = 0;
-      const int64_t t3 = now_ns();
-      check(A.mhaq_fq_act_relu_bwd_partials(fptr(z), fptr(g), fptr_or_null(ga), fptr_mut(gx), n, fptr(params), (int)method,
-                                            d.seed, d.offset, d.offset_dev, ws.mutable_data_ptr(), nb, &nparts,
-                                            cur_stream(z)),
-            "mhaq_fq_act_relu_bwd_partials");
-      const int64_t t4 = now_ns();
-      hub->pending.push_back(Hub::Pending{slot_i, nparts, ws});
-      Tensor ph = hub->placeholder(params);
-      if (nz) out[0] = gx;
-      if (nadd) out[1] = gx;
-      if (ns) out[2] = ph;
-      if (nq) out[3] = ph;
-      if (nbias) out[4] = ph;
-      tick(T_ACT_BWD_HUB, t2, t3);
-      tick(T_ACT_BWD_LAUNCH, t3, t4);
-      tick(T_ACT_BWD, t0, now_ns());
-      return out;
-    }
-    Tensor gr = at::empty({3}, z.options());
-    Tensor ws = at::empty({(int64_t)nb}, z.options().dtype(at::kByte));
-    check(A.mhaq_fq_act_relu_bwd(fptr(z), fptr(g), fptr_or_null(ga), fptr_mut(gx), n, fptr(params), (int)method, d.seed,
-                                 d.offset, d.offset_dev, fptr_mut(gr), ws.mutable_data_ptr(), nb, cur_stream(z)),
-          "mhaq_fq_act_relu_bwd");
-    const auto shapes = ctx->saved_data["shapes"].to<std::vector<std::vector<int64_t>>>();
-    if (nz) out[0] = gx;
-    if (nadd) out[1] = gx;
-    if (ns) out[2] = gr.narrow(0, 0, 1).view(shapes[0]);
-    if (nq) out[3] = gr.narrow(0, 1, 1).view(shapes[1]);
-    if (nbias) out[4] = gr.narrow(0, 2, 1).view(shapes[2]);
+    ActGrads res = act_backward(ctx, t0, t1, saved, ic, grads[0], g_a_def ? grads[2] : Tensor(), /*has_r=*/false,
+                                /*need0=*/1 + e,
+                               [](const ActBwdLaunch& a) {
+      if (a.hub)
+        check(A.mhaq_fq_act_relu_bwd_partials(fptr(a.x), fptr(a.g), fptr_or_null(a.ga), fptr_mut(a.gx), a.n, fptr(a.params),
+                                              a.method, a.d.seed, a.d.offset, a.d.offset_dev, a.ws, a.nb, a.nparts,
+                                              a.stream),
+              "mhaq_fq_act_relu_bwd_partials");
+      else
+        check(A.mhaq_fq_act_relu_bwd(fptr(a.x), fptr(a.g), fptr_or_null(a.ga), fptr_mut(a.gx), a.n, fptr(a.params), a.method,
+                                     a.d.seed, a.d.offset, a.d.offset_dev, a.gr, a.ws, a.nb, a.stream),
+              "mhaq_fq_act_relu_bwd");
+    });
+    if (e && ctx->needs_input_grad(1)) out[1] = res.gx;    // z and addend take the one gradient
+    if (ctx->needs_input_grad(0)) out[0] = std::move(res.gx);
+    for (int c = 0; c < 3; ++c) out[2 + c] = std::move(res.gp[c]);
     return out;
   }
 };
@@ -579,10 +634,7 @@ std::tuple<Tensor, std::optional<Tensor>, Tensor, Tensor, Tensor> act_relu_layer
   TORCH_CHECK(!has_add || want_act, "act_relu_layer: with an addend the ReLU output is an output of the op (want_act)");
   TORCH_CHECK(method == MHAQ_FQ_STE || method == MHAQ_FQ_LSQ || method == MHAQ_FQ_EWGS,
               "act_relu_layer: STE, LSQ or EWGS");
-  TORCH_CHECK(log_s.numel() == 1 && log_q.numel() == 1 && b.numel() == 1 && log_s.is_cuda() && log_q.is_cuda() &&
-                  b.is_cuda() && log_s.scalar_type() == at::kFloat && log_q.scalar_type() == at::kFloat &&
-                  b.scalar_type() == at::kFloat,
-              "act_relu_layer: log_act_s / log_act_q / act_b must be one-element float32 device tensors");
+  check_act_params("act_relu_layer", log_s, log_q, b);
   const int64_t t0 = now_ns();
   auto out = ActReluFn::apply(z, addend, log_s, log_q, b, method, want_act, hub_id, slot, rank);
   const Tensor& params = out[1];
@@ -629,13 +681,8 @@ class WeightLayerFn : public torch::autograd::Function<WeightLayerFn> {
                                  fptr_mut(lwq), cur_stream(w)),
             "mhaq_fq_wlayer_fwd");
     }
-    if (r_sign.has_value() && r_sign->defined()) ctx->save_for_backward({w, s, zp, mx, *r_sign});
-    else ctx->save_for_backward({w, s, zp, mx});
-    ctx->saved_data["method"] = method;
-    ctx->saved_data["rank"] = rank;
+    weight_save_ctx(ctx, {w, s, zp, mx}, r_sign, method, rank, log_s);
     ctx->saved_data["dist"] = distributed;
-    ctx->saved_data["ls_shape"] = log_s.sizes().vec();
-    ctx->set_materialize_grads(false);
     // zp_grad = the quantized-bias mode (gdnsq_conv2d.py:86-94): the bias quantizer reuses this layer's s and zp and
     // sends gradient into both, so both stay differentiable outputs
     if (!zp_grad) ctx->mark_non_differentiable({s, zp});
@@ -663,14 +710,13 @@ class WeightLayerFn : public torch::autograd::Function<WeightLayerFn> {
     const Draw d = draw_signs(has_r, method, ctx->saved_data["rank"].toInt(), w);
     check(A.mhaq_fq_wlayer_bwd(fptr(w), fptr(G), fptr_mut(gw), fptr_mut(gls), fptr(s), fptr(zp), fptr(mx),
                                fptr_or_null(g_lwq), co, row, (int)method, fptr_or_null(stats), fptr_or_null(gzp_extra),
-                               has_r ? static_cast<const int8_t*>(saved[4].const_data_ptr()) : nullptr, d.seed, d.offset,
-                               d.offset_dev, cur_stream(w)),
+                               saved_sign(saved, 4), d.seed, d.offset, d.offset_dev, cur_stream(w)),
           "mhaq_fq_wlayer_bwd");
     if (grads[2].defined())     // gradient reaching s from the quantized bias: exp2 backward, grad * s * ln2
       gls = gls + at::mul(at::mul(grads[2].reshape({co}), s), 0.69314718055994531);
     variable_list out(8);
     out[0] = gw;
-    out[1] = gls.view(ctx->saved_data["ls_shape"].toIntVector());
+    out[1] = ls_view(ctx, gls);
     return out;
   }
 };
@@ -700,6 +746,12 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> weight_layer(const Tensor& w_in, cons
   return {out[0], out[1].view(shp), out[2].view(shp), out[3]};
 }
 
+// what weight_layer_pt / _ptl return from their node's (wq, aux = {s, zp, ..}, lwq): (wq, zp 0-dim, s [1], lwq [1])
+std::tuple<Tensor, Tensor, Tensor, Tensor> pt_result(const variable_list& out) {
+  const Tensor& aux = out[1];
+  return {out[0], aux.select(0, 1), aux.narrow(0, 0, 1), out[2]};
+}
+
 // PER_TENSOR weight layer small enough for one workgroup (every CIFAR ResNet-20 / RFDN layer): one launch per
 // direction from log_wght_s, regulariser input included.  Returns (wq, aux[4] = {s, zp, max, lwq}, lwq[1]).
 class WeightLayerPTFn : public torch::autograd::Function<WeightLayerPTFn> {
@@ -711,12 +763,7 @@ class WeightLayerPTFn : public torch::autograd::Function<WeightLayerPTFn> {
     check(A.mhaq_fq_wlayer_pt_fwd(fptr(w), fptr_mut(wq), fptr(log_s), w.numel(), fptr_mut(aux), cur_stream(w)),
           "mhaq_fq_wlayer_pt_fwd");
     Tensor lwq = aux.narrow(0, 3, 1).clone();
-    if (r_sign.has_value() && r_sign->defined()) ctx->save_for_backward({w, aux, *r_sign});
-    else ctx->save_for_backward({w, aux});
-    ctx->saved_data["method"] = method;
-    ctx->saved_data["rank"] = rank;
-    ctx->saved_data["ls_shape"] = log_s.sizes().vec();
-    ctx->set_materialize_grads(false);
+    weight_save_ctx(ctx, {w, aux}, r_sign, method, rank, log_s);
     ctx->mark_non_differentiable({aux});
     return {wq, aux, lwq};
   }
@@ -732,12 +779,11 @@ class WeightLayerPTFn : public torch::autograd::Function<WeightLayerPTFn> {
     Tensor gls = at::empty({1}, w.options());
     const Draw d = draw_signs(has_r, method, ctx->saved_data["rank"].toInt(), w);
     check(A.mhaq_fq_wlayer_pt_bwd(fptr(w), fptr(G), fptr_mut(gw), fptr_mut(gls), fptr(aux), fptr_or_null(g_lwq), w.numel(),
-                                  (int)method, has_r ? static_cast<const int8_t*>(saved[2].const_data_ptr()) : nullptr,
-                                  d.seed, d.offset, d.offset_dev, cur_stream(w)),
+                                  (int)method, saved_sign(saved, 2), d.seed, d.offset, d.offset_dev, cur_stream(w)),
           "mhaq_fq_wlayer_pt_bwd");
     variable_list out(5);
     out[0] = gw;
-    out[1] = gls.view(ctx->saved_data["ls_shape"].toIntVector());
+    out[1] = ls_view(ctx, gls);
     return out;
   }
 };
@@ -752,8 +798,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> weight_layer_pt(const Tensor& w_in, c
               "weight_layer_pt: weight and a one-element log_wght_s must be float32 device tensors");
   const Tensor w = w_in.contiguous();
   auto out = WeightLayerPTFn::apply(w, log_s, method, r_sign, rank);
-  const Tensor& aux = out[1];
-  return {out[0], aux.select(0, 1), aux.narrow(0, 0, 1), out[2]};
+  return pt_result(out);
 }
 
 // PER_TENSOR weight layer of any size (and every PER_TENSOR AEWGS layer): streaming launches, regulariser input and its
@@ -770,13 +815,8 @@ class WeightLayerPTLFn : public torch::autograd::Function<WeightLayerPTLFn> {
                                    cur_stream(w)),
           "mhaq_fq_wlayer_ptl_fwd");
     Tensor lwq = aux.narrow(0, 3, 1).clone();
-    if (r_sign.has_value() && r_sign->defined()) ctx->save_for_backward({w, aux, *r_sign});
-    else ctx->save_for_backward({w, aux});
-    ctx->saved_data["method"] = method;
-    ctx->saved_data["rank"] = rank;
+    weight_save_ctx(ctx, {w, aux}, r_sign, method, rank, log_s);
     ctx->saved_data["dist"] = distributed;
-    ctx->saved_data["ls_shape"] = log_s.sizes().vec();
-    ctx->set_materialize_grads(false);
     ctx->mark_non_differentiable({aux});
     return {wq, aux, lwq};
   }
@@ -811,13 +851,12 @@ class WeightLayerPTLFn : public torch::autograd::Function<WeightLayerPTLFn> {
     Tensor ws = at::empty({(int64_t)nb}, w.options().dtype(at::kByte));
     const Draw d = draw_signs(has_r, method, ctx->saved_data["rank"].toInt(), w);
     check(A.mhaq_fq_wlayer_ptl_bwd(fptr(w), fptr(G), fptr_mut(gw), fptr_mut(gls), fptr(aux), fptr_or_null(g_lwq), n,
-                                   (int)method, fptr_or_null(stats), period,
-                                   has_r ? static_cast<const int8_t*>(saved[2].const_data_ptr()) : nullptr, d.seed,
-                                   d.offset, d.offset_dev, ws.mutable_data_ptr(), nb, stream),
+                                   (int)method, fptr_or_null(stats), period, saved_sign(saved, 2), d.seed, d.offset,
+                                   d.offset_dev, ws.mutable_data_ptr(), nb, stream),
           "mhaq_fq_wlayer_ptl_bwd");
     variable_list out(6);
     out[0] = gw;
-    out[1] = gls.view(ctx->saved_data["ls_shape"].toIntVector());
+    out[1] = ls_view(ctx, gls);
     return out;
   }
 };
@@ -834,8 +873,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> weight_layer_ptl(const Tensor& w_in, 
   // statistics are per physical position within a dim-0 slice
   const Tensor w = w_in.is_non_overlapping_and_dense() ? w_in : w_in.contiguous();
   auto out = WeightLayerPTLFn::apply(w, log_s, method, r_sign, rank, g_dist_active.load());
-  const Tensor& aux = out[1];
-  return {out[0], aux.select(0, 1), aux.narrow(0, 0, 1), out[2]};
+  return pt_result(out);
 }
 
 // ------------------------------------------------------------------------------------------------ weight plan / groups
@@ -919,24 +957,12 @@ struct Plan {
   int64_t nlayers = 0, total_elems = 0, total_co = 0, max_row = 0;
   std::vector<int64_t> co, row, elem_off, chan_off, methods, group_of;
   std::vector<Group> groups;
-  // forward table cache: pointers of (weights, log scales) -> device table; captured entries are held, eager ones LRU
-  struct FwdTable { Tensor dev, host; bool captured = false; uint64_t stamp = 0; };
-  std::map<std::vector<int64_t>, FwdTable> fwd_tables;
-  uint64_t clock = 0;
+  TableCache fwd_tables;    // pointers of (weights, log scales) -> device table
   Tensor cur_wq, cur_aux;   // this step's model-wide forward
   static constexpr size_t kEagerTables = 2;
 };
 
-std::mutex g_plan_mu;
-std::unordered_map<int64_t, std::shared_ptr<Plan>>& g_plans = *new std::unordered_map<int64_t, std::shared_ptr<Plan>>();
-int64_t g_next_plan = 1;
-
-std::shared_ptr<Plan> plan_get(int64_t id) {
-  std::lock_guard<std::mutex> g(g_plan_mu);
-  auto it = g_plans.find(id);
-  if (it == g_plans.end()) throw MhaqError("weight plan " + std::to_string(id) + " no longer exists");
-  return it->second;
-}
+Registry<Plan>& g_plans = *new Registry<Plan>("weight plan");
 
 int64_t plan_create(std::vector<int64_t> co, std::vector<int64_t> row, std::vector<int64_t> methods,
                     std::vector<std::pair<int64_t, int64_t>> groups) {
@@ -972,14 +998,7 @@ int64_t plan_create(std::vector<int64_t> co, std::vector<int64_t> row, std::vect
     }
     p->groups.push_back(std::move(g));
   }
-  std::lock_guard<std::mutex> gl(g_plan_mu);
-  g_plans[g_next_plan] = p;
-  return g_next_plan++;
-}
-
-void plan_destroy(int64_t id) {
-  std::lock_guard<std::mutex> g(g_plan_mu);
-  g_plans.erase(id);
+  return g_plans.add(std::move(p));
 }
 
 // One launch quantizes every layer of the plan; returns (wq_all, aux_all, per layer: wq view with the weight's own
@@ -987,7 +1006,7 @@ void plan_destroy(int64_t id) {
 std::tuple<Tensor, Tensor, std::vector<std::vector<Tensor>>> plan_forward(int64_t plan_id, const std::vector<Tensor>& ws,
                                                                            const std::vector<Tensor>& lss) {
   need_lib();
-  auto p = plan_get(plan_id);
+  auto p = g_plans.get(plan_id);
   std::lock_guard<std::mutex> g(p->mu);
   const int64_t n = p->nlayers;
   TORCH_CHECK((int64_t)ws.size() == n && (int64_t)lss.size() == n, "plan_forward: expected ", n, " weights and log scales");
@@ -1007,32 +1026,16 @@ std::tuple<Tensor, Tensor, std::vector<std::vector<Tensor>>> plan_forward(int64_
   }
   for (int64_t i = 0; i < n; ++i) key.push_back((int64_t)(uintptr_t)lss[i].const_data_ptr());
   const Tensor& like = ws[0];
-  const bool cap = capturing();
-  auto it = p->fwd_tables.find(key);
-  if (it == p->fwd_tables.end()) {
+  const Tensor table = p->fwd_tables.get(key, Plan::kEagerTables, like, [&] {
     std::vector<mhaq_wlayer_desc> descs(n);
     for (int64_t i = 0; i < n; ++i)
       descs[i] = mhaq_wlayer_desc{fptr(ws[i]), fptr(lss[i]), nullptr, nullptr, p->co[i], p->row[i], p->elem_off[i],
                                   p->chan_off[i]};
-    auto up = upload(descs.data(), descs.size() * sizeof(descs[0]), like);
-    if (!cap) {
-      size_t eager = 0;
-      for (auto& kv : p->fwd_tables) eager += !kv.second.captured;
-      while (eager >= Plan::kEagerTables) {
-        auto victim = p->fwd_tables.end();
-        for (auto jt = p->fwd_tables.begin(); jt != p->fwd_tables.end(); ++jt)
-          if (!jt->second.captured && (victim == p->fwd_tables.end() || jt->second.stamp < victim->second.stamp)) victim = jt;
-        p->fwd_tables.erase(victim);
-        --eager;
-      }
-    }
-    it = p->fwd_tables.emplace(key, Plan::FwdTable{up.first, up.second, cap, 0}).first;
-  }
-  it->second.captured = it->second.captured || cap;
-  it->second.stamp = ++p->clock;
+    return descs;
+  });
   Tensor wq_all = at::empty({p->total_elems}, like.options());
   Tensor aux_all = at::empty({4, p->total_co}, like.options());
-  check(A.mhaq_fq_wlayer_fwd_multi(static_cast<const mhaq_wlayer_desc*>(it->second.dev.const_data_ptr()), (int)n,
+  check(A.mhaq_fq_wlayer_fwd_multi(static_cast<const mhaq_wlayer_desc*>(table.const_data_ptr()), (int)n,
                                    p->total_co, p->max_row, fptr_mut(wq_all), fptr_mut(aux_all), cur_stream(like)),
         "mhaq_fq_wlayer_fwd_multi");
   p->cur_wq = wq_all;
@@ -1060,7 +1063,7 @@ class WeightGroupFn : public torch::autograd::Function<WeightGroupFn> {
  public:
   static variable_list forward(AutogradContext* ctx, int64_t plan_id, int64_t gi, at::TensorList tensors, int64_t rank,
                                bool distributed) {
-    auto p = plan_get(plan_id);
+    auto p = g_plans.get(plan_id);
     std::lock_guard<std::mutex> lk(p->mu);
     const Group& grp = p->groups.at(gi);
     const int64_t n = grp.n;
@@ -1091,7 +1094,7 @@ class WeightGroupFn : public torch::autograd::Function<WeightGroupFn> {
   }
 
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    auto p = plan_get(ctx->saved_data["plan"].toInt());
+    auto p = g_plans.get(ctx->saved_data["plan"].toInt());
     std::unique_lock<std::mutex> lk(p->mu);
     Group& grp = p->groups.at(ctx->saved_data["group"].toInt());
     const int64_t n = grp.n;
@@ -1282,20 +1285,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   });
   m.def("set_dist_active", [](bool v) { g_dist_active.store(v); });
 
-  // activation hub
+  // activation hub and the activation nodes
   m.def("hub_create", &hub_create);
-  m.def("hub_destroy", &hub_destroy);
+  m.def("hub_destroy", [](int64_t id) { g_hubs.erase(id); });
   m.def("hub_begin", &hub_begin);
-  m.def("hub_clear_pending", [](int64_t id) { auto h = hub_get(id); std::lock_guard<std::mutex> g(h->mu); h->pending.clear(); });
-  m.def("hub_release_captured", [](int64_t id) { hub_get(id)->release_captured(); });
+  m.def("hub_clear_pending", [](int64_t id) { auto h = g_hubs.get(id); std::lock_guard<std::mutex> g(h->mu); h->pending.clear(); });
+  m.def("hub_release_captured", [](int64_t id) { g_hubs.get(id)->release_captured(); });
   m.def("hub_state", [](int64_t id) {
-    auto h = hub_get(id);
+    auto h = g_hubs.get(id);
     std::lock_guard<std::mutex> g(h->mu);
     py::dict d;
-    size_t captured = 0;
-    for (auto& kv : h->tables) captured += kv.second.captured;
-    d["tables"] = h->tables.size();
-    d["captured_tables"] = captured;
+    d["tables"] = h->tables.entries.size();
+    d["captured_tables"] = h->tables.captured();
     d["retired"] = h->retired.size();
     d["pending"] = h->pending.size();
     d["has_table"] = h->last_table.defined();
@@ -1307,32 +1308,34 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   });
   m.def("act_layer", &act_layer, py::arg("x"), py::arg("log_act_s"), py::arg("log_act_q"), py::arg("act_b"),
         py::arg("method"), py::arg("r_sign") = py::none(), py::arg("hub") = 0, py::arg("slot") = 0, py::arg("rank") = 0);
-
-  // weight layers
   m.def("act_relu_layer", &act_relu_layer, py::arg("z"), py::arg("addend"), py::arg("log_act_s"), py::arg("log_act_q"),
         py::arg("act_b"), py::arg("method"), py::arg("want_act"), py::arg("hub") = 0, py::arg("slot") = 0,
         py::arg("rank") = 0);
+
+  // weight layers
   m.def("weight_layer", &weight_layer, py::arg("w"), py::arg("log_wght_s"), py::arg("method"),
         py::arg("r_sign") = py::none(), py::arg("zp_grad") = false, py::arg("pre") = py::none(), py::arg("rank") = 0);
   m.def("weight_layer_pt", &weight_layer_pt, py::arg("w"), py::arg("log_wght_s"), py::arg("method"),
         py::arg("r_sign") = py::none(), py::arg("rank") = 0);
   m.def("weight_layer_ptl", &weight_layer_ptl, py::arg("w"), py::arg("log_wght_s"), py::arg("method"),
         py::arg("r_sign") = py::none(), py::arg("rank") = 0);
+
+  // weight plan / groups
   m.def("plan_create", &plan_create);
-  m.def("plan_destroy", &plan_destroy);
+  m.def("plan_destroy", [](int64_t id) { g_plans.erase(id); });
   m.def("plan_forward", &plan_forward);
   m.def("plan_group_apply", &plan_group_apply);
   m.def("plan_release_captured", [](int64_t id) {
-    auto p = plan_get(id);
+    auto p = g_plans.get(id);
     std::lock_guard<std::mutex> g(p->mu);
     for (auto& grp : p->groups) if (grp.pool) grp.pool->release_captured();
-    for (auto it = p->fwd_tables.begin(); it != p->fwd_tables.end();) it = it->second.captured ? p->fwd_tables.erase(it) : std::next(it);
+    p->fwd_tables.release_captured();
   });
   m.def("plan_state", [](int64_t id) {
-    auto p = plan_get(id);
+    auto p = g_plans.get(id);
     std::lock_guard<std::mutex> g(p->mu);
     py::dict d;
-    d["fwd_tables"] = p->fwd_tables.size();
+    d["fwd_tables"] = p->fwd_tables.entries.size();
     py::list pools;
     for (auto& grp : p->groups) {
       py::dict e;

@@ -109,17 +109,6 @@ def backward_groups(sizes, methods, min_elems):
     return out
 
 
-class _PoolView:
-    """Read-only picture of a group's descriptor-table pool in the compiled binding (torch_binding.cpp: TablePool):
-    device tables + pinned staging buffers allocated up front (nothing may be allocated inside a hipGraph capture, and
-    a captured upload re-reads its staging buffer at every replay -- so an entry filled during a capture is held
-    until release_captured()); eager entries are recycled least-recently-used, after their previous upload has run."""
-
-    def __init__(self, state):
-        self.keys = [object() if i < state["used"] else None for i in range(state["size"])]
-        self.held = [i < state["held"] for i in range(state["size"])]
-
-
 class _WeightGroup:
     """Consecutive per-channel layers whose backward is ONE launch (plus, for AEWGS under data parallelism, one
     statistics launch and ONE packed all-reduce).  The forward is the model-wide launch of this step; the group's
@@ -135,10 +124,6 @@ class _WeightGroup:
         self.max_row = max(plan.row[i] for i in self.idx)
         self.method = plan.methods[first]
         self.outs = None
-
-    @property
-    def pool(self):
-        return _PoolView(_ext().plan_state(self.plan.plan_id)["pools"][self.index])
 
     def take(self, i):
         """(wq, lwq) of layer `i` of the plan as outputs of the group's autograd node."""
@@ -199,7 +184,6 @@ class MultiTensorWeightQuant:
             raise ValueError("all batched layers must use the same estimator")
         self.method = methods.pop()
         self.methods = [ops._method_value(m.Q.qnmethod) for m in self.layers]
-        self._joint_tables = {}
         self.nlayers = len(self.layers)
         self.shape = [tuple(m.weight.shape) for m in self.layers]
         self.per_tensor = [m.qscheme != QScheme.PER_CHANNEL for m in self.layers]
@@ -238,12 +222,10 @@ class MultiTensorWeightQuant:
         except Exception:             # interpreter shutdown
             pass
 
-    @property
-    def _tables(self):
-        """One entry per uploaded forward pointer table (joint mode: the dict of device tables itself)."""
-        if self.plan_id is None:
-            return self._joint_tables
-        return [None] * _ext().plan_state(self.plan_id)["fwd_tables"]
+    def state(self) -> dict:
+        """{'fwd_tables', 'pools': [{'size', 'used', 'held'} per backward group]} of the C++ plan (torch_binding.cpp:
+        TableCache, TablePool); {} in joint mode, which has no plan."""
+        return {} if self.plan_id is None else _ext().plan_state(self.plan_id)
 
     def release_captured(self) -> None:
         """Drop the descriptor tables held for captured hipGraphs (call when those graphs are gone)."""

@@ -484,19 +484,23 @@ def _act_layer(x, log_act_s, log_act_q, act_b, method, r_sign=None, hub_slot=Non
     return _ext().act_layer(x, log_act_s, log_act_q, act_b, m, r_sign, hub, slot, _rank())
 
 
-_seeded = False
 _E = None
+
+
+def _seeded_ext():
+    """The extension handle of the hot paths, cached once the sign stream has a seed (a seed, once set, is only ever
+    replaced by another seed)."""
+    global _E
+    if _E is None:
+        rng.ensure_seeded()
+        _E = _ext()
+    return _E
 
 
 def act_layer_routed(x, routed, method: int, ref):
     """NoisyAct's hot path under an ActGradHub: x is a float32 device tensor, `routed` the hub's aliases of the three
     parameters (device tensors by construction), `ref` the module's HubRef."""
-    global _seeded, _E
-    if not _seeded:
-        rng.ensure_seeded()
-        _seeded = True           # a seed, once set, is only ever replaced by another seed
-        _E = _ext()
-    return _E.act_layer(x, routed[0], routed[1], routed[2], method, None, ref.hub.id, ref.slot, _rank())
+    return _seeded_ext().act_layer(x, routed[0], routed[1], routed[2], method, None, ref.hub.id, ref.slot, _rank())
 
 
 def act_relu_layer(z, addend, log_act_s, log_act_q, act_b, method: int, want_act: bool, hub_slot=None):
@@ -506,25 +510,23 @@ def act_relu_layer(z, addend, log_act_s, log_act_q, act_b, method: int, want_act
     Every value equals what torch.relu / torch.add + fake_quant_act_layer + autograd give.  z: a dense float32 device
     tensor, addend with z's strides; method STE / LSQ / EWGS as an integer (the caller -- NoisyAct.forward_fused,
     fused_blocks.py -- has checked all of this: anything else raises here)."""
-    global _seeded, _E
-    if not _seeded:
-        rng.ensure_seeded()
-        _seeded = True
-        _E = _ext()
     hub, slot = (hub_slot[0].id, hub_slot[1]) if hub_slot is not None else (0, 0)
-    return _E.act_relu_layer(z, addend, log_act_s, log_act_q, act_b, method, want_act, hub, slot, _rank())
+    return _seeded_ext().act_relu_layer(z, addend, log_act_s, log_act_q, act_b, method, want_act, hub, slot, _rank())
 
 
 @_on_device
 @torch.no_grad()
 def fake_quant_act_layer_eval(x, log_act_s, log_act_q, act_b):
     """Eval-mode NoisyAct in one launch (+ a tiny finalize): (y, params, qstats[2], flags[1]).  A 16-bit x under autocast
-    (autocast_x16) takes mhaq_fq_act_fwd_x16 and gets y in its dtype; another 16-bit x runs on x.float()."""
-    if x.is_cuda and x.dtype in _X16:
-        if autocast_x16(x):
-            return _act_layer_eval_x16(x, log_act_s, log_act_q, act_b)
-        x = x.float()
-    x = _require_cuda_f32(x, "x", any_dense_layout=True)
+    (autocast_x16) takes mhaq_fq_act_fwd_x16 (any dense layout; the workspace is the fp32 query's) and gets y in its
+    dtype; another 16-bit x runs on x.float()."""
+    x16 = x.is_cuda and x.dtype in _X16
+    if x16 and autocast_x16(x):
+        x = x if _is_dense(x) else x.contiguous()
+        name, dtype = "mhaq_fq_act_fwd_x16", (_X16[x.dtype],)       # the entry point's extra `dtype` argument
+    else:
+        x = _require_cuda_f32(x.float() if x16 else x, "x", any_dense_layout=True)
+        name, dtype = "mhaq_fq_act_fwd", ()
     dev = x.device
     L = _lib.lib()
     y = torch.empty_like(x)
@@ -533,29 +535,12 @@ def fake_quant_act_layer_eval(x, log_act_s, log_act_q, act_b):
     flags = torch.empty(1, dtype=torch.int32, device=dev)
     nb = L.mhaq_fq_pt_fwd_workspace_bytes(x.numel())
     ws = _workspace(nb, dev)
-    _lib.check(L.mhaq_fq_act_fwd(x.data_ptr(), y.data_ptr(), x.numel(), _scalar(log_act_s, dev, "s").data_ptr(),
-                                 _scalar(log_act_q, dev, "q").data_ptr(), _scalar(act_b, dev, "b").data_ptr(),
-                                 params.data_ptr(), qstats.data_ptr(), flags.data_ptr(), ws.data_ptr(), nb,
-                                 _stream()), "mhaq_fq_act_fwd")
-    return y, params, qstats, flags
-
-
-def _act_layer_eval_x16(x, log_act_s, log_act_q, act_b):
-    """fake_quant_act_layer_eval for a 16-bit x (bf16 / fp16, any dense layout); the workspace is the fp32 query's."""
-    if not _is_dense(x):
-        x = x.contiguous()
-    dev = x.device
-    L = _lib.lib()
-    y = torch.empty_like(x)
-    params = torch.empty(5, dtype=torch.float32, device=dev)
-    qstats = torch.empty(2, dtype=torch.float32, device=dev)
-    flags = torch.empty(1, dtype=torch.int32, device=dev)
-    nb = L.mhaq_fq_pt_fwd_workspace_bytes(x.numel())
-    ws = _workspace(nb, dev)
-    _lib.check(L.mhaq_fq_act_fwd_x16(x.data_ptr(), y.data_ptr(), x.numel(), _X16[x.dtype],
-                                     _scalar(log_act_s, dev, "s").data_ptr(), _scalar(log_act_q, dev, "q").data_ptr(),
-                                     _scalar(act_b, dev, "b").data_ptr(), params.data_ptr(), qstats.data_ptr(),
-                                     flags.data_ptr(), ws.data_ptr(), nb, _stream()), "mhaq_fq_act_fwd_x16")
+    # mhaq_fq_act_fwd(x, y, n, log_s, log_q, b, ...) / mhaq_fq_act_fwd_x16(x, y, n, dtype, log_s, log_q, b, ...): the
+    # same list but for `dtype` right behind n
+    _lib.check(getattr(L, name)(x.data_ptr(), y.data_ptr(), x.numel(), *dtype, _scalar(log_act_s, dev, "s").data_ptr(),
+                                _scalar(log_act_q, dev, "q").data_ptr(), _scalar(act_b, dev, "b").data_ptr(),
+                                params.data_ptr(), qstats.data_ptr(), flags.data_ptr(), ws.data_ptr(), nb,
+                                _stream()), name)
     return y, params, qstats, flags
 
 

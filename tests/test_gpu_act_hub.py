@@ -219,7 +219,7 @@ def _weight_forward_case(M, MultiTensorWeightQuant, channels_last):
         assert torch.equal(out, ref_out)
         assert len(g) == len(ref_g) and all(torch.equal(a, b) for a, b in zip(g, ref_g))
         assert all(m._pre_fwd is None for m in net)                # consumed (or discarded) by the forward
-    assert len(multi._tables) == 1                                 # the pointer table is uploaded once
+    assert multi.state()["fwd_tables"] == 1                        # the pointer table is uploaded once
 
 
 def test_trainer_with_and_without_model_wide_weight_forward_agree_bit_for_bit():

@@ -225,3 +225,47 @@ def test_error_codes_are_the_existing_ones():
                                            None, ws.data_ptr(), ws.numel(), ctypes.byref(npo), ops._stream()) == -3  # EALIGN
     assert L.mhaq_fq_act_relu_fwd(None, None, x.data_ptr(), None, 64, p.data_ptr(), p.data_ptr(), p.data_ptr(),
                                   p.data_ptr(), ops._stream()) == -1
+
+
+@pytest.mark.parametrize("use_hub", [False, True])
+def test_a_backward_draws_one_sign_stream_offset_or_none(use_hub):
+    """Host side only (any size runs the same host code): a backward that launches a random estimator (STE, EWGS) takes
+    exactly ONE offset of the sign stream -- whichever of y and a were used --, LSQ and explicit signs take none; with and
+    without an ActGradHub."""
+    import mhaq_amd as M
+    from mhaq_amd import ops
+    from mhaq_amd.act_hub import ActGradHub
+    z0 = torch.randn(2, 3, 5, 7, device=DEV)
+    g = torch.randn_like(z0)
+    q = _quantizer(M.QNMethod.STE, 0.25)
+    hub = ActGradHub(torch.nn.ModuleList([q])) if use_hub else None
+    ops.manual_seed(3)
+
+    def drawn_by(op, used):
+        """Sign-stream offsets taken by the backward of the outputs `used` of op(z, parameters, hub_slot)."""
+        z = z0.clone().requires_grad_(True)
+        params = (q.log_act_s, q.log_act_q, q.act_b)
+        if hub is not None:
+            hub.begin()
+            params = hub.take(0)
+        outs = op(z, params, (hub, 0) if hub is not None else None)
+        if hub is not None:
+            hub.end()
+        before = ops.rng.drawn()
+        torch.autograd.backward([outs[i] for i in used], [g] * len(used))
+        torch.cuda.synchronize()
+        assert z.grad is not None
+        return ops.rng.drawn() - before
+
+    try:
+        for method, want in (("STE", 1), ("EWGS", 1), ("LSQ", 0)):
+            m = M.QNMethod[method].value
+            for used in ((0,), (1,), (0, 1)):            # y only, a only, both
+                got = drawn_by(lambda z, p, hs: ops.act_relu_layer(z, None, *p, m, True, hub_slot=hs)[:2], used)
+                assert got == want, (method, used, got)
+        r_sign = torch.ones(z0.shape, dtype=torch.int8, device=DEV)
+        for r, want in ((r_sign, 0), (None, 1)):
+            got = drawn_by(lambda z, p, hs: ops.fake_quant_act_layer(z, *p, M.QNMethod.STE, r, hub_slot=hs), (0,))
+            assert got == want, (r is not None, got)
+    finally:
+        q.__dict__.pop("_hub", None)

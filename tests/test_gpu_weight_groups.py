@@ -297,9 +297,8 @@ def test_descriptor_pool_recycles_its_entries_without_mixing_tables():
             wq, zp, s, lwq = ops.fake_quant_weight_layer(m.weight, m.log_wght_s, "LSQ")
             ((wq * Gs[i]).sum() + lwq.sum()).backward()
             assert torch.equal(m.weight.grad, got[i][0]) and torch.equal(m.log_wght_s.grad, got[i][1]), (it, i)
-    pool = plan.groups[0].pool
-    assert len([k for k in pool.keys if k is not None]) == len(pool.keys)        # full, and recycled 12 times
-    assert not any(pool.held)
+    st = plan.state()["pools"][0]
+    assert st["used"] == st["size"] > 0 and st["held"] == 0                     # full, and recycled 12 times
 
 
 PT_SHAPES = [(16, 16, 3, 3), (32, 16, 3, 3), (12, 12, 3, 3), (10, 5, 1, 1), (64, 64, 3, 3), (24, 50, 3, 3)]

@@ -11,7 +11,6 @@ import torch
 
 import mhaq_amd as M
 from mhaq_amd import nets, ops
-from mhaq_amd._ext import ext
 from mhaq_amd.qat import QATConfig, QATTrainer
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 1500
@@ -38,7 +37,7 @@ for mode in (False, True):
         if i in (N // 3, N - 1):
             torch.cuda.synchronize()
             assert bool(torch.isfinite(loss)), (mode, i)
-            marks.append((torch.cuda.memory_allocated(), rss_mb(), tr.act_hub.state(), ext().plan_state(tr.weight_forward.plan_id)))
+            marks.append((torch.cuda.memory_allocated(), rss_mb(), tr.act_hub.state(), tr.weight_forward.state()))
     (m1, r1, h1, p1), (m2, r2, h2, p2) = marks
     print(f"capture_graph={mode}: device MB {m1 / 2**20:.1f} -> {m2 / 2**20:.1f}, peak host RSS MB {r1:.0f} -> {r2:.0f}, "
           f"hub {h1} -> {h2}, plan {p1} -> {p2}, final loss {float(loss):.4f}", flush=True)
