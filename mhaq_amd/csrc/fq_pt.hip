@@ -221,6 +221,13 @@ __global__ __launch_bounds__(kFwdFinalThreads) void pt_fwd_finalize_kernel(const
 // =============================================================== backward
 constexpr int kNAcc = 5;  // d/ds, d/dzp, d/dlo, d/dhi, count(x == zp)
 
+// g != 0 whose product g*s is subnormal or has underflowed to zero.  There the reference's (g*s)/s is the quotient of
+// the ROUNDED product -- up to 1/(2s) subnormal ulps away from g -- and the exact-quotient correction below, which
+// assumes g*s carries g's relative precision, would return g itself: such elements take the IEEE division.
+__device__ __forceinline__ bool product_underflowed(float g, float gq) {
+  return ((__float_as_uint(gq) & 0x7f800000u) == 0u) && (g != 0.f);
+}
+
 // One element of the fused backward.  The quantizer core is recomputed so q and the rounding
 // noise are bit-identical to the forward.  The other two divisions of the reference's graph are
 // by the same wave-uniform scale:
@@ -236,10 +243,12 @@ __device__ inline float bwd_elem(float x, float g, float r, float delta, const B
   const float gq = g * k.s;                                   // dequantize: d(q*s)/dq
   const float gv = gq + noise_grad_v<METHOD>(gq, c.n, delta); // q = v + noise(v)
   float g1;                                                   // v = v1 / s
-  if ((METHOD == MHAQ_FQ_STE || METHOD == MHAQ_FQ_LSQ) && k.fast_div)
+  if ((METHOD == MHAQ_FQ_STE || METHOD == MHAQ_FQ_LSQ) && k.fast_div) {
     g1 = __fmaf_rn(__fmaf_rn(-k.s, g, gv), k.rs, g);
-  else
+    if (__builtin_expect(product_underflowed(g, gq), 0)) g1 = gv / k.s;
+  } else {
     g1 = gv / k.s;
+  }
   const float noise_s = (METHOD == MHAQ_FQ_LSQ) ? gq * c.n : (MHAQ_INV_SQRT3 * gq) * r;
   // d/ds: mul-backward g*q, div-backward -gv*((v1/s)/s), noise estimator term.  For STE/LSQ
   // gv == g*s, so g*q - gv*(v/s) == g*(q - v) == g*noise exactly: one product instead of the
@@ -286,7 +295,8 @@ __device__ __forceinline__ float bwd_elem_fast(float x, float g, float rsc, cons
   const float n = rintf(v) - v;
   const float gq = g * k.s;
   const float gv = __fmaf_rn(gq, 0.f, gq);
-  const float g1 = __fmaf_rn(__fmaf_rn(-k.s, g, gv), k.rs, g);        // == gv / s, correctly rounded
+  float g1 = __fmaf_rn(__fmaf_rn(-k.s, g, gv), k.rs, g);              // == gv / s, correctly rounded ...
+  if (__builtin_expect(product_underflowed(g, gq), 0)) g1 = gv / k.s;   // ... unless g*s lost g's precision
   if (METHOD == MHAQ_FQ_LSQ) acc[0] = __fmaf_rn(g + gq, n, acc[0]);
   else acc[0] = __fmaf_rn(g, n + rsc, acc[0]);
   acc[1] += g - g1;

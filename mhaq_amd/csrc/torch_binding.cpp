@@ -426,7 +426,7 @@ struct ActGrads { Tensor gx, gp[3]; };      // gp: dL/dlog_act_s, dL/dlog_act_q,
 
 // The backward of ActLayerFn and ActReluFn behind their own input checks: x = saved[0], params = saved[1], ic = the
 // node's saved integers, gy / ga the incoming gradients as autograd handed them over (gy undefined: a y nobody used, the
-// quantizer's terms are those of a zero gradient), need0 = needs_input_grad index of log_act_s.  One sign-stream draw
+// quantizer's parameters get zeros), need0 = needs_input_grad index of log_act_s.  One sign-stream draw
 // (draw_signs: none for explicit signs / LSQ), taken before the hub's lock; `launch(const ActBwdLaunch&)` runs the node's
 // entry point.  With a hub the parameter gradients are its placeholder (HubFn::backward delivers the real ones).
 // t0 / t1: the node's clock at its start and after it has read its saved state (T_ACT_BWD_SAVED).
@@ -455,6 +455,8 @@ ActGrads act_backward(AutogradContext* ctx, int64_t t0, int64_t t1, const variab
     const int64_t t3 = now_ns();
     launch(ActBwdLaunch{x, g, ga, out.gx, params, n, (int)method, d, ws.mutable_data_ptr(), nb, true, nullptr, &nparts,
                         cur_stream(x)});
+    // a y nobody used gives its quantizer NO gradient (0 * NaN of a non-finite input is not one): empty rows
+    if (!gy.defined()) ws.narrow(0, 0, 3 * (int64_t)nparts * (int64_t)sizeof(float)).zero_();
     const int64_t t4 = now_ns();
     hub->pending.push_back(Hub::Pending{slot, nparts, ws});
     const Tensor ph = hub->placeholder(params);     // float32 like the parameters (x may be 16-bit)
@@ -469,6 +471,7 @@ ActGrads act_backward(AutogradContext* ctx, int64_t t0, int64_t t1, const variab
   Tensor ws = at::empty({(int64_t)nb}, x.options().dtype(at::kByte));
   launch(ActBwdLaunch{x, g, ga, out.gx, params, n, (int)method, d, ws.mutable_data_ptr(), nb, false, fptr_mut(gr), nullptr,
                       cur_stream(x)});
+  if (!gy.defined()) gr.zero_();             // (as above: an unused y gives no parameter gradient)
   const auto shapes = ctx->saved_data["shapes"].to<std::vector<std::vector<int64_t>>>();
   for (int c = 0; c < 3; ++c)
     if (ctx->needs_input_grad(need0 + c)) out.gp[c] = gr.narrow(0, c, 1).view(shapes[c]);
