@@ -262,6 +262,24 @@ int mhaq_fq_act_relu_bwd_partials(const float* z, const float* g_y, const float*
                                   const uint64_t* offset_dev, void* workspace, size_t workspace_bytes,
                                   int32_t* nparts_out, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Backward of training-mode BatchNorm (torch.nn.BatchNorm2d on a channels_last tensor) from the statistics its forward
+ * saved.  Additive to ABI v4 -- MHAQ_FQ_ABI_VERSION stays 4; a caller discovers these entry points by symbol.
+ *   x, dy, dx       dense fp32 NHWC seen as [m = N*H*W][c]; c % 4 == 0 and c <= 2^22 (else MHAQ_FQ_EUNSUPPORTED);
+ *                   x, dy, dx and `workspace` 16-byte aligned (else MHAQ_FQ_EALIGN)
+ *   mean, invstd    [c], the batch statistics of the forward (invstd = (var + eps)^-1/2)
+ *   weight          [c], NULL = 1
+ *   dbias   = sum_rows dy                                dweight = invstd * sum_rows dy * (x - mean)
+ *   dx      = (weight * invstd) * ((dy - dbias / m) - ((x - mean) * invstd) * (dweight / m))
+ * Any of dx, dweight, dbias may be NULL (dx == NULL skips its launch).  Three launches: partial sums (x and dy read once,
+ * fp32 per lane, one partial row per block in `workspace`), a fixed-order fp64 final sum, the dx stream -- deterministic,
+ * no float atomics.
+ * ---------------------------------------------------------------------- */
+size_t mhaq_fq_bn_bwd_workspace_bytes(int64_t m, int64_t c);
+int mhaq_fq_bn_bwd(const float* x, const float* dy, const float* mean, const float* invstd, const float* weight,
+                   float* dx, float* dweight, float* dbias, int64_t m, int64_t c,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
 /* Whole-tensor min / max (zero point of a PER_TENSOR weight quantizer,
  * gdnsq_conv2d.py:82-83; min/max observer, calib/minmaxobserver.py:19-36).
  * out[0] = min, out[1] = max. */

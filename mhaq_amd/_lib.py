@@ -50,6 +50,9 @@ SIGNATURES = {
     "mhaq_fq_act_relu_fwd": (_int, [_p, _p, _p, _p, _i64, _p, _p, _p, _p, _p]),
     "mhaq_fq_act_relu_bwd": (_int, [_p, _p, _p, _p, _i64, _p, _int, _u64, _u64, _p, _p, _p, _sz, _p]),
     "mhaq_fq_act_relu_bwd_partials": (_int, [_p, _p, _p, _p, _i64, _p, _int, _u64, _u64, _p, _p, _sz, _p, _p]),
+    # training BatchNorm backward from the saved statistics (additive, ABI v4 kept)
+    "mhaq_fq_bn_bwd_workspace_bytes": (_sz, [_i64, _i64]),
+    "mhaq_fq_bn_bwd": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _sz, _p]),
     "mhaq_fq_minmax_workspace_bytes": (_sz, [_i64]),
     "mhaq_fq_minmax": (_int, [_p, _i64, _p, _p, _sz, _p]),
     "mhaq_fq_row_minmax": (_int, [_p, _i64, _i64, _p, _p, _p]),

@@ -1,0 +1,69 @@
+"""Training BatchNorm2d with the framework's forward and the HIP backward (csrc/bn_bwd.hip).
+
+In a float32 channels_last training step the BatchNorm backward is three MIOpen launches per layer on the critical path
+(two reads for dgamma / dbeta, a finalize, two reads and a write for dx) that run well short of the memory rate on all
+but the largest tensors.  The compiled node `bn_train` (csrc/torch_binding.cpp, BatchNormTrainFn) keeps the forward
+exactly as F.batch_norm runs it -- at::_batch_norm_impl_index: y, the saved statistics and the running statistics keep
+their bits -- and replaces only the backward, by mhaq_fq_bn_bwd, where that applies (a dense float32 channels_last device
+tensor with C % 4 == 0); everywhere else the node calls the backward autograd itself would have called.  The gradients
+of the HIP path differ from the stock ones by summation order only.
+
+install() switches the CLASS of every module whose exact type is nn.BatchNorm2d (HipBackwardBatchNorm2d is a subclass
+that adds a forward and nothing else): module names, named_modules() order, state_dict keys, copy.deepcopy and
+isinstance(m, nn.BatchNorm2d) are what they were; SyncBatchNorm and subclasses are left alone.  The decision is taken per
+call: the original forward runs in eval mode, with track_running_stats=False or affine=False, on a CPU tensor and on a
+non-float32 input (so under autocast, where the convolution in front hands over a 16-bit tensor).
+
+MHAQ_BN_BACKWARD=0 in the environment keeps QATTrainer from installing (A/B runs of an unchanged benchmark);
+QATConfig.hip_bn_backward=False does the same per trainer.
+"""
+from __future__ import annotations
+
+import os
+
+import torch
+from torch import nn
+
+ENV_SWITCH = "MHAQ_BN_BACKWARD"
+
+
+def enabled_by_env() -> bool:
+    """False when MHAQ_BN_BACKWARD=0 (or "false" / "off") is set."""
+    return os.environ.get(ENV_SWITCH, "1").strip().lower() not in ("0", "false", "off", "no")
+
+
+class HipBackwardBatchNorm2d(nn.BatchNorm2d):
+    """nn.BatchNorm2d whose training forward goes through the compiled node; nn.BatchNorm2d.forward runs otherwise."""
+
+    def forward(self, input):
+        if (not self.training or not self.track_running_stats or not self.affine or not input.is_cuda
+                or input.dtype != torch.float32 or self.weight.dtype != torch.float32):
+            return super().forward(input)
+        self._check_input_dim(input)
+        # the bookkeeping of _BatchNorm.forward (training mode, tracked statistics)
+        exponential_average_factor = 0.0 if self.momentum is None else self.momentum
+        if self.num_batches_tracked is not None:
+            self.num_batches_tracked.add_(1)
+            if self.momentum is None:
+                exponential_average_factor = 1.0 / float(self.num_batches_tracked)
+            else:
+                exponential_average_factor = self.momentum
+        from . import _ext
+        return _ext.ext().bn_train(input, self.weight, self.bias, self.running_mean, self.running_var,
+                                   exponential_average_factor, self.eps, torch.backends.cudnn.enabled)
+
+
+def install(model: nn.Module) -> int:
+    """Give every nn.BatchNorm2d of `model` (the exact type) the forward above.  Returns the number of modules switched."""
+    switched = 0
+    for m in model.modules():
+        if type(m) is nn.BatchNorm2d:
+            m.__class__ = HipBackwardBatchNorm2d
+            switched += 1
+    return switched
+
+
+def uninstall(model: nn.Module) -> None:
+    for m in model.modules():
+        if type(m) is HipBackwardBatchNorm2d:
+            m.__class__ = nn.BatchNorm2d

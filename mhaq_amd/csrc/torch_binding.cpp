@@ -53,7 +53,8 @@ namespace {
   X(mhaq_fq_potential_loss_fwd) X(mhaq_fq_potential_loss_bwd) X(mhaq_fq_wlayer_ptl_workspace_bytes)                   \
   X(mhaq_fq_wlayer_ptl_fwd) X(mhaq_fq_wlayer_ptl_bwd) X(mhaq_fq_pt_aewgs_colstats_workspace_bytes)                     \
   X(mhaq_fq_pt_aewgs_colstats) X(mhaq_fq_act_fwd_x16) X(mhaq_fq_act_bwd_x16) X(mhaq_fq_act_bwd_partials_x16)                    \
-  X(mhaq_fq_act_relu_fwd) X(mhaq_fq_act_relu_bwd) X(mhaq_fq_act_relu_bwd_partials)
+  X(mhaq_fq_act_relu_fwd) X(mhaq_fq_act_relu_bwd) X(mhaq_fq_act_relu_bwd_partials)                                    \
+  X(mhaq_fq_bn_bwd_workspace_bytes) X(mhaq_fq_bn_bwd)
 
 struct Api {
 #define X(n) decltype(&::n) n = nullptr;
@@ -646,6 +647,95 @@ std::tuple<Tensor, std::optional<Tensor>, Tensor, Tensor, Tensor> act_relu_layer
       params.narrow(0, 3, 1)};
   tick(T_ACT_FWD, t0, now_ns());
   return res;
+}
+
+// ------------------------------------------------------------------------------------------------ BatchNorm backward
+// Training-mode BatchNorm whose FORWARD is the framework's own -- at::_batch_norm_impl_index, what F.batch_norm calls:
+// same dispatch, same kernels, same bits in y, the saved statistics and the running statistics -- and whose BACKWARD
+// runs mhaq_fq_bn_bwd on a dense float32 channels_last tensor with C % 4 == 0.  Everything else takes
+// at::_batch_norm_impl_index_backward with the saved implementation index and reserve: the backward autograd itself
+// would have run.  The gradients of the HIP path differ from it by summation order only.  Once-differentiable.
+inline bool aligned16(const Tensor& t) { return (reinterpret_cast<uintptr_t>(t.const_data_ptr()) & 15) == 0; }
+
+inline bool bn_bwd_eligible(const Tensor& x, const Tensor& w, const Tensor& mean, const Tensor& invstd) {
+  if (!x.is_cuda() || x.scalar_type() != at::kFloat || x.dim() != 4 || x.numel() == 0) return false;
+  if (!x.is_contiguous(at::MemoryFormat::ChannelsLast) || (x.size(1) & 3) || !aligned16(x)) return false;
+  auto stat_ok = [&](const Tensor& t) {
+    return t.defined() && t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == x.size(1);
+  };
+  return stat_ok(mean) && stat_ok(invstd) && (!w.defined() || stat_ok(w));
+}
+
+std::atomic<int64_t> g_bn_hip_backwards{0};   // backwards that took mhaq_fq_bn_bwd (tests: the fallback is never silent)
+
+class BatchNormTrainFn : public torch::autograd::Function<BatchNormTrainFn> {
+ public:
+  static Tensor forward(AutogradContext* ctx, const Tensor& x, const std::optional<Tensor>& w,
+                        const std::optional<Tensor>& b, const std::optional<Tensor>& running_mean,
+                        const std::optional<Tensor>& running_var, double momentum, double eps, bool cudnn_enabled) {
+    auto out = at::_batch_norm_impl_index(x, w, b, running_mean, running_var, /*training=*/true, momentum, eps,
+                                          cudnn_enabled);
+    const bool has_w = w.has_value() && w->defined();
+    ctx->save_for_backward({x, has_w ? *w : Tensor(), std::get<1>(out), std::get<2>(out), std::get<3>(out)});
+    ctx->saved_data["impl"] = std::get<4>(out);
+    ctx->saved_data["eps"] = eps;
+    // read by no training-mode backward; handed on as the framework's own node does, without its version check
+    if (running_mean.has_value() && running_mean->defined()) ctx->saved_data["rm"] = *running_mean;
+    if (running_var.has_value() && running_var->defined()) ctx->saved_data["rv"] = *running_var;
+    ctx->set_materialize_grads(false);
+    return std::get<0>(out);
+  }
+
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    variable_list out(8);
+    if (!grads[0].defined()) return out;
+    TORCH_CHECK(!(at::GradMode::is_enabled() && grads[0].requires_grad()),
+                "bn_train: the node is once-differentiable (no double backward)");
+    at::NoGradGuard no_grad;
+    auto saved = ctx->get_saved_variables();
+    const Tensor &x = saved[0], &w = saved[1], &mean = saved[2], &invstd = saved[3], &reserve = saved[4];
+    const std::array<bool, 3> mask = {ctx->needs_input_grad(0), w.defined() && ctx->needs_input_grad(1),
+                                      ctx->needs_input_grad(2)};
+    if (!bn_bwd_eligible(x, w, mean, invstd)) {
+      auto opt = [](const Tensor& t) { return t.defined() ? std::optional<Tensor>(t) : std::nullopt; };
+      auto get = [&](const char* k) {
+        return ctx->saved_data.count(k) ? std::optional<Tensor>(ctx->saved_data[k].toTensor()) : std::nullopt;
+      };
+      auto g = at::_batch_norm_impl_index_backward(ctx->saved_data["impl"].toInt(), x, grads[0], opt(w), get("rm"),
+                                                   get("rv"), opt(mean), opt(invstd), /*train=*/true,
+                                                   ctx->saved_data["eps"].toDouble(), mask, reserve);
+      if (mask[0]) out[0] = std::get<0>(g);
+      if (mask[1]) out[1] = std::get<1>(g);
+      if (mask[2]) out[2] = std::get<2>(g);
+      return out;
+    }
+    need_lib();
+    const int64_t c = x.size(1), m = x.numel() / c;
+    const Tensor dy = like_layout(grads[0].scalar_type() == at::kFloat ? grads[0] : grads[0].to(at::kFloat), x);
+    Tensor dx = mask[0] ? at::empty_like(x) : Tensor();
+    Tensor dw = mask[1] ? at::empty_like(w) : Tensor();
+    Tensor db = mask[2] ? at::empty({c}, mean.options()) : Tensor();
+    const size_t nb = A.mhaq_fq_bn_bwd_workspace_bytes(m, c);
+    Tensor ws = at::empty({(int64_t)nb}, x.options().dtype(at::kByte));
+    check(A.mhaq_fq_bn_bwd(fptr(x), fptr(dy), fptr(mean), fptr(invstd), fptr_or_null(w), mask[0] ? fptr_mut(dx) : nullptr,
+                           mask[1] ? fptr_mut(dw) : nullptr, mask[2] ? fptr_mut(db) : nullptr, m, c, ws.mutable_data_ptr(),
+                           nb, cur_stream(x)),
+          "mhaq_fq_bn_bwd");
+    g_bn_hip_backwards.fetch_add(1, std::memory_order_relaxed);
+    out[0] = dx;
+    out[1] = dw;
+    out[2] = db;
+    return out;
+  }
+};
+
+Tensor bn_train(const Tensor& x, const std::optional<Tensor>& w, const std::optional<Tensor>& b,
+                const std::optional<Tensor>& running_mean, const std::optional<Tensor>& running_var, double momentum,
+                double eps, bool cudnn_enabled) {
+  TORCH_CHECK(w.has_value() && w->defined() && b.has_value() && b->defined(),
+              "bn_train: an affine BatchNorm (weight and bias) is required");
+  MHAQ_ON_DEVICE_OF(x);
+  return BatchNormTrainFn::apply(x, w, b, running_mean, running_var, momentum, eps, cudnn_enabled);
 }
 
 // ------------------------------------------------------------------------------------------------ weight layer ops
@@ -1314,6 +1404,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("act_relu_layer", &act_relu_layer, py::arg("z"), py::arg("addend"), py::arg("log_act_s"), py::arg("log_act_q"),
         py::arg("act_b"), py::arg("method"), py::arg("want_act"), py::arg("hub") = 0, py::arg("slot") = 0,
         py::arg("rank") = 0);
+
+  // training BatchNorm: the framework's forward, the HIP backward
+  m.def("bn_train", &bn_train, py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("running_mean"),
+        py::arg("running_var"), py::arg("momentum"), py::arg("eps"), py::arg("cudnn_enabled") = true);
+
+  m.def("bn_hip_backwards", []() { return g_bn_hip_backwards.load(); },
+        "number of BatchNorm backwards so far that ran the HIP kernels instead of the framework's backward");
 
   // weight layers
   m.def("weight_layer", &weight_layer, py::arg("w"), py::arg("log_wght_s"), py::arg("method"),

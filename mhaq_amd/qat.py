@@ -58,6 +58,9 @@ class QATConfig:
     # ReLU and residual add of nets.BasicBlock / the nets.ResNet18 stem inside the activation quantizer's kernels
     # (fused_blocks.py; value-identical to the separate modules).  MHAQ_FUSE_BLOCKS=0 in the environment switches it off.
     fuse_blocks: bool = True
+    # backward of every nn.BatchNorm2d on the HIP kernels of csrc/bn_bwd.hip; the forward stays the framework's, bit for bit
+    # (bn_backward.py).  MHAQ_BN_BACKWARD=0 in the environment switches it off.
+    hip_bn_backward: bool = True
     criterion: nn.Module = field(default_factory=nn.CrossEntropyLoss)
     # mixed precision (the reference trainer's `precision = "bf16-mixed"`, training/trainer.py:126): torch.bfloat16 runs
     # the teacher and student forwards, the loss and validate_step's forward under torch.autocast; the activation
@@ -213,6 +216,10 @@ class QATTrainer:
             from . import fused_blocks
             if fused_blocks.enabled_by_env():
                 fused_blocks.install(net)
+        if cfg.hip_bn_backward and layers is None and self.device.type == "cuda":
+            from . import bn_backward
+            if bn_backward.enabled_by_env():
+                bn_backward.install(net)
         self.net = net
         self.teacher_stream = None
         if cfg.distillation and cfg.overlap_teacher and self.device.type == "cuda":
