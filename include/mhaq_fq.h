@@ -280,6 +280,32 @@ int mhaq_fq_bn_bwd(const float* x, const float* dy, const float* mean, const flo
                    float* dx, float* dweight, float* dbias, int64_t m, int64_t c,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * The ResNet stem's max pool behind a training-mode BatchNorm: max_pool2d(kernel 3, stride 2, padding 1, dilation 1,
+ * ceil_mode = false) of a dense fp32 NHWC tensor [n, h, w, c], oh = (h - 1) / 2 + 1 and ow likewise.  Additive to ABI v4.
+ *   c % 4 == 0, c <= 2^22 and n * h * w < 2^31 (else MHAQ_FQ_EUNSUPPORTED); t, p, x, g, dx and `workspace` 16-byte
+ *   aligned, `code` 4-byte aligned (else MHAQ_FQ_EALIGN); errors are returned before any launch.
+ *
+ * mhaq_fq_maxpool3s2_fwd: p[n, oh, ow, c] = the window maxima of t, code[n, oh, ow, c] (one byte each) = kh * 3 + kw of the
+ * chosen element.  The selection is that of torch's channels_last kernel: the in-range positions in kh, then kw order,
+ * starting at -inf, replaced on  val > max || isnan(val).  A window in which nothing replaces the start (all -inf) has
+ * torch's index 0, element (0, 0) of the plane: code 4 in the window (0, 0), which contains it, and code 9 ("none chosen",
+ * matched by no input element: torch's backward sends that window's gradient nowhere either) in every other window.
+ *
+ * mhaq_fq_bn_pool_bwd: mhaq_fq_bn_bwd on x[n, h, w, c] whose dy is the pool's backward of the pooled gradient
+ * g[n, oh, ow, c], computed on the fly and never stored, with the values of torch's channels_last max_pool2d backward, bit
+ * for bit: where ONE window covers (ih, iw), dy[n, ih, iw, .] is its g if its code names (ih, iw) and 0.0f if not; where
+ * two or four do, dy = 0.0f plus g of every covering window whose code names (ih, iw), added in ascending oh, then ascending
+ * ow.  Same partition, sums and workspace layout as mhaq_fq_bn_bwd(m = n * h * w): dx, dweight, dbias and the partial rows
+ * are the bits that call gives on the materialized dy.
+ * ---------------------------------------------------------------------- */
+int mhaq_fq_maxpool3s2_fwd(const float* t, float* p, uint8_t* code, int64_t n, int64_t h, int64_t w, int64_t c,
+                           void* stream);
+size_t mhaq_fq_bn_pool_bwd_workspace_bytes(int64_t n, int64_t h, int64_t w, int64_t c);
+int mhaq_fq_bn_pool_bwd(const float* x, const float* g, const uint8_t* code, const float* mean, const float* invstd,
+                        const float* weight, float* dx, float* dweight, float* dbias, int64_t n, int64_t h, int64_t w,
+                        int64_t c, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Whole-tensor min / max (zero point of a PER_TENSOR weight quantizer,
  * gdnsq_conv2d.py:82-83; min/max observer, calib/minmaxobserver.py:19-36).
  * out[0] = min, out[1] = max. */

@@ -14,6 +14,10 @@ isinstance(m, nn.BatchNorm2d) are what they were; SyncBatchNorm and subclasses a
 call: the original forward runs in eval mode, with track_running_stats=False or affine=False, on a CPU tensor and on a
 non-float32 input (so under autocast, where the convolution in front hands over a 16-bit tensor).
 
+forward_pooled() is the same module with the ResNet stem's max pool behind it in one node (fused_blocks.FusedResNet18 calls
+it; csrc/torch_binding.cpp, BatchNormPoolTrainFn): same forward bits, and a backward that never materializes the pool's
+gradient.
+
 MHAQ_BN_BACKWARD=0 in the environment keeps QATTrainer from installing (A/B runs of an unchanged benchmark);
 QATConfig.hip_bn_backward=False does the same per trainer.
 """
@@ -35,12 +39,14 @@ def enabled_by_env() -> bool:
 class HipBackwardBatchNorm2d(nn.BatchNorm2d):
     """nn.BatchNorm2d whose training forward goes through the compiled node; nn.BatchNorm2d.forward runs otherwise."""
 
-    def forward(self, input):
-        if (not self.training or not self.track_running_stats or not self.affine or not input.is_cuda
-                or input.dtype != torch.float32 or self.weight.dtype != torch.float32):
-            return super().forward(input)
-        self._check_input_dim(input)
-        # the bookkeeping of _BatchNorm.forward (training mode, tracked statistics)
+    def takes_node(self, input) -> bool:
+        """True when this call goes through the compiled node (forward() and forward_pooled() decide alike)."""
+        return not (not self.training or not self.track_running_stats or not self.affine or not input.is_cuda
+                    or input.dtype != torch.float32 or self.weight.dtype != torch.float32)
+
+    def _step_average_factor(self) -> float:
+        """The bookkeeping of _BatchNorm.forward (training mode, tracked statistics): counts the batch, returns the
+        exponential average factor of this call."""
         exponential_average_factor = 0.0 if self.momentum is None else self.momentum
         if self.num_batches_tracked is not None:
             self.num_batches_tracked.add_(1)
@@ -48,9 +54,24 @@ class HipBackwardBatchNorm2d(nn.BatchNorm2d):
                 exponential_average_factor = 1.0 / float(self.num_batches_tracked)
             else:
                 exponential_average_factor = self.momentum
+        return exponential_average_factor
+
+    def _node(self, entry, input):
+        self._check_input_dim(input)
+        return entry(input, self.weight, self.bias, self.running_mean, self.running_var, self._step_average_factor(),
+                     self.eps, torch.backends.cudnn.enabled)
+
+    def forward(self, input):
+        if not self.takes_node(input):
+            return super().forward(input)
         from . import _ext
-        return _ext.ext().bn_train(input, self.weight, self.bias, self.running_mean, self.running_var,
-                                   exponential_average_factor, self.eps, torch.backends.cudnn.enabled)
+        return self._node(_ext.ext().bn_train, input)
+
+    def forward_pooled(self, input):
+        """max_pool2d(self(input), 3, 2, 1) as one node (bn_pool_train: the BatchNorm output is not kept, the backward
+        gathers its dy from the pooled gradient).  Call only when takes_node(input) holds."""
+        from . import _ext
+        return self._node(_ext.ext().bn_pool_train, input)
 
 
 def install(model: nn.Module) -> int:

@@ -9,6 +9,13 @@
 // The mean is NOT folded into an additive constant (B * x + D cancels when |mean| >> sigma): every term above is the
 // closed form's own, so the error of dx is bounded on |dy| + |dbias| / M + |xhat| * |dweight| / M.
 // Deterministic: fixed partition, fixed-order sums, no float atomics, no last-block ticket.
+//
+// Where dy comes from is a template argument of the two streaming kernels: a tensor in memory (DyMem, mhaq_fq_bn_bwd) or
+// the gradient of a 3x3 / stride 2 / padding 1 max pool behind the BatchNorm, gathered on the fly from the pooled gradient
+// and a 1-byte argmax code per output (DyPool, mhaq_fq_bn_pool_bwd; the codes are written by maxpool3s2_fwd_kernel at the
+// end of this file).  Partition, sums, finalize and the dx expression are one code for both.
+#include <type_traits>
+
 #include "fq_common.hpp"
 
 namespace mhaq {
@@ -23,6 +30,120 @@ __device__ __forceinline__ void bn_st4(float* p, int64_t vidx, vf4 v) {
   __builtin_nontemporal_store(v, reinterpret_cast<vf4*>(p) + vidx);
 }
 
+// ---------------------------------------------------------------- where dy comes from
+// A source hands out, per float4 of x, a bundle of loads (issued with x's, before anything waits) and later the four dy
+// values out of it.  `Walk` follows a lane's rows through the reduction: (n, ih, iw) of a row, advanced by a fixed row
+// step without a division.
+struct DyMem {
+  const float* __restrict__ dy;
+  static constexpr int kDxWaves = 8;               // the occupancy the dx kernel is held to below kBnBigElems
+  struct Walk {
+    __device__ __forceinline__ Walk(const DyMem&, uint32_t, uint32_t) {}
+    __device__ __forceinline__ void next() {}
+  };
+  struct Loads { vf4 v; };
+  template <bool NT>
+  __device__ __forceinline__ Loads load(int64_t vidx, const Walk&, bool, uint32_t, uint32_t) const {
+    return Loads{bn_ld4<NT>(dy, vidx)};
+  }
+  template <bool NT>
+  __device__ __forceinline__ Loads load_at_pixel(int64_t vidx, uint32_t, bool, uint32_t, uint32_t) const {
+    return Loads{bn_ld4<NT>(dy, vidx)};
+  }
+  __device__ __forceinline__ void value(const Loads& l, float (&o)[4]) const {
+    o[0] = l.v.x; o[1] = l.v.y; o[2] = l.v.z; o[3] = l.v.w;
+  }
+};
+
+// dy[n, ih, iw, .] of max_pool2d(kernel 3, stride 2, padding 1) from the pooled gradient g[n, oh, ow, .] and the argmax
+// code (kh * 3 + kw of the chosen element, one byte per output element).  The windows that cover row ih are
+//   oh = ih / 2          with kh = 1 + ih % 2, always there, and
+//   oh = ih / 2 + 1      with kh = 0, for an odd ih when that row of windows exists,
+// likewise along iw: 1, 2 or 4 candidates.  The value is that of the framework's channels_last backward, bit for bit: with ONE
+// candidate window dy is its g where its code names (ih, iw) and 0.0f where not (no add: a -0.0f arrives as -0.0f); with
+// more, dy = 0.0f and g of every candidate whose code names (ih, iw) is added in ascending oh, then ascending ow, in fp32.
+// All four (g, code) pairs are loaded whatever the parity: a candidate that does not exist re-reads its neighbour's address
+// and can match no code.
+constexpr uint32_t kPoolNoCode = 0xFFu;           // codes are 0 .. 8, and kPoolNoneChosen:
+constexpr uint32_t kPoolNoneChosen = 9u;          // a window that chose no element (maxpool3s2_fwd_kernel)
+struct DyPool {
+  const float* __restrict__ g;
+  const uint8_t* __restrict__ code;
+  uint32_t h, w, oh, ow;
+  static constexpr int kDxWaves = 5;               // 84 VGPRs with the gather's loads in flight: 8 waves would spill
+  struct Walk {
+    uint32_t n, ih, iw, dn, dh, dw, h, w;
+    // row -> (n, ih, iw) once per lane; step = dn * h * w + dh * w + dw
+    __device__ __forceinline__ Walk(const DyPool& s, uint32_t row, uint32_t step) : h(s.h), w(s.w) {
+      const uint32_t q = row / w, sq = step / w;
+      iw = row - q * w;
+      n = q / h;
+      ih = q - n * h;
+      dw = step - sq * w;
+      dn = sq / h;
+      dh = sq - dn * h;
+    }
+    __device__ __forceinline__ void next() {
+      iw += dw;
+      const bool cw = iw >= w;
+      iw -= cw ? w : 0u;
+      ih += dh + (cw ? 1u : 0u);
+      const bool ch = ih >= h;                      // ih < 2 h: dh <= h - 1
+      ih -= ch ? h : 0u;
+      n += dn + (ch ? 1u : 0u);
+    }
+  };
+  struct Loads { vf4 g[4]; uint32_t c[4]; uint32_t want; };      // want: the four codes to match, one byte each
+  __device__ __forceinline__ Loads load_at(uint32_t n, uint32_t ih, uint32_t iw, bool ok, uint32_t col, uint32_t cv) const {
+    if (!ok) n = ih = iw = 0u;                      // (a dropped row: any valid address)
+    const uint32_t oa = ih >> 1, pa = iw >> 1;
+    const bool vh = (ih & 1u) && oa + 1u < oh, vw = (iw & 1u) && pa + 1u < ow;
+    const uint32_t ob = vh ? oa + 1u : oa, pb = vw ? pa + 1u : pa;
+    const uint32_t kh = 1u + (ih & 1u), kw = 1u + (iw & 1u);
+    const uint32_t w00 = kh * 3u + kw, w01 = vw ? kh * 3u : kPoolNoCode, w10 = vh ? kw : kPoolNoCode,
+                   w11 = (vh && vw) ? 0u : kPoolNoCode;
+    const uint32_t ra = (n * oh + oa) * ow, rb = (n * oh + ob) * ow;      // < n * h * w < 2^31
+    const uint32_t px[4] = {ra + pa, ra + pb, rb + pa, rb + pb};
+    Loads l;
+    l.want = w00 | (w01 << 8) | (w10 << 16) | (w11 << 24);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int64_t vidx = (int64_t)px[k] * cv + col;
+      l.g[k] = bn_ld4<false>(g, vidx);
+      l.c[k] = reinterpret_cast<const uint32_t*>(code)[vidx];
+    }
+    return l;
+  }
+  template <bool NT>
+  __device__ __forceinline__ Loads load(int64_t, const Walk& k, bool ok, uint32_t col, uint32_t cv) const {
+    return load_at(k.n, k.ih, k.iw, ok, col, cv);
+  }
+  template <bool NT>
+  __device__ __forceinline__ Loads load_at_pixel(int64_t, uint32_t pixel, bool ok, uint32_t col, uint32_t cv) const {
+    const uint32_t q = pixel / w, n = q / h;
+    return load_at(n, q - n * h, pixel - q * w, ok, col, cv);
+  }
+  __device__ __forceinline__ void value(const Loads& l, float (&o)[4]) const {
+    uint32_t d[4];                                  // byte j of d[k] == 0: candidate k is the argmax of channel j
+#pragma unroll
+    for (int k = 0; k < 4; ++k) d[k] = l.c[k] ^ (((l.want >> (8 * k)) & 0xFFu) * 0x01010101u);
+    const float gk[4][4] = {{l.g[0].x, l.g[0].y, l.g[0].z, l.g[0].w}, {l.g[1].x, l.g[1].y, l.g[1].z, l.g[1].w},
+                            {l.g[2].x, l.g[2].y, l.g[2].z, l.g[2].w}, {l.g[3].x, l.g[3].y, l.g[3].z, l.g[3].w}};
+    const bool single = (l.want >> 8) == 0xFFFFFFu;      // one candidate window: its g is passed on, not added to 0.0f
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float acc = 0.0f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const bool hit = ((d[k] >> (8 * j)) & 0xFFu) == 0u;
+        const float sum = (k == 0 && single) ? gk[k][j] : acc + gk[k][j];
+        acc = hit ? sum : acc;                     // a select: an unselected NaN stays out
+      }
+      o[j] = acc;
+    }
+  }
+};
+
 // ---------------------------------------------------------------- geometry of the reduction
 // A block of the reduction owns `rows` consecutive rows of up to kBnCols float4 columns (64 channels: 256 contiguous
 // bytes of a row, two whole cache lines; narrower tensors are read as one contiguous range).  Its 256 threads form
@@ -32,6 +153,7 @@ __device__ __forceinline__ void bn_st4(float* p, int64_t vidx, vf4 v) {
 // The column split buys blocks where the 1 % rule leaves few row chunks: [12250][512] is 28 row chunks x 8 column chunks.
 constexpr int kBnCols = 16;
 constexpr int kBnRedU = 4;
+constexpr int kBnPoolRedU = 4;        // rows in flight with the pool's gather (9 loads per row, 163 VGPRs, no scratch); 2 measured the same
 constexpr int kBnMinRows = 448;
 constexpr int kBnMaxChunks = 2048;
 constexpr int kBnDxU = 2;             // float4 per lane and stream in the dx kernel (kBwdU of fq_pt.hip)
@@ -66,7 +188,7 @@ constexpr int64_t kBnReduceNtElems = 28ll << 20;
 constexpr int64_t kBnDxNtElems = 28ll << 20;
 // occupancy of the dx kernel by size: the rule of pt_bwd_kernel (fq_pt.hip)
 constexpr int64_t kBnBigElems = 20ll << 20;
-constexpr int kBnMinWaves = 8, kBnBigMaxWaves = 6;
+constexpr int kBnBigMaxWaves = 6;     // (below kBnBigElems the kernel is held to Dy::kDxWaves: 8 with dy in memory)
 
 // ---------------------------------------------------------------- 1. partial sums
 // partials[chunk][2][C] (fp64): row 0 = sum dy, row 1 = sum dy * (x - mean) over the chunk's rows.
@@ -77,9 +199,9 @@ constexpr int kBnMinWaves = 8, kBnBigMaxWaves = 6;
 // -- 6e-8 of a product, of a lane's or a block's subtotal -- is an error of 6e-8 M^1/2 |term|, several 1e-6 of that |sum|;
 // the framework's fp32 sums measure 3e-6 to 6e-6 of the bound's term sum at M = 245 ... 25 088 for that reason.  fp64 adds
 // run at the fp32 rate on this chip and the kernel stays memory-bound (20 VALU operations per 32 loaded bytes).
-template <bool NT>
+template <bool NT, class Dy, int U>
 __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_kernel(
-    const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ mean,
+    const float* __restrict__ x, const Dy dy, const float* __restrict__ mean,
     double* __restrict__ partials, int64_t m, int cv, int64_t rows) {
   const int c0 = (int)blockIdx.y * kBnCols;
   const int cols = (cv - c0) < kBnCols ? (cv - c0) : kBnCols;
@@ -93,23 +215,28 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_kernel(
 #pragma unroll
   for (int j = 0; j < 4; ++j) mu[j] = mean[colv * 4 + j];
   double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
-  for (int64_t rb = row0 + ty; rb - ty < rend; rb += (int64_t)rpp * kBnRedU) {
-    // unconditional, clamped loads: all 2 * U in flight before anything waits; lanes past the chunk's end re-read its
-    // last row and drop it
-    vf4 a[kBnRedU], b[kBnRedU];
-    bool ok[kBnRedU];
+  typename Dy::Walk walk(dy, (uint32_t)(row0 + ty), (uint32_t)rpp);       // (the pool's source: m < 2^31)
+  for (int64_t rb = row0 + ty; rb - ty < rend; rb += (int64_t)rpp * U) {
+    // unconditional, clamped loads: all of the U rows in flight before anything waits; lanes past the chunk's end
+    // re-read its last row and drop it
+    vf4 a[U];
+    typename Dy::Loads b[U];
+    bool ok[U];
 #pragma unroll
-    for (int u = 0; u < kBnRedU; ++u) {
+    for (int u = 0; u < U; ++u) {
       const int64_t r = rb + (int64_t)u * rpp;
       ok[u] = live && r < rend;
       const int64_t vidx = (ok[u] ? r : rend - 1) * cv + colv;
       a[u] = bn_ld4<NT>(x, vidx);
-      b[u] = bn_ld4<NT>(dy, vidx);
+      b[u] = dy.template load<NT>(vidx, walk, ok[u], (uint32_t)colv, (uint32_t)cv);
+      walk.next();
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int u = 0; u < kBnRedU; ++u) {
-      const float av[4] = {a[u].x, a[u].y, a[u].z, a[u].w}, bv[4] = {b[u].x, b[u].y, b[u].z, b[u].w};
+    for (int u = 0; u < U; ++u) {
+      const float av[4] = {a[u].x, a[u].y, a[u].z, a[u].w};
+      float bv[4];
+      dy.value(b[u], bv);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const double g = ok[u] ? (double)bv[j] : 0.0;          // a select, not a product: a dropped NaN stays dropped
@@ -180,21 +307,35 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_finalize_kernel(
 // clamp their index), the per-channel constants arrive under them.  The column of a float4 is its index modulo C / 4:
 // two wave-uniform 32-bit modulos per block, one per lane, a conditional subtract per further float4 -- and no
 // second fetch of the constants when 256 % (C / 4) == 0 (every power-of-two width up to 1024 channels).
-template <bool NT, bool BIG>
-__global__ __attribute__((amdgpu_waves_per_eu((BIG ? 1 : kBnMinWaves), (BIG ? kBnBigMaxWaves : kBnMinWaves))))
+// The pool's source needs the pixel of a float4 as well: pixel and column of the block's first float4 from 32-bit
+// wave-uniform divisions (b = q * cv + r: b * 512 / cv = q * 512 + r * 512 / cv, r * 512 < 2^29), one 32-bit division by cv
+// per lane and float4 on top, two more inside the source for (n, ih, iw).
+template <bool NT, bool BIG, class Dy>
+__global__ __attribute__((amdgpu_waves_per_eu(
+    (BIG ? 1 : Dy::kDxWaves), (BIG && kBnBigMaxWaves < Dy::kDxWaves ? kBnBigMaxWaves : Dy::kDxWaves))))
 __launch_bounds__(kBlock) void bn_bwd_dx_kernel(
-    const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ dx, int64_t nvec, int cv,
+    const float* __restrict__ x, const Dy dy, float* __restrict__ dx, int64_t nvec, int cv,
     const float* __restrict__ consts) {
   const int64_t blk0 = (int64_t)blockIdx.x * (kBlock * kBnDxU);
   const int64_t base = blk0 + threadIdx.x;
   const bool full = blk0 + kBlock * kBnDxU <= nvec;
-  vf4 a[kBnDxU], b[kBnDxU];
+  vf4 a[kBnDxU];
+  typename Dy::Loads b[kBnDxU];
+  uint32_t pix0 = 0, col0 = 0;
+  if constexpr (!std::is_same<Dy, DyMem>::value) {
+    const uint32_t q = blockIdx.x / (uint32_t)cv, r = (blockIdx.x - q * (uint32_t)cv) * (uint32_t)(kBlock * kBnDxU);
+    const uint32_t rq = r / (uint32_t)cv;
+    pix0 = q * (uint32_t)(kBlock * kBnDxU) + rq;
+    col0 = r - rq * (uint32_t)cv + threadIdx.x;
+  }
 #pragma unroll
   for (int u = 0; u < kBnDxU; ++u) {
     const int64_t idx = base + u * kBlock;
-    const int64_t idc = (full || idx < nvec) ? idx : nvec - 1;
+    const bool ok = full || idx < nvec;
+    const int64_t idc = ok ? idx : nvec - 1;
     a[u] = bn_ld4<NT>(x, idc);
-    b[u] = bn_ld4<NT>(dy, idc);
+    const uint32_t t = col0 + (uint32_t)(u * kBlock), tq = t / (uint32_t)cv;
+    b[u] = dy.template load_at_pixel<NT>(idc, pix0 + tq, ok, t - tq * (uint32_t)cv, (uint32_t)cv);
   }
   __builtin_amdgcn_sched_barrier(0);
   // column of the block's first float4: (b * 512) mod cv from two 32-bit modulos (cv <= 2^20: the product fits)
@@ -216,8 +357,9 @@ __launch_bounds__(kBlock) void bn_bwd_dx_kernel(
       for (int q = 0; q < kBnNConst; ++q) ldv<4>(consts + q * c + (int64_t)col * 4, k[q]);
     }
     if (full || idx < nvec) {
-      const float xv[4] = {a[u].x, a[u].y, a[u].z, a[u].w}, gv[4] = {b[u].x, b[u].y, b[u].z, b[u].w};
-      float o[4];
+      const float xv[4] = {a[u].x, a[u].y, a[u].z, a[u].w};
+      float gv[4], o[4];
+      dy.value(b[u], gv);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float xh = (xv[j] - k[0][j]) * k[1][j];
@@ -229,6 +371,104 @@ __launch_bounds__(kBlock) void bn_bwd_dx_kernel(
 }
 
 static inline bool bn_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+// The three launches behind both entry points (arguments checked by the caller); RU = rows in flight in the reduction.
+template <class Dy, int RU>
+static int bn_bwd_launch(const float* x, const Dy dy, const float* mean, const float* invstd, const float* weight,
+                         float* dx, float* dweight, float* dbias, int64_t m, int64_t c, void* workspace, hipStream_t st) {
+  const BnGeom g = bn_geom(m, c);
+  const int64_t nvec = m * (c >> 2);
+  const int64_t dx_grid = (nvec + kBlock * kBnDxU - 1) / (kBlock * kBnDxU);
+  if (g.nchunks > 0x7fffffff || dx_grid > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
+  if (!dx && !dweight && !dbias) return 0;
+  float* consts = (float*)workspace;
+  double* parts = (double*)(consts + kBnNConst * c);      // 20 * c bytes in: 16-byte aligned (c % 4 == 0)
+  const int cv = (int)(c >> 2);
+  const bool nt_r = m * c >= kBnReduceNtElems, nt_d = m * c >= kBnDxNtElems, big = m * c >= kBnBigElems;
+  const dim3 rgrid((unsigned)g.nchunks, (unsigned)g.ncol);
+  if (nt_r) MHAQ_LAUNCH((bn_bwd_reduce_kernel<true, Dy, RU>), rgrid, dim3(kBlock), 0, st, x, dy, mean, parts, m, cv, g.rows);
+  else MHAQ_LAUNCH((bn_bwd_reduce_kernel<false, Dy, RU>), rgrid, dim3(kBlock), 0, st, x, dy, mean, parts, m, cv, g.rows);
+  int rc = launch_status();
+  if (rc) return rc;
+  MHAQ_LAUNCH(bn_bwd_finalize_kernel, dim3((unsigned)cv), dim3(kBlock), 0, st, (const double*)parts, (int)g.nchunks,
+              (int)c, mean, invstd, weight, 1.0 / (double)m, consts, dweight, dbias);
+  rc = launch_status();
+  if (rc || !dx) return rc;
+  const dim3 dgrid((unsigned)dx_grid);
+#define MHAQ_LAUNCH_BN_DX(NT, BG) \
+  MHAQ_LAUNCH((bn_bwd_dx_kernel<NT, BG, Dy>), dgrid, dim3(kBlock), 0, st, x, dy, dx, nvec, cv, (const float*)consts)
+  if (big) { if (nt_d) MHAQ_LAUNCH_BN_DX(true, true); else MHAQ_LAUNCH_BN_DX(false, true); }
+  else { if (nt_d) MHAQ_LAUNCH_BN_DX(true, false); else MHAQ_LAUNCH_BN_DX(false, false); }
+#undef MHAQ_LAUNCH_BN_DX
+  return launch_status();
+}
+
+// ---------------------------------------------------------------- the pool's forward: values and argmax codes
+// max_pool2d(kernel 3, stride 2, padding 1) of a dense fp32 NHWC tensor: one lane per float4 of the output.  The selection
+// is the framework's channels_last kernel's: the window's in-range positions in kh, then kw order, starting at -inf and
+// replacing on  val > max || isnan(val)  (so the LAST NaN of a window wins).  code = kh * 3 + kw of the chosen position.  A
+// window in which nothing replaces the start (all -inf) keeps the framework's initial index, 0 -- element (0, 0) of the plane,
+// which only the window (0, 0) contains (there it is code 4); every other such window gets kPoolNoneChosen, which no input
+// element matches: like the framework's backward, it sends its gradient nowhere.  The nine loads are unconditional on
+// clamped coordinates and take the default cache policy like the stores: every element of t is wanted again by up to three
+// neighbouring windows, p and code by the quantizer behind and by the backward (non-temporal loads of t measured 236 us
+// against 212 us on [250,64,112,112]; docs/NOTEBOOK.md section 6, "Stem pool").
+__global__ __launch_bounds__(kBlock) void maxpool3s2_fwd_kernel(
+    const float* __restrict__ t, float* __restrict__ p, uint8_t* __restrict__ code, uint32_t h, uint32_t w, uint32_t oh,
+    uint32_t ow, uint32_t cv, int64_t nvec) {
+  // pixel and column of the block's first float4, as in bn_bwd_dx_kernel
+  const uint32_t bq = blockIdx.x / cv, br = (blockIdx.x - bq * cv) * (uint32_t)kBlock, brq = br / cv;
+  const uint32_t tt = br - brq * cv + threadIdx.x, tq = tt / cv;
+  const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool ok = idx < nvec;
+  const uint32_t pixel = ok ? bq * (uint32_t)kBlock + brq + tq : 0u, col = tt - tq * cv;
+  const uint32_t q = pixel / ow, n = q / oh, po = q - n * oh, pw = pixel - q * ow;
+  const int ih0 = (int)(po * 2u) - 1, iw0 = (int)(pw * 2u) - 1;
+  vf4 v[9];
+  bool in[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const int ih = ih0 + k / 3, iw = iw0 + k % 3;
+    in[k] = ih >= 0 && ih < (int)h && iw >= 0 && iw < (int)w;
+    const uint32_t ihc = (uint32_t)(ih < 0 ? 0 : (ih < (int)h ? ih : (int)h - 1));
+    const uint32_t iwc = (uint32_t)(iw < 0 ? 0 : (iw < (int)w ? iw : (int)w - 1));
+    v[k] = bn_ld4<false>(t, (int64_t)((n * h + ihc) * w + iwc) * cv + col);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  if (!ok) return;
+  const uint32_t start = (po == 0u && pw == 0u) ? 4u : kPoolNoneChosen;     // the framework's initial index 0
+  float mx[4];
+  uint32_t cd[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    mx[j] = -INFINITY;
+    cd[j] = start;
+  }
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const float e[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool take = in[k] && (e[j] > mx[j] || e[j] != e[j]);
+      mx[j] = take ? e[j] : mx[j];
+      cd[j] = take ? (uint32_t)k : cd[j];
+    }
+  }
+  reinterpret_cast<vf4*>(p)[idx] = vf4{mx[0], mx[1], mx[2], mx[3]};
+  reinterpret_cast<uint32_t*>(code)[idx] = cd[0] | (cd[1] << 8) | (cd[2] << 16) | (cd[3] << 24);
+}
+
+// pooled extent of kernel 3, stride 2, padding 1, dilation 1, ceil_mode = false
+static inline int64_t pool_out(int64_t in) { return (in - 1) / 2 + 1; }
+// n, h, w, c of either pool entry point: 0, or the error code
+static inline int pool_dims_status(int64_t n, int64_t h, int64_t w, int64_t c) {
+  if (n <= 0 || h <= 0 || w <= 0 || c <= 0) return MHAQ_FQ_EINVAL;
+  // the pixel arithmetic of the kernels is 32-bit: n * h * w < 2^31
+  if ((c & 3) || c > kBnMaxChannels || h >= (1ll << 31) || w >= (1ll << 31) || n >= (1ll << 31) ||
+      n * h >= (1ll << 31) || n * h * w >= (1ll << 31))
+    return MHAQ_FQ_EUNSUPPORTED;
+  return 0;
+}
 
 }  // namespace mhaq
 
@@ -252,32 +492,41 @@ int mhaq_fq_bn_bwd(const float* x, const float* dy, const float* mean, const flo
       !bn_aligned(mean, 4) || !bn_aligned(invstd, 4) || !bn_aligned(weight, 4) || !bn_aligned(dweight, 4) ||
       !bn_aligned(dbias, 4))
     return MHAQ_FQ_EALIGN;
-  const BnGeom g = bn_geom(m, c);
-  const int64_t nvec = m * (c >> 2);
-  const int64_t dx_grid = (nvec + kBlock * kBnDxU - 1) / (kBlock * kBnDxU);
-  if (g.nchunks > 0x7fffffff || dx_grid > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
-  if (!dx && !dweight && !dbias) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  float* consts = (float*)workspace;
-  double* parts = (double*)(consts + kBnNConst * c);      // 20 * c bytes in: 16-byte aligned (c % 4 == 0)
-  const int cv = (int)(c >> 2);
-  const bool nt_r = m * c >= kBnReduceNtElems, nt_d = m * c >= kBnDxNtElems, big = m * c >= kBnBigElems;
-  const dim3 rgrid((unsigned)g.nchunks, (unsigned)g.ncol);
-  if (nt_r) MHAQ_LAUNCH(bn_bwd_reduce_kernel<true>, rgrid, dim3(kBlock), 0, st, x, dy, mean, parts, m, cv, g.rows);
-  else MHAQ_LAUNCH(bn_bwd_reduce_kernel<false>, rgrid, dim3(kBlock), 0, st, x, dy, mean, parts, m, cv, g.rows);
-  int rc = launch_status();
-  if (rc) return rc;
-  MHAQ_LAUNCH(bn_bwd_finalize_kernel, dim3((unsigned)cv), dim3(kBlock), 0, st, (const double*)parts, (int)g.nchunks,
-              (int)c, mean, invstd, weight, 1.0 / (double)m, consts, dweight, dbias);
-  rc = launch_status();
-  if (rc || !dx) return rc;
-  const dim3 dgrid((unsigned)dx_grid);
-#define MHAQ_LAUNCH_BN_DX(NT, BG) \
-  MHAQ_LAUNCH((bn_bwd_dx_kernel<NT, BG>), dgrid, dim3(kBlock), 0, st, x, dy, dx, nvec, cv, (const float*)consts)
-  if (big) { if (nt_d) MHAQ_LAUNCH_BN_DX(true, true); else MHAQ_LAUNCH_BN_DX(false, true); }
-  else { if (nt_d) MHAQ_LAUNCH_BN_DX(true, false); else MHAQ_LAUNCH_BN_DX(false, false); }
-#undef MHAQ_LAUNCH_BN_DX
+  return bn_bwd_launch<DyMem, kBnRedU>(x, DyMem{dy}, mean, invstd, weight, dx, dweight, dbias, m, c, workspace,
+                                       (hipStream_t)stream);
+}
+
+int mhaq_fq_maxpool3s2_fwd(const float* t, float* p, uint8_t* code, int64_t n, int64_t h, int64_t w, int64_t c,
+                           void* stream) {
+  if (!t || !p || !code) return MHAQ_FQ_EINVAL;
+  if (const int rc = pool_dims_status(n, h, w, c)) return rc;
+  if (!bn_aligned(t, 16) || !bn_aligned(p, 16) || !bn_aligned(code, 4)) return MHAQ_FQ_EALIGN;
+  const int64_t oh = pool_out(h), ow = pool_out(w), nvec = n * oh * ow * (c >> 2);
+  const int64_t grid = (nvec + kBlock - 1) / kBlock;
+  if (grid > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
+  MHAQ_LAUNCH(maxpool3s2_fwd_kernel, dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream, t, p, code, (uint32_t)h,
+              (uint32_t)w, (uint32_t)oh, (uint32_t)ow, (uint32_t)(c >> 2), nvec);
   return launch_status();
+}
+
+size_t mhaq_fq_bn_pool_bwd_workspace_bytes(int64_t n, int64_t h, int64_t w, int64_t c) {
+  if (pool_dims_status(n, h, w, c)) return 0;
+  return mhaq_fq_bn_bwd_workspace_bytes(n * h * w, c);
+}
+
+int mhaq_fq_bn_pool_bwd(const float* x, const float* g, const uint8_t* code, const float* mean, const float* invstd,
+                        const float* weight, float* dx, float* dweight, float* dbias, int64_t n, int64_t h, int64_t w,
+                        int64_t c, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!x || !g || !code || !mean || !invstd || !workspace) return MHAQ_FQ_EINVAL;
+  if (const int rc = pool_dims_status(n, h, w, c)) return rc;
+  if (workspace_bytes < mhaq_fq_bn_pool_bwd_workspace_bytes(n, h, w, c)) return MHAQ_FQ_EWORKSPACE;
+  if (!bn_aligned(x, 16) || !bn_aligned(g, 16) || !bn_aligned(code, 4) || !bn_aligned(dx, 16) ||
+      !bn_aligned(workspace, 16) || !bn_aligned(mean, 4) || !bn_aligned(invstd, 4) || !bn_aligned(weight, 4) ||
+      !bn_aligned(dweight, 4) || !bn_aligned(dbias, 4))
+    return MHAQ_FQ_EALIGN;
+  const DyPool src{g, code, (uint32_t)h, (uint32_t)w, (uint32_t)pool_out(h), (uint32_t)pool_out(w)};
+  return bn_bwd_launch<DyPool, kBnPoolRedU>(x, src, mean, invstd, weight, dx, dweight, dbias, n * h * w, c, workspace,
+                                            (hipStream_t)stream);
 }
 
 }  // extern "C"

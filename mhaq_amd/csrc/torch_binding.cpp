@@ -54,7 +54,8 @@ namespace {
   X(mhaq_fq_wlayer_ptl_fwd) X(mhaq_fq_wlayer_ptl_bwd) X(mhaq_fq_pt_aewgs_colstats_workspace_bytes)                     \
   X(mhaq_fq_pt_aewgs_colstats) X(mhaq_fq_act_fwd_x16) X(mhaq_fq_act_bwd_x16) X(mhaq_fq_act_bwd_partials_x16)                    \
   X(mhaq_fq_act_relu_fwd) X(mhaq_fq_act_relu_bwd) X(mhaq_fq_act_relu_bwd_partials)                                    \
-  X(mhaq_fq_bn_bwd_workspace_bytes) X(mhaq_fq_bn_bwd)
+  X(mhaq_fq_bn_bwd_workspace_bytes) X(mhaq_fq_bn_bwd) X(mhaq_fq_maxpool3s2_fwd)                                       \
+  X(mhaq_fq_bn_pool_bwd_workspace_bytes) X(mhaq_fq_bn_pool_bwd)
 
 struct Api {
 #define X(n) decltype(&::n) n = nullptr;
@@ -738,6 +739,95 @@ Tensor bn_train(const Tensor& x, const std::optional<Tensor>& w, const std::opti
   return BatchNormTrainFn::apply(x, w, b, running_mean, running_var, momentum, eps, cudnn_enabled);
 }
 
+// ------------------------------------------------------------------------------------------------ BatchNorm + stem pool
+// max_pool2d(bn_train(x, ..), 3, 2, 1) as ONE node (the ResNet stem, mhaq_amd/fused_blocks.py).  Forward: the framework's
+// BatchNorm forward as above, then mhaq_fq_maxpool3s2_fwd, which leaves the pooled tensor and a 1-byte argmax code per
+// output; the BatchNorm output dies with the forward, and neither it nor int64 indices are kept for the backward.
+// Backward: mhaq_fq_bn_pool_bwd, the BatchNorm backward that gathers its dy from the pooled gradient and the codes instead
+// of reading a materialized one.  Output, running statistics and the three gradients are the bits of the two nodes run one
+// after the other.  Taken under BatchNormTrainFn's own conditions (and n * h * w < 2^31); outside them bn_pool_train IS
+// that composition.
+inline bool bn_pool_eligible(const Tensor& x, const Tensor& w) {
+  auto stat_ok = [&](const Tensor& t) {
+    return t.defined() && t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == x.size(1);
+  };
+  if (!x.is_cuda() || x.scalar_type() != at::kFloat || x.dim() != 4 || x.numel() == 0) return false;
+  if (!x.is_contiguous(at::MemoryFormat::ChannelsLast) || (x.size(1) & 3) || !aligned16(x)) return false;
+  return x.numel() / x.size(1) < (1ll << 31) && stat_ok(w);
+}
+
+std::atomic<int64_t> g_bn_pool_hip_backwards{0};   // backwards that took mhaq_fq_bn_pool_bwd
+
+class BatchNormPoolTrainFn : public torch::autograd::Function<BatchNormPoolTrainFn> {
+ public:
+  static Tensor forward(AutogradContext* ctx, const Tensor& x, const Tensor& w, const Tensor& b,
+                        const std::optional<Tensor>& running_mean, const std::optional<Tensor>& running_var,
+                        double momentum, double eps, bool cudnn_enabled) {
+    auto out = at::_batch_norm_impl_index(x, w, b, running_mean, running_var, /*training=*/true, momentum, eps,
+                                          cudnn_enabled);
+    const Tensor &mean = std::get<1>(out), &invstd = std::get<2>(out);
+    TORCH_CHECK(bn_bwd_eligible(x, w, mean, invstd), "bn_pool_train: the BatchNorm forward left statistics the HIP "
+                "backward cannot read (there is no fallback behind this point)");
+    const Tensor t = std::get<0>(out).contiguous(at::MemoryFormat::ChannelsLast);
+    const int64_t n = x.size(0), c = x.size(1), h = x.size(2), wd = x.size(3);
+    Tensor p = at::empty({n, c, (h - 1) / 2 + 1, (wd - 1) / 2 + 1}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
+    Tensor code = at::empty_like(p, p.options().dtype(at::kByte));
+    check(A.mhaq_fq_maxpool3s2_fwd(fptr(t), fptr_mut(p), static_cast<uint8_t*>(code.mutable_data_ptr()), n, h, wd, c,
+                                   cur_stream(x)),
+          "mhaq_fq_maxpool3s2_fwd");
+    ctx->save_for_backward({x, w, mean, invstd, code});
+    ctx->set_materialize_grads(false);
+    return p;
+  }
+
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    variable_list out(8);
+    if (!grads[0].defined()) return out;
+    TORCH_CHECK(!(at::GradMode::is_enabled() && grads[0].requires_grad()),
+                "bn_pool_train: the node is once-differentiable (no double backward)");
+    at::NoGradGuard no_grad;
+    auto saved = ctx->get_saved_variables();
+    const Tensor &x = saved[0], &w = saved[1], &mean = saved[2], &invstd = saved[3], &code = saved[4];
+    const std::array<bool, 3> mask = {ctx->needs_input_grad(0), ctx->needs_input_grad(1), ctx->needs_input_grad(2)};
+    need_lib();
+    const int64_t n = x.size(0), c = x.size(1), h = x.size(2), wd = x.size(3);
+    // the pooled gradient in the memory order of the pooled tensor (= the codes')
+    Tensor g = grads[0].scalar_type() == at::kFloat ? grads[0] : grads[0].to(at::kFloat);
+    if (g.sizes() != code.sizes() || g.strides() != code.strides()) {
+      Tensor dense = at::empty_like(code, code.options().dtype(at::kFloat));
+      dense.copy_(g);
+      g = dense;
+    }
+    Tensor dx = mask[0] ? at::empty_like(x) : Tensor();
+    Tensor dw = mask[1] ? at::empty_like(w) : Tensor();
+    Tensor db = mask[2] ? at::empty({c}, mean.options()) : Tensor();
+    const size_t nb = A.mhaq_fq_bn_pool_bwd_workspace_bytes(n, h, wd, c);
+    Tensor ws = at::empty({(int64_t)nb}, x.options().dtype(at::kByte));
+    check(A.mhaq_fq_bn_pool_bwd(fptr(x), fptr(g), static_cast<const uint8_t*>(code.const_data_ptr()), fptr(mean),
+                                fptr(invstd), fptr(w), mask[0] ? fptr_mut(dx) : nullptr, mask[1] ? fptr_mut(dw) : nullptr,
+                                mask[2] ? fptr_mut(db) : nullptr, n, h, wd, c, ws.mutable_data_ptr(), nb, cur_stream(x)),
+          "mhaq_fq_bn_pool_bwd");
+    g_bn_pool_hip_backwards.fetch_add(1, std::memory_order_relaxed);
+    out[0] = dx;
+    out[1] = dw;
+    out[2] = db;
+    return out;
+  }
+};
+
+Tensor bn_pool_train(const Tensor& x, const std::optional<Tensor>& w, const std::optional<Tensor>& b,
+                     const std::optional<Tensor>& running_mean, const std::optional<Tensor>& running_var, double momentum,
+                     double eps, bool cudnn_enabled) {
+  TORCH_CHECK(w.has_value() && w->defined() && b.has_value() && b->defined(),
+              "bn_pool_train: an affine BatchNorm (weight and bias) is required");
+  MHAQ_ON_DEVICE_OF(x);
+  if (!bn_pool_eligible(x, *w))
+    return at::max_pool2d(BatchNormTrainFn::apply(x, w, b, running_mean, running_var, momentum, eps, cudnn_enabled),
+                          {3, 3}, {2, 2}, {1, 1});
+  need_lib();
+  return BatchNormPoolTrainFn::apply(x, *w, *b, running_mean, running_var, momentum, eps, cudnn_enabled);
+}
+
 // ------------------------------------------------------------------------------------------------ weight layer ops
 struct Pre {   // this step's forward of the layer out of the model-wide launch (multi.py, forward-only mode)
   bool has = false;
@@ -1411,6 +1501,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
 
   m.def("bn_hip_backwards", []() { return g_bn_hip_backwards.load(); },
         "number of BatchNorm backwards so far that ran the HIP kernels instead of the framework's backward");
+  // ... with the stem's 3x3 / stride 2 max pool in the same node
+  m.def("bn_pool_train", &bn_pool_train, py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("running_mean"),
+        py::arg("running_var"), py::arg("momentum"), py::arg("eps"), py::arg("cudnn_enabled") = true);
+  m.def("bn_pool_hip_backwards", []() { return g_bn_pool_hip_backwards.load(); },
+        "number of BatchNorm + pool backwards so far that ran mhaq_fq_bn_pool_bwd (the fallback is the two separate nodes)");
 
   // weight layers
   m.def("weight_layer", &weight_layer, py::arg("w"), py::arg("log_wght_s"), py::arg("method"),

@@ -30,8 +30,15 @@ were.  The decision to fuse is taken per call and per place; the original forwar
 Eval mode, calibration and hook-based observers therefore always see the original modules.  BatchNorm is untouched: the
 fused path is the same under DDP and SyncBatchNorm.
 
+  * Stem pool: where the stem's bn1 is a bn_backward.HipBackwardBatchNorm2d that takes its compiled node on this input and
+    the pool is exactly nn.MaxPool2d(3, 2, 1), both hook-free, BatchNorm and pool run as ONE node
+    (HipBackwardBatchNorm2d.forward_pooled): the [N,64,112,112] BatchNorm output is not kept for the backward, no int64
+    indices are written, and the BatchNorm backward gathers its dy from the pooled gradient instead of reading one the
+    pool's backward wrote.  Same bits in every output and gradient.
+
 MHAQ_FUSE_BLOCKS=0 in the environment keeps QATTrainer from installing (A/B runs of an unchanged benchmark);
-QATConfig.fuse_blocks=False does the same per trainer.
+QATConfig.fuse_blocks=False does the same per trainer.  MHAQ_STEM_POOL=0 / QATConfig.fuse_stem_pool=False keep only the
+stem pool's node out (install(stem_pool=False)).
 """
 from __future__ import annotations
 
@@ -42,15 +49,23 @@ from torch import nn
 from torch.nn.modules import module as _nn_module
 
 from . import nets
+from .bn_backward import HipBackwardBatchNorm2d
 from .layers import NoisyAct
 
 ENV_SWITCH = "MHAQ_FUSE_BLOCKS"
+ENV_SWITCH_STEM_POOL = "MHAQ_STEM_POOL"
 _TAG = "_mhaq_fq"
+_STEM_POOL = "_mhaq_stem_pool"
 
 
 def enabled_by_env() -> bool:
     """False when MHAQ_FUSE_BLOCKS=0 (or "false" / "off") is set."""
     return os.environ.get(ENV_SWITCH, "1").strip().lower() not in ("0", "false", "off", "no")
+
+
+def stem_pool_enabled_by_env() -> bool:
+    """False when MHAQ_STEM_POOL=0 (or "false" / "off") is set."""
+    return os.environ.get(ENV_SWITCH_STEM_POOL, "1").strip().lower() not in ("0", "false", "off", "no")
 
 
 def _hook_free(*mods) -> bool:
@@ -92,6 +107,14 @@ def _take_pinned(x, seq):
     return tag[1] if tag[0] is seq._modules.get("activations_quantizer") else None
 
 
+def _is_stem_pool(mp) -> bool:
+    """Exactly nn.MaxPool2d(3, 2, 1): the one geometry mhaq_fq_maxpool3s2_fwd / mhaq_fq_bn_pool_bwd implement."""
+    def both(v, k):
+        return v == k or v == (k, k) or v == [k, k]
+    return (type(mp) is nn.MaxPool2d and both(mp.kernel_size, 3) and both(mp.stride, 2) and both(mp.padding, 1)
+            and both(mp.dilation, 1) and not mp.ceil_mode and not mp.return_indices)
+
+
 class FusedBasicBlock(nets.BasicBlock):
     """nets.BasicBlock with the fused places; nets.BasicBlock.forward is what runs wherever a place cannot be fused."""
 
@@ -126,18 +149,26 @@ class FusedResNet18(nets.ResNet18):
 
     def forward(self, x):
         first = self.layer1[0] if len(self.layer1) else None
-        t = self.bn1(self.conv1(x))
+        c = self.conv1(x)
+        t = None
         fused = False
         if (self.training and _no_global_hooks() and type(first) is FusedBasicBlock and first.training
                 and type(self.maxpool) is nn.MaxPool2d):
             q = _bypassable(first.conv1, self.relu)
-            # (the pool keeps dtype, device and density: what holds for t holds for its output)
-            if q is not None and _hook_free(self.maxpool, self.layer1, first) and q.can_fuse_relu(t):
-                y, a = q.forward_fused(self.maxpool(t), None, want_act=True)
+            # (BatchNorm and pool keep dtype, device and density: what holds for the convolution's output holds for theirs)
+            if q is not None and _hook_free(self.maxpool, self.layer1, first) and q.can_fuse_relu(c):
+                bn = self.bn1
+                if (self.__dict__.get(_STEM_POOL) and type(bn) is HipBackwardBatchNorm2d and bn.takes_node(c)
+                        and _is_stem_pool(self.maxpool) and _hook_free(bn)):
+                    p = bn.forward_pooled(c)
+                else:
+                    t = bn(c)
+                    p = self.maxpool(t)
+                y, a = q.forward_fused(p, None, want_act=True)
                 setattr(a, _TAG, (q, y))
                 x, fused = a, True
         if not fused:
-            x = self.maxpool(self.relu(t))
+            x = self.maxpool(self.relu(self.bn1(c) if t is None else t))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         return self.fc(torch.flatten(self.avgpool(x), 1))
 
@@ -147,10 +178,11 @@ def _fusable_block(m) -> bool:
                                            or _wrapped_quantizer(m.conv2) is not None)
 
 
-def install(model: nn.Module) -> int:
+def install(model: nn.Module, stem_pool: bool = True) -> int:
     """Give every quantized nets.BasicBlock of `model` (wrap.quantize_model with the stock layers) the fused forward, and
     a nets.ResNet18 the fused stem and the links from each block to its consumer.  Returns the number of modules switched;
-    a model wrapped with other layer classes (the CPU checker's) is left alone."""
+    a model wrapped with other layer classes (the CPU checker's) is left alone.  stem_pool: whether a fused stem may run
+    its BatchNorm and pool as one node."""
     switched = 0
     for m in list(model.modules()):
         if _fusable_block(m):
@@ -169,6 +201,7 @@ def install(model: nn.Module) -> int:
                 b.__dict__["_mhaq_next"] = nb
                 b.__dict__["_mhaq_path"] = (lay,) if nlay is lay else (lay, nlay)
             m.__class__ = FusedResNet18
+            m.__dict__[_STEM_POOL] = bool(stem_pool)
             switched += 1
     return switched
 
@@ -180,4 +213,5 @@ def uninstall(model: nn.Module) -> None:
             m.__dict__.pop("_mhaq_path", None)
             m.__class__ = nets.BasicBlock
         elif type(m) is FusedResNet18:
+            m.__dict__.pop(_STEM_POOL, None)
             m.__class__ = nets.ResNet18

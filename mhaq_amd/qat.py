@@ -58,6 +58,9 @@ class QATConfig:
     # ReLU and residual add of nets.BasicBlock / the nets.ResNet18 stem inside the activation quantizer's kernels
     # (fused_blocks.py; value-identical to the separate modules).  MHAQ_FUSE_BLOCKS=0 in the environment switches it off.
     fuse_blocks: bool = True
+    # the stem's BatchNorm and max pool as one node where both switches around this one are on (fused_blocks.py, "Stem
+    # pool"; bit-identical).  MHAQ_STEM_POOL=0 in the environment switches it off.
+    fuse_stem_pool: bool = True
     # backward of every nn.BatchNorm2d on the HIP kernels of csrc/bn_bwd.hip; the forward stays the framework's, bit for bit
     # (bn_backward.py).  MHAQ_BN_BACKWARD=0 in the environment switches it off.
     hip_bn_backward: bool = True
@@ -215,7 +218,7 @@ class QATTrainer:
         if cfg.fuse_blocks and layers is None and self.device.type == "cuda":
             from . import fused_blocks
             if fused_blocks.enabled_by_env():
-                fused_blocks.install(net)
+                fused_blocks.install(net, stem_pool=cfg.fuse_stem_pool and fused_blocks.stem_pool_enabled_by_env())
         if cfg.hip_bn_backward and layers is None and self.device.type == "cuda":
             from . import bn_backward
             if bn_backward.enabled_by_env():
