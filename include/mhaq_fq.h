@@ -263,6 +263,39 @@ int mhaq_fq_act_relu_bwd_partials(const float* z, const float* g_y, const float*
                                   int32_t* nparts_out, void* stream);
 
 /* ------------------------------------------------------------------------
+ * The same on 16-bit tensors (a NoisyAct behind a ReLU under torch.autocast).  Additive to ABI v4 -- MHAQ_FQ_ABI_VERSION
+ * stays 4; a caller discovers these entry points by symbol.  z, addend, y, a_out, g_y, g_a, gx are 16-bit (dtype =
+ * MHAQ_FQ_DT_BF16 or MHAQ_FQ_DT_F16, else MHAQ_FQ_EINVAL), at least 2-byte aligned (MHAQ_FQ_EALIGN); 16-byte aligned
+ * ones with n >= 8 take the 8-elements-per-lane kernels, others an element kernel.  params, grads and the quantizer's
+ * parameters are fp32.  STE, LSQ or EWGS.
+ * Arithmetic: the BITS of the separate 16-bit launches -- the framework's 16-bit add, relu, threshold_backward and
+ * gradient accumulation around the 16-bit entry points above -- not a single-rounding variant of them.  With up = the exact
+ * conversion to fp32 and R = round to nearest-even to dtype (NaN stays NaN):
+ *   relu_fwd:  t = addend ? R(up(z) + up(addend)) : z;   a = relu(t) (NaN passes), written to a_out when non-NULL;
+ *              y = R(fake_quant(up(a))), what the 16-bit forward above gives on a.
+ *   relu_bwd:  a = relu(up(z)) (z = the ReLU's input or its output);   gq = R(gx of the fp32 backward on (a, up(g_y)));
+ *              gs = g_a ? R(up(gq) + up(g_a)) : gq;   gx = (up(z) <= 0) ? +0 : gs   (a NaN z passes the gradient).
+ *              gs is rounded TWICE on purpose: unfused, the quantizer writes a 16-bit gq and the framework adds the other
+ *              consumer's 16-bit gradient with a 16-bit add.  R(unrounded gq + g_a) would be nearer the exact sum, and
+ *              another training run than the one the separate launches give.
+ * The partial rows (count, layout, values, {s, qr} behind them), the random signs at (seed, offset, offset_dev) and
+ * grads[3] are those of the 16-bit backward above on (a, g_y), byte for byte: the parameter sums take the fp32 values of
+ * every element, masked or not.  The workspace is the fp32 query's for n, and the finalize of several quantizers serves
+ * fused and plain, 16-bit and fp32 launches together.  Stream-ordered, no host synchronisation, capture-safe.
+ * ---------------------------------------------------------------------- */
+int mhaq_fq_act_relu_fwd_x16(const void* z, const void* addend, void* y, void* a_out, int64_t n, int dtype,
+                             const float* log_act_s, const float* log_act_q, const float* act_b,
+                             float* params_out /* [5] */, void* stream);
+int mhaq_fq_act_relu_bwd_x16(const void* z, const void* g_y, const void* g_a, void* gx, int64_t n, int dtype,
+                             const float* params /* [5] */, int method, uint64_t seed, uint64_t offset,
+                             const uint64_t* offset_dev, float* grads /* [3] */, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int mhaq_fq_act_relu_bwd_partials_x16(const void* z, const void* g_y, const void* g_a, void* gx, int64_t n, int dtype,
+                                      const float* params /* [5] */, int method, uint64_t seed, uint64_t offset,
+                                      const uint64_t* offset_dev, void* workspace, size_t workspace_bytes,
+                                      int32_t* nparts_out, void* stream);
+
+/* ------------------------------------------------------------------------
  * Backward of training-mode BatchNorm (torch.nn.BatchNorm2d on a channels_last tensor) from the statistics its forward
  * saved.  Additive to ABI v4 -- MHAQ_FQ_ABI_VERSION stays 4; a caller discovers these entry points by symbol.
  *   x, dy, dx       dense fp32 NHWC seen as [m = N*H*W][c]; c % 4 == 0 and c <= 2^22 (else MHAQ_FQ_EUNSUPPORTED);

@@ -50,6 +50,10 @@ SIGNATURES = {
     "mhaq_fq_act_relu_fwd": (_int, [_p, _p, _p, _p, _i64, _p, _p, _p, _p, _p]),
     "mhaq_fq_act_relu_bwd": (_int, [_p, _p, _p, _p, _i64, _p, _int, _u64, _u64, _p, _p, _p, _sz, _p]),
     "mhaq_fq_act_relu_bwd_partials": (_int, [_p, _p, _p, _p, _i64, _p, _int, _u64, _u64, _p, _p, _sz, _p, _p]),
+    # ... and on 16-bit tensors: `dtype` after n (additive, ABI v4 kept)
+    "mhaq_fq_act_relu_fwd_x16": (_int, [_p, _p, _p, _p, _i64, _int, _p, _p, _p, _p, _p]),
+    "mhaq_fq_act_relu_bwd_x16": (_int, [_p, _p, _p, _p, _i64, _int, _p, _int, _u64, _u64, _p, _p, _p, _sz, _p]),
+    "mhaq_fq_act_relu_bwd_partials_x16": (_int, [_p, _p, _p, _p, _i64, _int, _p, _int, _u64, _u64, _p, _p, _sz, _p, _p]),
     # training BatchNorm backward from the saved statistics (additive, ABI v4 kept)
     "mhaq_fq_bn_bwd_workspace_bytes": (_sz, [_i64, _i64]),
     "mhaq_fq_bn_bwd": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _sz, _p]),

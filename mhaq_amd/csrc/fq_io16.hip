@@ -17,6 +17,13 @@
 // (COUNT = false), verbatim in arithmetic: fq_pt.hip stays untouched because the committed traffic profile
 // (profiles/r06_traffic.json) is tied to its hash.  tests/test_gpu_act16.py holds the copies to the fp32 kernels bit
 // for bit; folding both into a shared header belongs to the next change that re-measures traffic anyway.
+//
+// ReLU (+ residual add) forms (mhaq_fq_act_relu_*_x16, further down): the NoisyAct behind a ReLU as ONE launch per direction,
+// as fq_pt.hip's pt_fwd_relu_kernel / pt_bwd_relu_kernel.  Their contract is NOT "the fp32 result rounded once" but the bits of
+// the separate 16-bit launches they replace (torch's 16-bit add / relu / threshold_backward / gradient accumulation around the
+// kernels above): z + addend is rounded to 16 bits before the ReLU, and the gradient gq is rounded to 16 bits BEFORE g_a is
+// added and the sum is rounded again -- two roundings, as the quantizer's 16-bit gx and autograd's 16-bit add give them.
+// Partial rows, geometry, sign tile and workspace rule are those of x16_act_bwd_kernel on (relu(z), g_y).
 #include "fq_common.hpp"
 
 namespace mhaq {
@@ -432,6 +439,261 @@ __global__ MHAQ_X16_BWD_OCC void x16_act_bwd_kernel(
   }
 }
 
+// =============================================================== ReLU (+ residual add) fused in, 16-bit
+// fq_pt.hip's pt_fwd_relu_kernel / pt_bwd_relu_kernel on 16-bit tensors (mhaq_fq_act_relu_*_x16): the NoisyAct behind a
+// ReLU under torch.autocast.  The target is the BITS of the separate 16-bit launches -- torch's add, relu,
+// threshold_backward and autograd's accumulation around the kernels above -- so every 16-bit tensor those launches would
+// have written is rounded here where they round it, in registers:
+//   forward    t = addend ? R(up(z) + up(addend)) : z        (torch's 16-bit add: one fp32 sum, rounded once)
+//              a = relu(t)   (exact; NaN passes)             y = R(fwd_elem(up(a)))
+//   backward   a = relu(up(z))                               gq = R(bwd_elem(a, up(g_y)))
+//              gs = g_a ? R(up(gq) + up(g_a)) : gq           gx = (up(z) <= 0) ? +0 : gs
+// gs is rounded TWICE on purpose: unfused, the quantizer writes a 16-bit gq and autograd adds the other consumer's 16-bit
+// gradient to it with a 16-bit add.  R(fp32 gq + g_a) would be closer to the exact sum and a different training run.
+// The parameter sums take the fp32 (a, up(g_y)) of every element, masked or not: geometry, sign tile and partial rows are
+// x16_act_bwd_kernel's on (a, g_y), byte for byte.
+__device__ __forceinline__ float relu_elem(float x) { return (x <= 0.f) ? 0.f : x; }
+
+// keep-masks of a packed pair: threshold_backward / relu zero the halves whose value is <= 0 (a NaN keeps its half)
+__device__ __forceinline__ uint32_t keep2(float v0, float v1) {
+  return ((v0 <= 0.f) ? 0u : 0x0000ffffu) | ((v1 <= 0.f) ? 0u : 0xffff0000u);
+}
+
+// a = relu(z [+ addend]) of a packed pair: values a0, a1 and the bits of a (a is a 16-bit value or +0: no rounding)
+template <int DT, bool HAS_ADD>
+__device__ __forceinline__ uint32_t relu_in2(uint32_t zw, uint32_t dw, float& a0, float& a1) {
+  uint32_t tw = zw;
+  if (HAS_ADD) {
+    float z0, z1, d0, d1;
+    up2<DT>(zw, z0, z1);
+    up2<DT>(dw, d0, d1);
+    tw = down2<DT>(z0 + d0, z1 + d1);
+  }
+  float t0, t1;
+  up2<DT>(tw, t0, t1);
+  a0 = relu_elem(t0);
+  a1 = relu_elem(t1);
+  return tw & keep2(t0, t1);
+}
+template <int DT, bool HAS_ADD>
+__device__ __forceinline__ uint16_t relu_in1(uint16_t z, uint16_t d, float& a) {
+  uint16_t tb = z;
+  if (HAS_ADD) tb = down1<DT>(up1<DT>(z) + up1<DT>(d));
+  const float t = up1<DT>(tb);
+  a = relu_elem(t);
+  return (t <= 0.f) ? (uint16_t)0 : tb;
+}
+
+// gx of a packed pair from the fp32 results q0, q1 of the element body, the other consumers' gradient cw and z
+template <int DT, bool HAS_GA>
+__device__ __forceinline__ uint32_t relu_out2(float q0, float q1, uint32_t cw, float z0, float z1) {
+  uint32_t w = down2<DT>(q0, q1);
+  if (HAS_GA) {
+    float r0, r1, c0, c1;
+    up2<DT>(w, r0, r1);
+    up2<DT>(cw, c0, c1);
+    w = down2<DT>(r0 + c0, r1 + c1);
+  }
+  return w & keep2(z0, z1);
+}
+template <int DT, bool HAS_GA>
+__device__ __forceinline__ uint16_t relu_out1(float q, uint16_t c, float z) {
+  uint16_t w = down1<DT>(q);
+  if (HAS_GA) w = down1<DT>(up1<DT>(w) + up1<DT>(c));
+  return (z <= 0.f) ? (uint16_t)0 : w;
+}
+
+template <int DT, bool HAS_ADD, bool WRITE_A, bool ALIGNED, bool NTLD>
+__global__ __launch_bounds__(kBlock) void x16_act_relu_fwd_kernel(
+    const uint16_t* __restrict__ z, const uint16_t* __restrict__ addend, uint16_t* __restrict__ y,
+    uint16_t* __restrict__ a_out, int64_t n, const float* __restrict__ ps, const float* __restrict__ pq,
+    const float* __restrict__ pb, float* __restrict__ params_out) {
+  const int64_t nvec = n >> 3;
+  const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  vu4 a = {0u, 0u, 0u, 0u}, b = {0u, 0u, 0u, 0u};
+  if (ALIGNED) {
+    // unconditional loads, lanes past the end re-read the last vector (the launcher sends n < 8 to the element kernel)
+    const int64_t idc = (idx < nvec) ? idx : nvec - 1;
+    a = ld8<NTLD>(z, idc);
+    if (HAS_ADD) b = ld8<NTLD>(addend, idc);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  const float s = exp2f(*ps);
+  const float qr = exp2f(*pq);
+  const float zp = *pb, lo = zp;
+  const float hi = (zp + qr) - s;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    params_out[0] = s; params_out[1] = zp; params_out[2] = lo; params_out[3] = hi; params_out[4] = qr;
+  }
+  FwdStats st{INFINITY, -INFINITY, false};
+  if (ALIGNED) {
+    if (idx < nvec) {
+      vu4 o, av;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        float a0, a1;
+        av[w] = relu_in2<DT, HAS_ADD>(a[w], b[w], a0, a1);
+        const float r0 = fwd_elem<false>(a0, s, zp, lo, hi, st);
+        const float r1 = fwd_elem<false>(a1, s, zp, lo, hi, st);
+        o[w] = down2<DT>(r0, r1);
+      }
+      st8<true>(y, idx, o);
+      if (WRITE_A) st8<true>(a_out, idx, av);
+    }
+    const int64_t t = (nvec << 3) + threadIdx.x;       // n % 8 tail elements
+    if (blockIdx.x == 0 && t < n) {
+      float av;
+      const uint16_t ab = relu_in1<DT, HAS_ADD>(z[t], HAS_ADD ? addend[t] : (uint16_t)0, av);
+      y[t] = down1<DT>(fwd_elem<false>(av, s, zp, lo, hi, st));
+      if (WRITE_A) a_out[t] = ab;
+    }
+  } else {
+    // pointers not 16-byte aligned (tensor views) / n < 8: element accesses, grid-stride
+    for (int64_t i = idx; i < n; i += (int64_t)gridDim.x * kBlock) {
+      float av;
+      const uint16_t ab = relu_in1<DT, HAS_ADD>(z[i], HAS_ADD ? addend[i] : (uint16_t)0, av);
+      y[i] = down1<DT>(fwd_elem<false>(av, s, zp, lo, hi, st));
+      if (WRITE_A) a_out[i] = ab;
+    }
+  }
+}
+
+// x16_act_bwd_kernel<DT, METHOD, RSIGN = false, ALIGNED, BIG> on (relu(z), g) with a third input stream (g_a) and the
+// ReLU's mask on the elementwise output; everything that reaches the partial rows is that kernel's, line for line
+template <int DT, int METHOD, bool ALIGNED, bool HAS_GA, bool BIG>
+__global__ MHAQ_X16_BWD_OCC void x16_act_relu_bwd_kernel(
+    const uint16_t* __restrict__ z, const uint16_t* __restrict__ g, const uint16_t* __restrict__ ga,
+    uint16_t* __restrict__ gx, int64_t n, const float* __restrict__ params, uint64_t seed, uint64_t offset,
+    const uint64_t* __restrict__ offset_dev, float* __restrict__ partials) {
+  constexpr bool NEED_R = (METHOD != MHAQ_FQ_LSQ);
+  constexpr bool FAST_METHOD = (METHOD == MHAQ_FQ_STE || METHOD == MHAQ_FQ_LSQ);
+  constexpr int U = bwd_u(BIG);
+  constexpr int kTileCalls = 16 * U;
+  float acc[kAcc] = {0.f, 0.f, 0.f, 0.f};
+  const int64_t nvec = n >> 3;
+  const int64_t base = (int64_t)blockIdx.x * (kBlock * U) + threadIdx.x;
+  const bool full = ((int64_t)blockIdx.x + 1) * (kBlock * U) <= nvec;
+  vu4 a[U], b[U], c[U];
+  if (ALIGNED) {
+    // unconditional, clamped loads: all 3 * U in flight before anything waits (nvec >= 1 here)
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t idx = base + u * kBlock;
+      const int64_t idc = (full || idx < nvec) ? idx : nvec - 1;
+      a[u] = ld8<true>(z, idc);
+      b[u] = ld8<true>(g, idc);
+      if (HAS_GA) c[u] = ld8<true>(ga, idc);
+      else c[u] = vu4{0u, 0u, 0u, 0u};
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  offset = stream_offset(offset, offset_dev);
+  const float p_s = params[0], p_zp = params[1], p_lo = params[2], p_hi = params[3];
+  __shared__ __align__(16) uint32_t stile[4 * kTileCalls];
+  if (ALIGNED && NEED_R) {
+    sign_tile_fill(stile, (int64_t)blockIdx.x * kTileCalls, kTileCalls, seed, offset);
+    __syncthreads();
+  }
+  const BwdCtx k = make_bwd_ctx(p_s, p_zp, p_lo, p_hi);
+
+  if (ALIGNED) {
+    uint32_t nb[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      nb[u] = 0;
+      if (NEED_R) nb[u] = ~(stile[(u * kBlock + (int)threadIdx.x) >> 2] >> (((int)threadIdx.x & 3) * 8));
+    }
+    const bool fast = FAST_METHOD && k.fast_div && (k.lo < k.hi) && (k.s > 0.f);      // wave-uniform
+    if (FAST_METHOD && fast) {
+      const float hcs = (MHAQ_INV_SQRT3 * k.s) * 0.5f;
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t idx = base + u * kBlock;
+        if (full || idx < nvec) {
+          vu4 o;
+#pragma unroll
+          for (int w = 0; w < 4; ++w) {
+            float z0, z1, g0, g1;
+            up2<DT>(a[u][w], z0, z1);
+            up2<DT>(b[u][w], g0, g1);
+            float rc0 = 0.f, rc1 = 0.f;
+            if (NEED_R) {
+              rc0 = signed_half_scale(nb[u], 2 * w, hcs);
+              rc1 = signed_half_scale(nb[u], 2 * w + 1, hcs);
+            }
+            const float y0 = bwd_elem_fast<METHOD>(relu_elem(z0), g0, rc0, k, acc);
+            const float y1 = bwd_elem_fast<METHOD>(relu_elem(z1), g1, rc1, k, acc);
+            o[w] = relu_out2<DT, HAS_GA>(y0, y1, c[u][w], z0, z1);
+          }
+          st8<true>(gx, idx, o);
+        }
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t idx = base + u * kBlock;
+        if (full || idx < nvec) {
+          vu4 o;
+#pragma unroll
+          for (int w = 0; w < 4; ++w) {
+            float z0, z1, g0, g1;
+            up2<DT>(a[u][w], z0, z1);
+            up2<DT>(b[u][w], g0, g1);
+            float r0 = 0.f, r1 = 0.f;
+            if (NEED_R) {
+              const uint32_t bits = ~nb[u];
+              r0 = ((bits >> (2 * w)) & 1u) ? 0.5f : -0.5f;
+              r1 = ((bits >> (2 * w + 1)) & 1u) ? 0.5f : -0.5f;
+            }
+            const float y0 = bwd_elem<METHOD>(relu_elem(z0), g0, r0, 0.f, k, acc);
+            const float y1 = bwd_elem<METHOD>(relu_elem(z1), g1, r1, 0.f, k, acc);
+            o[w] = relu_out2<DT, HAS_GA>(y0, y1, c[u][w], z0, z1);
+          }
+          st8<true>(gx, idx, o);
+        }
+      }
+    }
+    const int64_t t = (nvec << 3) + threadIdx.x;
+    if (blockIdx.x == 0 && t < n) {   // n % 8 tail elements
+      const float zz = up1<DT>(z[t]);
+      const float r = NEED_R ? philox_r(t, seed, offset) : 0.f;
+      const float v = bwd_elem<METHOD>(relu_elem(zz), up1<DT>(g[t]), r, 0.f, k, acc);
+      gx[t] = relu_out1<DT, HAS_GA>(v, HAS_GA ? ga[t] : (uint16_t)0, zz);
+    }
+    if (BIG) {
+      __shared__ float smf[kAcc * (kBlock / 64)];
+      double tot[kAcc];
+      block_sum_f32<kAcc>(acc, tot, smf);
+      if (threadIdx.x == 0) write_act_partials(partials, tot, (int64_t)gridDim.x, (int64_t)blockIdx.x);
+      publish_act_scales(partials, params, (int64_t)gridDim.x);
+    } else {
+      float wsum[kAcc];
+#pragma unroll
+      for (int q = 0; q < kAcc; ++q) wsum[q] = wave_sum_dpp(acc[q]);
+      const int64_t nrows = (int64_t)gridDim.x * (kBlock / 64);
+      if ((threadIdx.x & 63) == 0)
+        write_act_partials(partials, wsum, nrows, (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6));
+      publish_act_scales(partials, params, nrows);
+    }
+  } else {
+    // unaligned tensor views / n < 8: element accesses, grid-stride, fp64 per-thread accumulators
+    double dacc[kAcc] = {0, 0, 0, 0};
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+      const float zz = up1<DT>(z[i]);
+      const float r = NEED_R ? philox_r(i, seed, offset) : 0.f;
+      float a1[kAcc] = {0.f, 0.f, 0.f, 0.f};
+      const float v = bwd_elem<METHOD>(relu_elem(zz), up1<DT>(g[i]), r, 0.f, k, a1);
+      gx[i] = relu_out1<DT, HAS_GA>(v, HAS_GA ? ga[i] : (uint16_t)0, zz);
+#pragma unroll
+      for (int q = 0; q < kAcc; ++q) dacc[q] += (double)a1[q];
+    }
+    __shared__ double sm[kAcc * (kBlock / 64)];
+    block_sum<kAcc>(dacc, sm);
+    if (threadIdx.x == 0) write_act_partials(partials, dacc, (int64_t)gridDim.x, (int64_t)blockIdx.x);
+    publish_act_scales(partials, params, (int64_t)gridDim.x);
+  }
+}
+
 // fq_pt.hip act_finalize_kernel: column sums -> {dL/dlog_act_s, dL/dlog_act_q, dL/dact_b}, same partition and order
 __global__ __launch_bounds__(kFinalThreads) void x16_act_finalize_kernel(const float* __restrict__ partials, int nparts,
                                                                           const float* __restrict__ params,
@@ -522,6 +784,54 @@ void launch_bwd_method(int method, const uint16_t* x, const uint16_t* g, uint16_
   }
 }
 
+template <int DT>
+void launch_relu_fwd(const uint16_t* z, const uint16_t* addend, uint16_t* y, uint16_t* a_out, int64_t n,
+                     const float* ps, const float* pq, const float* pb, float* params_out, int grid, bool al, bool ntld,
+                     hipStream_t st) {
+#define MHAQ_X16_RFWD_(HA, WA, AL, NL)                                                                               \
+  MHAQ_LAUNCH((x16_act_relu_fwd_kernel<DT, HA, WA, AL, NL>), dim3(grid), dim3(kBlock), 0, st, z, addend, y, a_out, n, \
+              ps, pq, pb, params_out)
+#define MHAQ_X16_RFWD(HA, WA)                                \
+  do {                                                       \
+    if (!al) MHAQ_X16_RFWD_(HA, WA, false, false);           \
+    else if (ntld) MHAQ_X16_RFWD_(HA, WA, true, true);       \
+    else MHAQ_X16_RFWD_(HA, WA, true, false);                \
+  } while (0)
+  if (addend) { if (a_out) MHAQ_X16_RFWD(true, true); else MHAQ_X16_RFWD(true, false); }
+  else        { if (a_out) MHAQ_X16_RFWD(false, true); else MHAQ_X16_RFWD(false, false); }
+#undef MHAQ_X16_RFWD
+#undef MHAQ_X16_RFWD_
+}
+
+template <int DT, int METHOD>
+void launch_relu_bwd(const uint16_t* z, const uint16_t* g, const uint16_t* ga, uint16_t* gx, int64_t n,
+                     const float* params, uint64_t seed, uint64_t offset, const uint64_t* offset_dev, float* parts,
+                     int grid, bool al, bool big, hipStream_t st) {
+#define MHAQ_X16_RBWD_(AL, GA, BG)                                                                                 \
+  MHAQ_LAUNCH((x16_act_relu_bwd_kernel<DT, METHOD, AL, GA, BG>), dim3(grid), dim3(kBlock), 0, st, z, g, ga, gx, n, \
+              params, seed, offset, offset_dev, parts)
+#define MHAQ_X16_RBWD(GA)                                    \
+  do {                                                       \
+    if (!al) MHAQ_X16_RBWD_(false, GA, false);               \
+    else if (big) MHAQ_X16_RBWD_(true, GA, true);            \
+    else MHAQ_X16_RBWD_(true, GA, false);                    \
+  } while (0)
+  if (ga) MHAQ_X16_RBWD(true); else MHAQ_X16_RBWD(false);
+#undef MHAQ_X16_RBWD
+#undef MHAQ_X16_RBWD_
+}
+
+template <int DT>
+void launch_relu_bwd_method(int method, const uint16_t* z, const uint16_t* g, const uint16_t* ga, uint16_t* gx,
+                            int64_t n, const float* params, uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
+                            float* parts, int grid, bool al, bool big, hipStream_t st) {
+  switch (method) {
+    case MHAQ_FQ_STE: launch_relu_bwd<DT, MHAQ_FQ_STE>(z, g, ga, gx, n, params, seed, offset, offset_dev, parts, grid, al, big, st); break;
+    case MHAQ_FQ_EWGS: launch_relu_bwd<DT, MHAQ_FQ_EWGS>(z, g, ga, gx, n, params, seed, offset, offset_dev, parts, grid, al, big, st); break;
+    default: launch_relu_bwd<DT, MHAQ_FQ_LSQ>(z, g, ga, gx, n, params, seed, offset, offset_dev, parts, grid, al, big, st); break;
+  }
+}
+
 }  // namespace io16
 }  // namespace mhaq
 
@@ -604,6 +914,77 @@ int mhaq_fq_act_bwd_x16(const void* x, const void* g, void* gx, int64_t n, int d
   int32_t nparts = 0;
   int rc = mhaq_fq_act_bwd_partials_x16(x, g, gx, n, dtype, params, method, r_sign, seed, offset, offset_dev,
                                         workspace, workspace_bytes, &nparts, stream);
+  if (rc) return rc;
+  MHAQ_LAUNCH(io16::x16_act_finalize_kernel, dim3(3), dim3(io16::kFinalThreads), 0, (hipStream_t)stream,
+              (const float*)workspace, (int)nparts, params, grads);
+  return launch_status();
+}
+
+// ---- ReLU (+ residual add) fused into the 16-bit NoisyAct launches (x16_act_relu_fwd_kernel / x16_act_relu_bwd_kernel)
+int mhaq_fq_act_relu_fwd_x16(const void* z, const void* addend, void* y, void* a_out, int64_t n, int dtype,
+                             const float* log_s, const float* log_q, const float* b, float* params_out, void* stream) {
+  if (n < 0 || !log_s || !log_q || !b || !params_out || (n > 0 && (!z || !y))) return MHAQ_FQ_EINVAL;
+  if (!io16::known_dtype(dtype)) return MHAQ_FQ_EINVAL;
+  if (!io16::aligned2(z) || !io16::aligned2(addend) || !io16::aligned2(y) || !io16::aligned2(a_out))
+    return MHAQ_FQ_EALIGN;
+  const bool al = n >= 8 && io16::aligned16(z) && io16::aligned16(y) && (!addend || io16::aligned16(addend)) &&
+                  (!a_out || io16::aligned16(a_out));
+  const int64_t grid64 = al ? io16::blocks8(n, io16::kFwdU) : io16::simple_grid(n);
+  if (grid64 > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
+  const int grid = (int)grid64;
+  hipStream_t st = (hipStream_t)stream;
+  const bool ntld = n > io16::kFwdPlainLoadElems;
+  const uint16_t *zs = (const uint16_t*)z, *ds = (const uint16_t*)addend;
+  uint16_t *ys = (uint16_t*)y, *as = (uint16_t*)a_out;
+  if (dtype == MHAQ_FQ_DT_BF16)
+    io16::launch_relu_fwd<MHAQ_FQ_DT_BF16>(zs, ds, ys, as, n, log_s, log_q, b, params_out, grid, al, ntld, st);
+  else
+    io16::launch_relu_fwd<MHAQ_FQ_DT_F16>(zs, ds, ys, as, n, log_s, log_q, b, params_out, grid, al, ntld, st);
+  return launch_status();
+}
+
+int mhaq_fq_act_relu_bwd_partials_x16(const void* z, const void* g_y, const void* g_a, void* gx, int64_t n, int dtype,
+                                      const float* params, int method, uint64_t seed, uint64_t offset,
+                                      const uint64_t* offset_dev, void* workspace, size_t workspace_bytes,
+                                      int32_t* nparts_out, void* stream) {
+  if (n < 0 || !params || (n > 0 && (!z || !g_y || !gx))) return MHAQ_FQ_EINVAL;
+  if (!io16::known_dtype(dtype)) return MHAQ_FQ_EINVAL;
+  if (method != MHAQ_FQ_STE && method != MHAQ_FQ_LSQ && method != MHAQ_FQ_EWGS)
+    return (method == MHAQ_FQ_AEWGS) ? MHAQ_FQ_EUNSUPPORTED : MHAQ_FQ_EINVAL;
+  if (!io16::aligned2(z) || !io16::aligned2(g_y) || !io16::aligned2(g_a) || !io16::aligned2(gx)) return MHAQ_FQ_EALIGN;
+  if (!workspace || workspace_bytes < mhaq_fq_act_bwd_workspace_bytes(n)) return MHAQ_FQ_EWORKSPACE;
+  const bool al = n >= 8 && io16::aligned16(z) && io16::aligned16(g_y) && io16::aligned16(gx) &&
+                  (!g_a || io16::aligned16(g_a));
+  const bool big = al && n >= io16::kBwdBigElems;
+  const int64_t grid64 = al ? io16::blocks8(n, io16::bwd_u(big)) : io16::simple_grid(n);
+  if (grid64 > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
+  // partial rows: those of mhaq_fq_act_bwd_partials_x16 over the same n and alignment
+  const int64_t rows64 = (al && !big) ? grid64 * (kBlock / 64) : grid64;
+  if (rows64 > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
+  if ((size_t)(3 * rows64 + 2) * sizeof(float) > workspace_bytes) return MHAQ_FQ_EWORKSPACE;
+  if (nparts_out) *nparts_out = (int32_t)rows64;
+  const int grid = (int)grid64;
+  hipStream_t st = (hipStream_t)stream;
+  float* parts = (float*)workspace;
+  const uint16_t *zs = (const uint16_t*)z, *gs = (const uint16_t*)g_y, *gas = (const uint16_t*)g_a;
+  uint16_t* gxs = (uint16_t*)gx;
+  if (dtype == MHAQ_FQ_DT_BF16)
+    io16::launch_relu_bwd_method<MHAQ_FQ_DT_BF16>(method, zs, gs, gas, gxs, n, params, seed, offset, offset_dev, parts,
+                                                  grid, al, big, st);
+  else
+    io16::launch_relu_bwd_method<MHAQ_FQ_DT_F16>(method, zs, gs, gas, gxs, n, params, seed, offset, offset_dev, parts,
+                                                 grid, al, big, st);
+  return launch_status();
+}
+
+int mhaq_fq_act_relu_bwd_x16(const void* z, const void* g_y, const void* g_a, void* gx, int64_t n, int dtype,
+                             const float* params, int method, uint64_t seed, uint64_t offset,
+                             const uint64_t* offset_dev, float* grads, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+  if (!grads) return MHAQ_FQ_EINVAL;
+  int32_t nparts = 0;
+  int rc = mhaq_fq_act_relu_bwd_partials_x16(z, g_y, g_a, gx, n, dtype, params, method, seed, offset, offset_dev,
+                                             workspace, workspace_bytes, &nparts, stream);
   if (rc) return rc;
   MHAQ_LAUNCH(io16::x16_act_finalize_kernel, dim3(3), dim3(io16::kFinalThreads), 0, (hipStream_t)stream,
               (const float*)workspace, (int)nparts, params, grads);

@@ -54,6 +54,7 @@ namespace {
   X(mhaq_fq_wlayer_ptl_fwd) X(mhaq_fq_wlayer_ptl_bwd) X(mhaq_fq_pt_aewgs_colstats_workspace_bytes)                     \
   X(mhaq_fq_pt_aewgs_colstats) X(mhaq_fq_act_fwd_x16) X(mhaq_fq_act_bwd_x16) X(mhaq_fq_act_bwd_partials_x16)                    \
   X(mhaq_fq_act_relu_fwd) X(mhaq_fq_act_relu_bwd) X(mhaq_fq_act_relu_bwd_partials)                                    \
+  X(mhaq_fq_act_relu_fwd_x16) X(mhaq_fq_act_relu_bwd_x16) X(mhaq_fq_act_relu_bwd_partials_x16)                        \
   X(mhaq_fq_bn_bwd_workspace_bytes) X(mhaq_fq_bn_bwd) X(mhaq_fq_maxpool3s2_fwd)                                       \
   X(mhaq_fq_bn_pool_bwd_workspace_bytes) X(mhaq_fq_bn_pool_bwd)
 
@@ -572,6 +573,9 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> act_layer(const Tensor& x_in, const T
 // and returns ONE gradient, which both z and addend take -- where the separate nodes ran autograd's accumulation of the
 // two gradients of a, threshold_backward and the quantizer's backward.  One sign-stream offset per backward, partials
 // registered with the hub: exactly as ActLayerFn.
+// z (and addend) float32, or bf16 / fp16 under autocast (mhaq_fq_act_relu_*_x16; mhaq_amd/layers.py decides when): y, a and
+// the gradient then have z's dtype and the bits of the separate 16-bit launches, params and the parameter gradients stay
+// float32 (include/mhaq_fq.h).
 class ActReluFn : public torch::autograd::Function<ActReluFn> {
  public:
   static variable_list forward(AutogradContext* ctx, const Tensor& z, const std::optional<Tensor>& addend,
@@ -580,11 +584,18 @@ class ActReluFn : public torch::autograd::Function<ActReluFn> {
     const bool has_add = addend.has_value() && addend->defined();
     Tensor y = at::empty_like(z);
     Tensor a = want_act ? at::empty_like(z) : Tensor();
-    Tensor params = at::empty({5}, z.options());
+    Tensor params = at::empty({5}, z.options().dtype(at::kFloat));
     const int64_t tl0 = now_ns();
-    check(A.mhaq_fq_act_relu_fwd(fptr(z), has_add ? fptr(*addend) : nullptr, fptr_mut(y), want_act ? fptr_mut(a) : nullptr,
-                                 z.numel(), fptr(log_s), fptr(log_q), fptr(b), fptr_mut(params), cur_stream(z)),
-          "mhaq_fq_act_relu_fwd");
+    if (const int dt = act_dtype(z))
+      check(A.mhaq_fq_act_relu_fwd_x16(z.const_data_ptr(), has_add ? addend->const_data_ptr() : nullptr,
+                                       y.mutable_data_ptr(), want_act ? a.mutable_data_ptr() : nullptr, z.numel(), dt,
+                                       fptr(log_s), fptr(log_q), fptr(b), fptr_mut(params), cur_stream(z)),
+            "mhaq_fq_act_relu_fwd_x16");
+    else
+      check(A.mhaq_fq_act_relu_fwd(fptr(z), has_add ? fptr(*addend) : nullptr, fptr_mut(y),
+                                   want_act ? fptr_mut(a) : nullptr, z.numel(), fptr(log_s), fptr(log_q), fptr(b),
+                                   fptr_mut(params), cur_stream(z)),
+            "mhaq_fq_act_relu_fwd");
     tick(T_ACT_FWD_LAUNCH, tl0, now_ns());
     // relu is idempotent: the backward recomputes a from the ReLU's input (mid-block) or from a itself
     ctx->save_for_backward({want_act ? a : z, params});
@@ -602,12 +613,29 @@ class ActReluFn : public torch::autograd::Function<ActReluFn> {
     const bool g_y_def = grads[0].defined(), g_a_def = ic[4] /*want_act*/ != 0 && grads.size() > 2 && grads[2].defined();
     if (!g_y_def && !g_a_def) return out;
     const int64_t t1 = now_ns();
+    // autograd hands the gradients over in y's and a's dtype (= z's); a 16-bit kernel must not read a float32 stream as 16-bit
+    const Tensor& zs = saved[0];
+    TORCH_CHECK((!g_y_def || grads[0].scalar_type() == zs.scalar_type()) &&
+                    (!g_a_def || grads[2].scalar_type() == zs.scalar_type()),
+                "act_relu_layer backward: a gradient does not have the input's dtype ", zs.scalar_type());
+    const int dt = act_dtype(zs);
     // (needs_input_grad counts the tensor inputs that were present: an absent addend takes no slot)
     const size_t e = ic[5] != 0 ? 1 : 0;
     ActGrads res = act_backward(ctx, t0, t1, saved, ic, grads[0], g_a_def ? grads[2] : Tensor(), /*has_r=*/false,
                                 /*need0=*/1 + e,
-                               [](const ActBwdLaunch& a) {
-      if (a.hub)
+                               [dt](const ActBwdLaunch& a) {
+      const void* gap = a.ga.defined() ? a.ga.const_data_ptr() : nullptr;
+      if (a.hub && dt)
+        check(A.mhaq_fq_act_relu_bwd_partials_x16(a.x.const_data_ptr(), a.g.const_data_ptr(), gap, a.gx.mutable_data_ptr(),
+                                                  a.n, dt, fptr(a.params), a.method, a.d.seed, a.d.offset, a.d.offset_dev,
+                                                  a.ws, a.nb, a.nparts, a.stream),
+              "mhaq_fq_act_relu_bwd_partials_x16");
+      else if (dt)
+        check(A.mhaq_fq_act_relu_bwd_x16(a.x.const_data_ptr(), a.g.const_data_ptr(), gap, a.gx.mutable_data_ptr(), a.n, dt,
+                                         fptr(a.params), a.method, a.d.seed, a.d.offset, a.d.offset_dev, a.gr, a.ws, a.nb,
+                                         a.stream),
+              "mhaq_fq_act_relu_bwd_x16");
+      else if (a.hub)
         check(A.mhaq_fq_act_relu_bwd_partials(fptr(a.x), fptr(a.g), fptr_or_null(a.ga), fptr_mut(a.gx), a.n, fptr(a.params),
                                               a.method, a.d.seed, a.d.offset, a.d.offset_dev, a.ws, a.nb, a.nparts,
                                               a.stream),
@@ -630,10 +658,10 @@ std::tuple<Tensor, std::optional<Tensor>, Tensor, Tensor, Tensor> act_relu_layer
     int64_t method, bool want_act, int64_t hub_id, int64_t slot, int64_t rank) {
   need_lib();
   MHAQ_ON_DEVICE_OF(z);
-  TORCH_CHECK(z.is_cuda() && z.scalar_type() == at::kFloat && z.is_non_overlapping_and_dense(),
-              "act_relu_layer: z must be a dense float32 device tensor");
+  TORCH_CHECK(z.is_cuda() && (z.scalar_type() == at::kFloat || act_dtype(z) != 0) && z.is_non_overlapping_and_dense(),
+              "act_relu_layer: z must be a dense float32, bfloat16 or float16 device tensor");
   const bool has_add = addend.has_value() && addend->defined();
-  TORCH_CHECK(!has_add || (addend->device() == z.device() && addend->scalar_type() == at::kFloat &&
+  TORCH_CHECK(!has_add || (addend->device() == z.device() && addend->scalar_type() == z.scalar_type() &&
                            addend->sizes() == z.sizes() && addend->strides() == z.strides()),
               "act_relu_layer: addend must have z's device, dtype, shape and strides");
   TORCH_CHECK(!has_add || want_act, "act_relu_layer: with an addend the ReLU output is an output of the op (want_act)");

@@ -10,7 +10,10 @@ As separate modules these are two or three full passes over the activation tenso
 own (torch's add, clamp_min, threshold_backward and autograd's accumulation of the two gradients of the ReLU output).
 NoisyAct.forward_fused (ops.act_relu_layer -> mhaq_fq_act_relu_fwd / _bwd) takes the ReLU's input instead: one forward and
 one backward kernel per place, and every value -- y, a, the gradients, the parameter gradients, the random signs -- is
-the one the separate modules give (ReLU, a two-term fp32 add and a mask are exact elementwise operations).
+the one the separate modules give (ReLU, a two-term fp32 add and a mask are exact elementwise operations).  Under
+torch.autocast the tensors are 16-bit and the same places take mhaq_fq_act_relu_*_x16, which give the BITS of the separate
+16-bit modules: the 16-bit add and the accumulation of the two gradients round, and the kernels round where those launches
+round (the accumulated gradient twice; include/mhaq_fq.h, DESIGN.md sections 10-11).
 
   * Block end: the producing block quantizes for its consumer.  It returns a = relu(bn2 + identity) as before, an ordinary
     tensor, and pins the consumer's quantized input to it (`a._mhaq_fq = (quantizer, y)`); the consumer takes it off and
@@ -22,7 +25,8 @@ the one the separate modules give (ReLU, a two-term fp32 add and a mask are exac
 install() switches the CLASS of the stock modules (FusedBasicBlock / FusedResNet18 are subclasses that add a forward and
 nothing else): module names, named_modules() order, state_dict keys, copy.deepcopy and torch.save(model) are what they
 were.  The decision to fuse is taken per call and per place; the original forward runs otherwise.  A place is fused only
-  - in training mode, on dense float32 device tensors (the addend sharing z's strides),
+  - in training mode, on dense device tensors that are float32 or, under torch.autocast, of the autocast dtype (the addend
+    sharing z's dtype and strides),
   - with the stock mhaq_amd.layers.NoisyAct, not disabled, not AEWGS,
   - when no forward, pre-forward or backward hook sits on a module whose forward would be bypassed or whose input would
     change (the nn.ReLU, the NoisyAct, the wrapping Sequential; for a block end also the two blocks and their containers,
@@ -34,7 +38,8 @@ fused path is the same under DDP and SyncBatchNorm.
     the pool is exactly nn.MaxPool2d(3, 2, 1), both hook-free, BatchNorm and pool run as ONE node
     (HipBackwardBatchNorm2d.forward_pooled): the [N,64,112,112] BatchNorm output is not kept for the backward, no int64
     indices are written, and the BatchNorm backward gathers its dy from the pooled gradient instead of reading one the
-    pool's backward wrote.  Same bits in every output and gradient.
+    pool's backward wrote.  Same bits in every output and gradient.  fp32 only: under autocast
+    takes_node() is false and the stem runs maxpool(bn(c)) in front of the fused quantizer.
 
 MHAQ_FUSE_BLOCKS=0 in the environment keeps QATTrainer from installing (A/B runs of an unchanged benchmark);
 QATConfig.fuse_blocks=False does the same per trainer.  MHAQ_STEM_POOL=0 / QATConfig.fuse_stem_pool=False keep only the

@@ -106,15 +106,17 @@ class NoisyAct(nn.Module):
         return y
 
     def can_fuse_relu(self, z, addend=None) -> bool:
-        """True when forward_fused serves this call: training mode, the STE / LSQ / EWGS hot path, dense float32 device
-        tensors (addend with z's strides) and no hook on this module (a hook must see the module's own forward)."""
+        """True when forward_fused serves this call: training mode, the STE / LSQ / EWGS hot path, dense device tensors
+        (addend with z's dtype and strides) that are float32 or, under torch.autocast, of the autocast dtype
+        (ops.autocast_x16: the 16-bit kernels; any other 16-bit tensor runs on x.float() in forward(), which the fused
+        kernels do not restate) and no hook on this module (a hook must see the module's own forward)."""
         if not self.training or self.disable or type(self) is not NoisyAct:
             return False
         if self._forward_hooks or self._forward_pre_hooks or self._backward_hooks or self._backward_pre_hooks:
             return False
-        if not (z.is_cuda and z.dtype is torch.float32 and ops._is_dense(z)):
+        if not (z.is_cuda and (z.dtype is torch.float32 or ops.autocast_x16(z)) and ops._is_dense(z)):
             return False
-        if addend is not None and not (addend.dtype is torch.float32 and addend.device == z.device
+        if addend is not None and not (addend.dtype is z.dtype and addend.device == z.device
                                        and addend.shape == z.shape and addend.stride() == z.stride()):
             return False
         try:

@@ -508,7 +508,9 @@ def act_relu_layer(z, addend, log_act_s, log_act_q, act_b, method: int, want_act
     (mhaq_fq_act_relu_fwd / _bwd; compiled node ActReluFn): a = relu(z [+ addend]), y = fake_quant(a).  Returns
     (y, a or None, params, params[0:1], params[3:4]); `a` (the ReLU output, for its other consumers) only with want_act.
     Every value equals what torch.relu / torch.add + fake_quant_act_layer + autograd give.  z: a dense float32 device
-    tensor, addend with z's strides; method STE / LSQ / EWGS as an integer (the caller -- NoisyAct.forward_fused,
+    tensor -- or bf16 / fp16 (mhaq_fq_act_relu_*_x16: y, a and the gradient in z's dtype, the bits of the separate 16-bit
+    ops, whose add and gradient accumulation round; the caller decides when: NoisyAct.can_fuse_relu asks for autocast) --,
+    addend with z's dtype and strides; method STE / LSQ / EWGS as an integer (the caller -- NoisyAct.forward_fused,
     fused_blocks.py -- has checked all of this: anything else raises here)."""
     hub, slot = (hub_slot[0].id, hub_slot[1]) if hub_slot is not None else (0, 0)
     return _seeded_ext().act_relu_layer(z, addend, log_act_s, log_act_q, act_b, method, want_act, hub, slot, _rank())

@@ -56,7 +56,8 @@ class QATConfig:
     # group instead of per layer.  0 = every layer keeps its own backward launch.
     weight_backward_group_elems: int = 4 << 20
     # ReLU and residual add of nets.BasicBlock / the nets.ResNet18 stem inside the activation quantizer's kernels
-    # (fused_blocks.py; value-identical to the separate modules).  MHAQ_FUSE_BLOCKS=0 in the environment switches it off.
+    # (fused_blocks.py; value-identical to the separate modules, in fp32 and under autocast_dtype).  MHAQ_FUSE_BLOCKS=0 in
+    # the environment switches it off.
     fuse_blocks: bool = True
     # the stem's BatchNorm and max pool as one node where both switches around this one are on (fused_blocks.py, "Stem
     # pool"; bit-identical).  MHAQ_STEM_POOL=0 in the environment switches it off.
