@@ -314,6 +314,27 @@ int mhaq_fq_bn_bwd(const float* x, const float* dy, const float* mean, const flo
                    void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * The same on 16-bit tensors (the BatchNorm behind a convolution under torch.autocast).  Additive to ABI v4 --
+ * MHAQ_FQ_ABI_VERSION stays 4; a caller discovers these entry points by symbol.
+ *   x, dy, dx       dense NHWC seen as [m][c], of the type named by `dtype` (MHAQ_FQ_DT_BF16 or MHAQ_FQ_DT_F16, anything else:
+ *                   MHAQ_FQ_EINVAL); c % 8 == 0 and c <= 2^22 (else MHAQ_FQ_EUNSUPPORTED); x, dy, dx and `workspace`
+ *                   16-byte aligned (else MHAQ_FQ_EALIGN)
+ *   mean, invstd, weight, dweight, dbias and everything in `workspace`: fp32 / fp64, as above; weight and each of the
+ *                   three outputs may be NULL.  Argument checks, their codes and their order are mhaq_fq_bn_bwd's, all
+ *                   before any launch.
+ * Arithmetic: every element is converted UP exactly and takes the arithmetic of mhaq_fq_bn_bwd unchanged -- up(x) - mean
+ * and its product with up(dy) in fp64, fixed-order fp64 sums, dweight and dbias rounded once from them --, and
+ *   dx = R16((weight * invstd) * ((up(dy) - dbias / m) - ((up(x) - mean) * invstd) * (dweight / m)))
+ * is evaluated in fp32 in this order, without contraction, and rounded to nearest-even ONCE (a plain conversion: NaN stays
+ * NaN, an fp16 overflow gives +-inf).  The partial-row geometry differs from mhaq_fq_bn_bwd's (a lane owns 8 channels):
+ * size the workspace with mhaq_fq_bn_bwd_x16_workspace_bytes.  Stream-ordered, capture-safe, stateless.
+ * ---------------------------------------------------------------------- */
+size_t mhaq_fq_bn_bwd_x16_workspace_bytes(int64_t m, int64_t c);
+int mhaq_fq_bn_bwd_x16(const void* x, const void* dy, const float* mean, const float* invstd, const float* weight,
+                       void* dx, float* dweight, float* dbias, int64_t m, int64_t c, int dtype,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * The ResNet stem's max pool behind a training-mode BatchNorm: max_pool2d(kernel 3, stride 2, padding 1, dilation 1,
  * ceil_mode = false) of a dense fp32 NHWC tensor [n, h, w, c], oh = (h - 1) / 2 + 1 and ow likewise.  Additive to ABI v4.
  *   c % 4 == 0, c <= 2^22 and n * h * w < 2^31 (else MHAQ_FQ_EUNSUPPORTED); t, p, x, g, dx and `workspace` 16-byte

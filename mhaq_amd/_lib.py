@@ -57,6 +57,9 @@ SIGNATURES = {
     # training BatchNorm backward from the saved statistics (additive, ABI v4 kept)
     "mhaq_fq_bn_bwd_workspace_bytes": (_sz, [_i64, _i64]),
     "mhaq_fq_bn_bwd": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _sz, _p]),
+    # ... and on 16-bit tensors: `dtype` after c, its own workspace query (additive, ABI v4 kept)
+    "mhaq_fq_bn_bwd_x16_workspace_bytes": (_sz, [_i64, _i64]),
+    "mhaq_fq_bn_bwd_x16": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _int, _p, _sz, _p]),
     # the stem's 3x3 / stride 2 max pool with 1-byte argmax codes, and the BatchNorm backward that gathers its dy from them
     "mhaq_fq_maxpool3s2_fwd": (_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _p]),
     "mhaq_fq_bn_pool_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),

@@ -14,9 +14,16 @@ isinstance(m, nn.BatchNorm2d) are what they were; SyncBatchNorm and subclasses a
 call: the original forward runs in eval mode, with track_running_stats=False or affine=False, on a CPU tensor and on a
 non-float32 input (so under autocast, where the convolution in front hands over a 16-bit tensor).
 
+16-bit inputs.  install(model, x16=True) also sends a bf16 / fp16 device input (float32 parameters) through the node and
+enables its 16-bit backward (mhaq_fq_bn_bwd_x16: the fp32 arithmetic on the exactly upcast x and dy, dx rounded to
+nearest-even once; C % 8 == 0 and a dy of x's dtype, else the node falls back to the framework's backward, bit for bit).
+The forward is still the framework's.  This is OFF by default -- it changes the gradient bits of every bf16 run --:
+QATConfig.hip_bn_backward_16bit=True switches it on per trainer, MHAQ_BN_BACKWARD_X16=1 (or "true" / "on") in the
+environment for an unchanged benchmark; the variable, when set, overrides the configuration either way.
+
 forward_pooled() is the same module with the ResNet stem's max pool behind it in one node (fused_blocks.FusedResNet18 calls
 it; csrc/torch_binding.cpp, BatchNormPoolTrainFn): same forward bits, and a backward that never materializes the pool's
-gradient.
+gradient.  float32 only (takes_pooled_node): a 16-bit stem stays maxpool(bn(c)), with the 16-bit backward above where enabled.
 
 MHAQ_BN_BACKWARD=0 in the environment keeps QATTrainer from installing (A/B runs of an unchanged benchmark);
 QATConfig.hip_bn_backward=False does the same per trainer.
@@ -29,6 +36,8 @@ import torch
 from torch import nn
 
 ENV_SWITCH = "MHAQ_BN_BACKWARD"
+ENV_SWITCH_X16 = "MHAQ_BN_BACKWARD_X16"
+_X16 = "_mhaq_bn_x16"          # per-module flag in the instance __dict__ (not a parameter, buffer or state_dict entry)
 
 
 def enabled_by_env() -> bool:
@@ -36,13 +45,32 @@ def enabled_by_env() -> bool:
     return os.environ.get(ENV_SWITCH, "1").strip().lower() not in ("0", "false", "off", "no")
 
 
+def x16_enabled(configured: bool = False) -> bool:
+    """The 16-bit route's switch: `configured` (QATConfig.hip_bn_backward_16bit) unless MHAQ_BN_BACKWARD_X16 is set, which
+    then decides: "1" / "true" / "on" / "yes" enable it, anything else disables it."""
+    v = os.environ.get(ENV_SWITCH_X16)
+    if v is None or not v.strip():
+        return bool(configured)
+    return v.strip().lower() in ("1", "true", "on", "yes")
+
+
 class HipBackwardBatchNorm2d(nn.BatchNorm2d):
     """nn.BatchNorm2d whose training forward goes through the compiled node; nn.BatchNorm2d.forward runs otherwise."""
 
     def takes_node(self, input) -> bool:
         """True when this call goes through the compiled node (forward() and forward_pooled() decide alike)."""
-        return not (not self.training or not self.track_running_stats or not self.affine or not input.is_cuda
-                    or input.dtype != torch.float32 or self.weight.dtype != torch.float32)
+        if (not self.training or not self.track_running_stats or not self.affine or not input.is_cuda
+                or self.weight.dtype != torch.float32):
+            return False
+        return input.dtype == torch.float32 or (self.takes_x16() and input.dtype in (torch.bfloat16, torch.float16))
+
+    def takes_x16(self) -> bool:
+        """True when install(..., x16=True) enabled the 16-bit backward for this module."""
+        return bool(self.__dict__.get(_X16, False))
+
+    def takes_pooled_node(self, input) -> bool:
+        """True when forward_pooled() applies: the pooled node's kernels are float32."""
+        return input.dtype == torch.float32 and self.takes_node(input)
 
     def _step_average_factor(self) -> float:
         """The bookkeeping of _BatchNorm.forward (training mode, tracked statistics): counts the batch, returns the
@@ -56,30 +84,33 @@ class HipBackwardBatchNorm2d(nn.BatchNorm2d):
                 exponential_average_factor = self.momentum
         return exponential_average_factor
 
-    def _node(self, entry, input):
+    def _node(self, entry, input, *more):
         self._check_input_dim(input)
         return entry(input, self.weight, self.bias, self.running_mean, self.running_var, self._step_average_factor(),
-                     self.eps, torch.backends.cudnn.enabled)
+                     self.eps, torch.backends.cudnn.enabled, *more)
 
     def forward(self, input):
         if not self.takes_node(input):
             return super().forward(input)
         from . import _ext
-        return self._node(_ext.ext().bn_train, input)
+        return self._node(_ext.ext().bn_train, input, input.dtype != torch.float32)
 
     def forward_pooled(self, input):
         """max_pool2d(self(input), 3, 2, 1) as one node (bn_pool_train: the BatchNorm output is not kept, the backward
-        gathers its dy from the pooled gradient).  Call only when takes_node(input) holds."""
+        gathers its dy from the pooled gradient).  Call only when takes_pooled_node(input) holds."""
         from . import _ext
         return self._node(_ext.ext().bn_pool_train, input)
 
 
-def install(model: nn.Module) -> int:
-    """Give every nn.BatchNorm2d of `model` (the exact type) the forward above.  Returns the number of modules switched."""
+def install(model: nn.Module, x16: bool = False) -> int:
+    """Give every nn.BatchNorm2d of `model` (the exact type) the forward above; x16=True also enables the 16-bit backward
+    on them.  Returns the number of modules switched."""
     switched = 0
     for m in model.modules():
         if type(m) is nn.BatchNorm2d:
             m.__class__ = HipBackwardBatchNorm2d
+            if x16:
+                m.__dict__[_X16] = True
             switched += 1
     return switched
 
@@ -88,3 +119,4 @@ def uninstall(model: nn.Module) -> None:
     for m in model.modules():
         if type(m) is HipBackwardBatchNorm2d:
             m.__class__ = nn.BatchNorm2d
+            m.__dict__.pop(_X16, None)

@@ -1,4 +1,5 @@
-// Backward of training-mode BatchNorm for gfx950, dense fp32 NHWC seen as [M = N*H*W][C], C % 4 == 0.
+// Backward of training-mode BatchNorm for gfx950, dense NHWC seen as [M = N*H*W][C]: fp32 with C % 4 == 0, or bf16 / fp16
+// with C % 8 == 0 (a lane owns 16 bytes of a row either way).
 //
 // The forward stays with the framework (it saves the batch mean and invstd); this file replaces the three launches of
 // its backward with three bandwidth-bound ones:
@@ -14,9 +15,15 @@
 // the gradient of a 3x3 / stride 2 / padding 1 max pool behind the BatchNorm, gathered on the fly from the pooled gradient
 // and a 1-byte argmax code per output (DyPool, mhaq_fq_bn_pool_bwd; the codes are written by maxpool3s2_fwd_kernel at the
 // end of this file).  Partition, sums, finalize and the dx expression are one code for both.
+//
+// The element type comes with the source (Dy::IO): IoF32, or Io16<dtype> for x, dy and dx in bf16 / fp16 (DyMem16,
+// mhaq_fq_bn_bwd_x16).  A 16-bit element is converted UP exactly and takes the fp32 arithmetic unchanged -- the same fp64
+// sums, the same finalize, the same dx expression in the same order --; dx is rounded to nearest-even ONCE on the way out
+// (io16::down2: a plain cast, NaN stays NaN, fp16 overflow gives +-inf).  Statistics, weight, dweight, dbias and the
+// workspace stay fp32 / fp64.
 #include <type_traits>
 
-#include "fq_common.hpp"
+#include "fq_io16.hpp"
 
 namespace mhaq {
 
@@ -30,11 +37,46 @@ __device__ __forceinline__ void bn_st4(float* p, int64_t vidx, vf4 v) {
   __builtin_nontemporal_store(v, reinterpret_cast<vf4*>(p) + vidx);
 }
 
+// ---------------------------------------------------------------- the element type of x, dy and dx
+// One 16-byte access of a lane: kW elements, unpacked to / packed from fp32.
+struct IoF32 {
+  using T = float;
+  using Vec = vf4;
+  static constexpr int kW = 4;
+  template <bool NT>
+  static __device__ __forceinline__ Vec ld(const T* p, int64_t vidx) { return bn_ld4<NT>(p, vidx); }
+  static __device__ __forceinline__ void unpack(const Vec& v, float (&o)[4]) {
+    o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+  }
+  static __device__ __forceinline__ void st(T* p, int64_t vidx, const float (&o)[4]) {
+    bn_st4(p, vidx, vf4{o[0], o[1], o[2], o[3]});
+  }
+};
+template <int DT>
+struct Io16 {
+  using T = uint16_t;
+  using Vec = io16::vu4;
+  static constexpr int kW = 8;
+  template <bool NT>
+  static __device__ __forceinline__ Vec ld(const T* p, int64_t vidx) { return io16::ld8<NT>(p, vidx); }
+  static __device__ __forceinline__ void unpack(const Vec& v, float (&o)[8]) {
+#pragma unroll
+    for (int w = 0; w < 4; ++w) io16::up2<DT>(v[w], o[2 * w], o[2 * w + 1]);
+  }
+  static __device__ __forceinline__ void st(T* p, int64_t vidx, const float (&o)[8]) {
+    Vec v;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) v[w] = io16::down2<DT>(o[2 * w], o[2 * w + 1]);
+    io16::st8<true>(p, vidx, v);
+  }
+};
+
 // ---------------------------------------------------------------- where dy comes from
-// A source hands out, per float4 of x, a bundle of loads (issued with x's, before anything waits) and later the four dy
+// A source hands out, per 16-byte vector of x, a bundle of loads (issued with x's, before anything waits) and later the IO::kW dy
 // values out of it.  `Walk` follows a lane's rows through the reduction: (n, ih, iw) of a row, advanced by a fixed row
 // step without a division.
 struct DyMem {
+  using IO = IoF32;
   const float* __restrict__ dy;
   static constexpr int kDxWaves = 8;               // the occupancy the dx kernel is held to below kBnBigElems
   struct Walk {
@@ -55,6 +97,28 @@ struct DyMem {
   }
 };
 
+// dy as a 16-bit tensor in memory
+template <int DT>
+struct DyMem16 {
+  using IO = Io16<DT>;
+  const uint16_t* __restrict__ dy;
+  static constexpr int kDxWaves = 6;               // 70 VGPRs (40 of them the constants of 8 channels): 8 waves would spill
+  struct Walk {
+    __device__ __forceinline__ Walk(const DyMem16&, uint32_t, uint32_t) {}
+    __device__ __forceinline__ void next() {}
+  };
+  struct Loads { io16::vu4 v; };
+  template <bool NT>
+  __device__ __forceinline__ Loads load(int64_t vidx, const Walk&, bool, uint32_t, uint32_t) const {
+    return Loads{io16::ld8<NT>(dy, vidx)};
+  }
+  template <bool NT>
+  __device__ __forceinline__ Loads load_at_pixel(int64_t vidx, uint32_t, bool, uint32_t, uint32_t) const {
+    return Loads{io16::ld8<NT>(dy, vidx)};
+  }
+  __device__ __forceinline__ void value(const Loads& l, float (&o)[8]) const { IO::unpack(l.v, o); }
+};
+
 // dy[n, ih, iw, .] of max_pool2d(kernel 3, stride 2, padding 1) from the pooled gradient g[n, oh, ow, .] and the argmax
 // code (kh * 3 + kw of the chosen element, one byte per output element).  The windows that cover row ih are
 //   oh = ih / 2          with kh = 1 + ih % 2, always there, and
@@ -67,6 +131,7 @@ struct DyMem {
 constexpr uint32_t kPoolNoCode = 0xFFu;           // codes are 0 .. 8, and kPoolNoneChosen:
 constexpr uint32_t kPoolNoneChosen = 9u;          // a window that chose no element (maxpool3s2_fwd_kernel)
 struct DyPool {
+  using IO = IoF32;
   const float* __restrict__ g;
   const uint8_t* __restrict__ code;
   uint32_t h, w, oh, ow;
@@ -165,13 +230,13 @@ struct BnGeom {
   int64_t nchunks;   // grid.x
   int ncol;          // grid.y
 };
-static inline BnGeom bn_geom(int64_t m, int64_t c) {
-  const int64_t cv = c >> 2;
+// cv = 16-byte vectors per row
+static inline BnGeom bn_geom_of(int64_t m, int64_t cv, int64_t min_rows) {
   const int64_t cols = cv < kBnCols ? cv : kBnCols;
   const int64_t rpp = kBlock / cols;                       // rows per pass of a block
   const int64_t unit = rpp * kBnRedU;
   int64_t rows = (m + kBnMaxChunks - 1) / kBnMaxChunks;
-  if (rows < kBnMinRows) rows = kBnMinRows;
+  if (rows < min_rows) rows = min_rows;
   rows = (rows + unit - 1) / unit * unit;
   BnGeom g;
   g.rows = rows;
@@ -179,6 +244,17 @@ static inline BnGeom bn_geom(int64_t m, int64_t c) {
   g.ncol = (int)((cv + kBnCols - 1) / kBnCols);
   return g;
 }
+static inline BnGeom bn_geom(int64_t m, int64_t c) { return bn_geom_of(m, c >> 2, kBnMinRows); }
+// 16-bit tensors: a lane owns 8 channels, so a block's 16 columns are 128 channels (the same 256 bytes of a row) and there
+// are twice as many rows of lanes per column.  A row of the tensor is 2 C bytes against 16 C of a partial row: the 0.9 %
+// rule asks for 2 * kBnMinRows rows, and a block never takes fewer rows than the fp32 geometry gives the same [m][c].
+constexpr int kBn16MinRows = 2 * kBnMinRows;
+static inline BnGeom bn_geom16(int64_t m, int64_t c) {
+  const int64_t rows32 = bn_geom(m, c).rows;
+  return bn_geom_of(m, c >> 3, rows32 > kBn16MinRows ? rows32 : kBn16MinRows);
+}
+template <class IO>
+static inline BnGeom bn_geom_io(int64_t m, int64_t c) { return IO::kW == 8 ? bn_geom16(m, c) : bn_geom(m, c); }
 
 // Cache policy of the loads, by tensor size and pass (measured per size, docs/NOTEBOOK.md section 6 "BatchNorm backward").
 // x and dy are read twice within three launches.  Below kBnReduceNtElems the first read loads with the default policy
@@ -189,6 +265,22 @@ constexpr int64_t kBnDxNtElems = 28ll << 20;
 // occupancy of the dx kernel by size: the rule of pt_bwd_kernel (fq_pt.hip)
 constexpr int64_t kBnBigElems = 20ll << 20;
 constexpr int kBnBigMaxWaves = 6;     // (below kBnBigElems the kernel is held to Dy::kDxWaves: 8 with dy in memory)
+// The same three for 16-bit elements (4 B of x + dy and 2 B of dx per element).  The cache policy goes by BYTES: x + dy fit
+// the Infinity Cache up to twice the fp32 element count; the occupancy rule goes by elements, as in fq_io16.hip
+// (docs/NOTEBOOK.md section 6, "BatchNorm backward, 16-bit").
+// Each can be overridden at build time: tools/bn_bwd16_bench.py times builds with a forced policy next to the product's.
+#ifndef MHAQ_BN16_REDUCE_NT_ELEMS
+#define MHAQ_BN16_REDUCE_NT_ELEMS (56ll << 20)
+#endif
+#ifndef MHAQ_BN16_DX_NT_ELEMS
+#define MHAQ_BN16_DX_NT_ELEMS (56ll << 20)
+#endif
+#ifndef MHAQ_BN16_BIG_ELEMS
+#define MHAQ_BN16_BIG_ELEMS (20ll << 20)
+#endif
+constexpr int64_t kBn16ReduceNtElems = MHAQ_BN16_REDUCE_NT_ELEMS;
+constexpr int64_t kBn16DxNtElems = MHAQ_BN16_DX_NT_ELEMS;
+constexpr int64_t kBn16BigElems = MHAQ_BN16_BIG_ELEMS;
 
 // ---------------------------------------------------------------- 1. partial sums
 // partials[chunk][2][C] (fp64): row 0 = sum dy, row 1 = sum dy * (x - mean) over the chunk's rows.
@@ -201,8 +293,10 @@ constexpr int kBnBigMaxWaves = 6;     // (below kBnBigElems the kernel is held t
 // run at the fp32 rate on this chip and the kernel stays memory-bound (20 VALU operations per 32 loaded bytes).
 template <bool NT, class Dy, int U>
 __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_kernel(
-    const float* __restrict__ x, const Dy dy, const float* __restrict__ mean,
+    const typename Dy::IO::T* __restrict__ x, const Dy dy, const float* __restrict__ mean,
     double* __restrict__ partials, int64_t m, int cv, int64_t rows) {
+  using IO = typename Dy::IO;
+  constexpr int K = IO::kW;                                    // channels of a lane
   const int c0 = (int)blockIdx.y * kBnCols;
   const int cols = (cv - c0) < kBnCols ? (cv - c0) : kBnCols;
   const int rpp = kBlock / cols;
@@ -211,15 +305,15 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_kernel(
   const int64_t row0 = (int64_t)blockIdx.x * rows;
   const int64_t rend = (row0 + rows < m) ? row0 + rows : m;    // > row0: the grid has ceil(m / rows) chunks
   const int64_t colv = c0 + tx;
-  float mu[4];
+  float mu[K];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) mu[j] = mean[colv * 4 + j];
-  double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
+  for (int j = 0; j < K; ++j) mu[j] = mean[colv * K + j];
+  double s1[K] = {}, s2[K] = {};
   typename Dy::Walk walk(dy, (uint32_t)(row0 + ty), (uint32_t)rpp);       // (the pool's source: m < 2^31)
   for (int64_t rb = row0 + ty; rb - ty < rend; rb += (int64_t)rpp * U) {
     // unconditional, clamped loads: all of the U rows in flight before anything waits; lanes past the chunk's end
     // re-read its last row and drop it
-    vf4 a[U];
+    typename IO::Vec a[U];
     typename Dy::Loads b[U];
     bool ok[U];
 #pragma unroll
@@ -227,18 +321,18 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_kernel(
       const int64_t r = rb + (int64_t)u * rpp;
       ok[u] = live && r < rend;
       const int64_t vidx = (ok[u] ? r : rend - 1) * cv + colv;
-      a[u] = bn_ld4<NT>(x, vidx);
+      a[u] = IO::template ld<NT>(x, vidx);
       b[u] = dy.template load<NT>(vidx, walk, ok[u], (uint32_t)colv, (uint32_t)cv);
       walk.next();
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const float av[4] = {a[u].x, a[u].y, a[u].z, a[u].w};
-      float bv[4];
+      float av[K], bv[K];
+      IO::unpack(a[u], av);
       dy.value(b[u], bv);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
+      for (int j = 0; j < K; ++j) {
         const double g = ok[u] ? (double)bv[j] : 0.0;          // a select, not a product: a dropped NaN stays dropped
         const double d = ok[u] ? (double)av[j] - (double)mu[j] : 0.0;
         s1[j] += g;
@@ -246,14 +340,14 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_kernel(
       }
     }
   }
-  // across the block's rows of lanes: LDS [ty][2][4 * cols], then thread (k, c) adds its column in row order
-  __shared__ __align__(16) double sm[kBlock * 8];
-  const int w = 4 * cols;
+  // across the block's rows of lanes: LDS [ty][2][K * cols], then thread (k, c) adds its column in row order
+  __shared__ __align__(16) double sm[kBlock * 2 * K];
+  const int w = K * cols;
   if (live) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      sm[(ty * 2 + 0) * w + tx * 4 + j] = s1[j];
-      sm[(ty * 2 + 1) * w + tx * 4 + j] = s2[j];
+    for (int j = 0; j < K; ++j) {
+      sm[(ty * 2 + 0) * w + tx * K + j] = s1[j];
+      sm[(ty * 2 + 1) * w + tx * K + j] = s2[j];
     }
   }
   __syncthreads();
@@ -261,7 +355,7 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_kernel(
     const int k = (int)threadIdx.x >= w ? 1 : 0, c = (int)threadIdx.x - k * w;
     double tot = 0.0;
     for (int r = 0; r < rpp; ++r) tot += sm[(r * 2 + k) * w + c];
-    partials[((int64_t)blockIdx.x * 2 + k) * ((int64_t)cv * 4) + (int64_t)c0 * 4 + c] = tot;
+    partials[((int64_t)blockIdx.x * 2 + k) * ((int64_t)cv * K) + (int64_t)c0 * K + c] = tot;
   }
 }
 
@@ -314,15 +408,17 @@ template <bool NT, bool BIG, class Dy>
 __global__ __attribute__((amdgpu_waves_per_eu(
     (BIG ? 1 : Dy::kDxWaves), (BIG && kBnBigMaxWaves < Dy::kDxWaves ? kBnBigMaxWaves : Dy::kDxWaves))))
 __launch_bounds__(kBlock) void bn_bwd_dx_kernel(
-    const float* __restrict__ x, const Dy dy, float* __restrict__ dx, int64_t nvec, int cv,
+    const typename Dy::IO::T* __restrict__ x, const Dy dy, typename Dy::IO::T* __restrict__ dx, int64_t nvec, int cv,
     const float* __restrict__ consts) {
+  using IO = typename Dy::IO;
+  constexpr int K = IO::kW;
   const int64_t blk0 = (int64_t)blockIdx.x * (kBlock * kBnDxU);
   const int64_t base = blk0 + threadIdx.x;
   const bool full = blk0 + kBlock * kBnDxU <= nvec;
-  vf4 a[kBnDxU];
+  typename IO::Vec a[kBnDxU];
   typename Dy::Loads b[kBnDxU];
   uint32_t pix0 = 0, col0 = 0;
-  if constexpr (!std::is_same<Dy, DyMem>::value) {
+  if constexpr (std::is_same<Dy, DyPool>::value) {
     const uint32_t q = blockIdx.x / (uint32_t)cv, r = (blockIdx.x - q * (uint32_t)cv) * (uint32_t)(kBlock * kBnDxU);
     const uint32_t rq = r / (uint32_t)cv;
     pix0 = q * (uint32_t)(kBlock * kBnDxU) + rq;
@@ -333,7 +429,7 @@ __launch_bounds__(kBlock) void bn_bwd_dx_kernel(
     const int64_t idx = base + u * kBlock;
     const bool ok = full || idx < nvec;
     const int64_t idc = ok ? idx : nvec - 1;
-    a[u] = bn_ld4<NT>(x, idc);
+    a[u] = IO::template ld<NT>(x, idc);
     const uint32_t t = col0 + (uint32_t)(u * kBlock), tq = t / (uint32_t)cv;
     b[u] = dy.template load_at_pixel<NT>(idc, pix0 + tq, ok, t - tq * (uint32_t)cv, (uint32_t)cv);
   }
@@ -343,8 +439,8 @@ __launch_bounds__(kBlock) void bn_bwd_dx_kernel(
   const uint32_t cb = ((blockIdx.x % ucv) * ((uint32_t)(kBlock * kBnDxU) % ucv)) % ucv;      // wave-uniform
   const uint32_t step = (uint32_t)kBlock % ucv;                                               // wave-uniform
   uint32_t col = (cb + threadIdx.x) % ucv;
-  const int64_t c = (int64_t)cv * 4;
-  float k[kBnNConst][4];
+  const int64_t c = (int64_t)cv * K;
+  float k[kBnNConst][K / 4][4];
 #pragma unroll
   for (int u = 0; u < kBnDxU; ++u) {
     const int64_t idx = base + u * kBlock;
@@ -354,18 +450,21 @@ __launch_bounds__(kBlock) void bn_bwd_dx_kernel(
     }
     if (u == 0 || step != 0) {
 #pragma unroll
-      for (int q = 0; q < kBnNConst; ++q) ldv<4>(consts + q * c + (int64_t)col * 4, k[q]);
+      for (int q = 0; q < kBnNConst; ++q)
+#pragma unroll
+        for (int h = 0; h < K / 4; ++h) ldv<4>(consts + q * c + (int64_t)col * K + 4 * h, k[q][h]);
     }
     if (full || idx < nvec) {
-      const float xv[4] = {a[u].x, a[u].y, a[u].z, a[u].w};
-      float gv[4], o[4];
+      float xv[K], gv[K], o[K];
+      IO::unpack(a[u], xv);
       dy.value(b[u], gv);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float xh = (xv[j] - k[0][j]) * k[1][j];
-        o[j] = k[2][j] * ((gv[j] - k[3][j]) - xh * k[4][j]);
+      for (int j = 0; j < K; ++j) {
+        const int h = j >> 2, i = j & 3;
+        const float xh = (xv[j] - k[0][h][i]) * k[1][h][i];
+        o[j] = k[2][h][i] * ((gv[j] - k[3][h][i]) - xh * k[4][h][i]);
       }
-      bn_st4(dx, idx, vf4{o[0], o[1], o[2], o[3]});
+      IO::st(dx, idx, o);
     }
   }
 }
@@ -374,23 +473,27 @@ static inline bool bn_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p
 
 // The three launches behind both entry points (arguments checked by the caller); RU = rows in flight in the reduction.
 template <class Dy, int RU>
-static int bn_bwd_launch(const float* x, const Dy dy, const float* mean, const float* invstd, const float* weight,
-                         float* dx, float* dweight, float* dbias, int64_t m, int64_t c, void* workspace, hipStream_t st) {
-  const BnGeom g = bn_geom(m, c);
-  const int64_t nvec = m * (c >> 2);
+static int bn_bwd_launch(const typename Dy::IO::T* x, const Dy dy, const float* mean, const float* invstd,
+                         const float* weight, typename Dy::IO::T* dx, float* dweight, float* dbias, int64_t m, int64_t c,
+                         void* workspace, hipStream_t st) {
+  using IO = typename Dy::IO;
+  constexpr bool x16 = IO::kW == 8;
+  const BnGeom g = bn_geom_io<IO>(m, c);
+  const int64_t nvec = m * (c / IO::kW);
   const int64_t dx_grid = (nvec + kBlock * kBnDxU - 1) / (kBlock * kBnDxU);
   if (g.nchunks > 0x7fffffff || dx_grid > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
   if (!dx && !dweight && !dbias) return 0;
   float* consts = (float*)workspace;
   double* parts = (double*)(consts + kBnNConst * c);      // 20 * c bytes in: 16-byte aligned (c % 4 == 0)
-  const int cv = (int)(c >> 2);
-  const bool nt_r = m * c >= kBnReduceNtElems, nt_d = m * c >= kBnDxNtElems, big = m * c >= kBnBigElems;
+  const int cv = (int)(c / IO::kW);
+  const bool nt_r = m * c >= (x16 ? kBn16ReduceNtElems : kBnReduceNtElems);
+  const bool nt_d = m * c >= (x16 ? kBn16DxNtElems : kBnDxNtElems), big = m * c >= (x16 ? kBn16BigElems : kBnBigElems);
   const dim3 rgrid((unsigned)g.nchunks, (unsigned)g.ncol);
   if (nt_r) MHAQ_LAUNCH((bn_bwd_reduce_kernel<true, Dy, RU>), rgrid, dim3(kBlock), 0, st, x, dy, mean, parts, m, cv, g.rows);
   else MHAQ_LAUNCH((bn_bwd_reduce_kernel<false, Dy, RU>), rgrid, dim3(kBlock), 0, st, x, dy, mean, parts, m, cv, g.rows);
   int rc = launch_status();
   if (rc) return rc;
-  MHAQ_LAUNCH(bn_bwd_finalize_kernel, dim3((unsigned)cv), dim3(kBlock), 0, st, (const double*)parts, (int)g.nchunks,
+  MHAQ_LAUNCH(bn_bwd_finalize_kernel, dim3((unsigned)(c >> 2)), dim3(kBlock), 0, st, (const double*)parts, (int)g.nchunks,
               (int)c, mean, invstd, weight, 1.0 / (double)m, consts, dweight, dbias);
   rc = launch_status();
   if (rc || !dx) return rc;
@@ -494,6 +597,34 @@ int mhaq_fq_bn_bwd(const float* x, const float* dy, const float* mean, const flo
     return MHAQ_FQ_EALIGN;
   return bn_bwd_launch<DyMem, kBnRedU>(x, DyMem{dy}, mean, invstd, weight, dx, dweight, dbias, m, c, workspace,
                                        (hipStream_t)stream);
+}
+
+size_t mhaq_fq_bn_bwd_x16_workspace_bytes(int64_t m, int64_t c) {
+  if (m <= 0 || c <= 0 || (c & 7) || c > kBnMaxChannels) return 0;
+  return ((size_t)kBnNConst * sizeof(float) + 2 * (size_t)bn_geom16(m, c).nchunks * sizeof(double)) * (size_t)c;
+}
+
+int mhaq_fq_bn_bwd_x16(const void* x, const void* dy, const float* mean, const float* invstd, const float* weight, void* dx,
+                       float* dweight, float* dbias, int64_t m, int64_t c, int dtype, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+  if (m <= 0 || c <= 0 || !x || !dy || !mean || !invstd || !workspace) return MHAQ_FQ_EINVAL;
+  if (dtype != MHAQ_FQ_DT_BF16 && dtype != MHAQ_FQ_DT_F16) return MHAQ_FQ_EINVAL;
+  // C % 8: a lane owns 8 channels
+  if ((c & 7) || c > kBnMaxChannels || m > (INT64_MAX >> 3) / c) return MHAQ_FQ_EUNSUPPORTED;
+  if (workspace_bytes < mhaq_fq_bn_bwd_x16_workspace_bytes(m, c)) return MHAQ_FQ_EWORKSPACE;
+  if (!bn_aligned(x, 16) || !bn_aligned(dy, 16) || !bn_aligned(dx, 16) || !bn_aligned(workspace, 16) ||
+      !bn_aligned(mean, 4) || !bn_aligned(invstd, 4) || !bn_aligned(weight, 4) || !bn_aligned(dweight, 4) ||
+      !bn_aligned(dbias, 4))
+    return MHAQ_FQ_EALIGN;
+  const uint16_t* x16 = (const uint16_t*)x;
+  const uint16_t* dy16 = (const uint16_t*)dy;
+  if (dtype == MHAQ_FQ_DT_BF16)
+    return bn_bwd_launch<DyMem16<MHAQ_FQ_DT_BF16>, kBnRedU>(x16, DyMem16<MHAQ_FQ_DT_BF16>{dy16}, mean, invstd, weight,
+                                                            (uint16_t*)dx, dweight, dbias, m, c, workspace,
+                                                            (hipStream_t)stream);
+  return bn_bwd_launch<DyMem16<MHAQ_FQ_DT_F16>, kBnRedU>(x16, DyMem16<MHAQ_FQ_DT_F16>{dy16}, mean, invstd, weight,
+                                                         (uint16_t*)dx, dweight, dbias, m, c, workspace,
+                                                         (hipStream_t)stream);
 }
 
 int mhaq_fq_maxpool3s2_fwd(const float* t, float* p, uint8_t* code, int64_t n, int64_t h, int64_t w, int64_t c,

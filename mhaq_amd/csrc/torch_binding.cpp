@@ -56,7 +56,8 @@ namespace {
   X(mhaq_fq_act_relu_fwd) X(mhaq_fq_act_relu_bwd) X(mhaq_fq_act_relu_bwd_partials)                                    \
   X(mhaq_fq_act_relu_fwd_x16) X(mhaq_fq_act_relu_bwd_x16) X(mhaq_fq_act_relu_bwd_partials_x16)                        \
   X(mhaq_fq_bn_bwd_workspace_bytes) X(mhaq_fq_bn_bwd) X(mhaq_fq_maxpool3s2_fwd)                                       \
-  X(mhaq_fq_bn_pool_bwd_workspace_bytes) X(mhaq_fq_bn_pool_bwd)
+  X(mhaq_fq_bn_pool_bwd_workspace_bytes) X(mhaq_fq_bn_pool_bwd) X(mhaq_fq_bn_bwd_x16_workspace_bytes)                 \
+  X(mhaq_fq_bn_bwd_x16)
 
 struct Api {
 #define X(n) decltype(&::n) n = nullptr;
@@ -684,6 +685,8 @@ std::tuple<Tensor, std::optional<Tensor>, Tensor, Tensor, Tensor> act_relu_layer
 // runs mhaq_fq_bn_bwd on a dense float32 channels_last tensor with C % 4 == 0.  Everything else takes
 // at::_batch_norm_impl_index_backward with the saved implementation index and reserve: the backward autograd itself
 // would have run.  The gradients of the HIP path differ from it by summation order only.  Once-differentiable.
+// A bf16 / fp16 x (the convolution's output under autocast) takes mhaq_fq_bn_bwd_x16 where the caller enabled that route for
+// the call (`x16`): C % 8 == 0, fp32 weight and statistics, and a dy of x's dtype; its dx is the fp32 arithmetic rounded once.
 inline bool aligned16(const Tensor& t) { return (reinterpret_cast<uintptr_t>(t.const_data_ptr()) & 15) == 0; }
 
 inline bool bn_bwd_eligible(const Tensor& x, const Tensor& w, const Tensor& mean, const Tensor& invstd) {
@@ -695,19 +698,34 @@ inline bool bn_bwd_eligible(const Tensor& x, const Tensor& w, const Tensor& mean
   return stat_ok(mean) && stat_ok(invstd) && (!w.defined() || stat_ok(w));
 }
 
+// the 16-bit route: as above with 8 channels per 16-byte access; dy (in x's layout) must have x's dtype
+inline bool bn_bwd_x16_eligible(const Tensor& x, const Tensor& dy, const Tensor& w, const Tensor& mean,
+                                const Tensor& invstd) {
+  if (!x.is_cuda() || act_dtype(x) == 0 || x.dim() != 4 || x.numel() == 0) return false;
+  if (!x.is_contiguous(at::MemoryFormat::ChannelsLast) || (x.size(1) & 7) || !aligned16(x)) return false;
+  if (dy.scalar_type() != x.scalar_type() || !dy.is_cuda() || dy.sizes() != x.sizes()) return false;
+  auto stat_ok = [&](const Tensor& t) {
+    return t.defined() && t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == x.size(1);
+  };
+  return stat_ok(mean) && stat_ok(invstd) && (!w.defined() || stat_ok(w));
+}
+
 std::atomic<int64_t> g_bn_hip_backwards{0};   // backwards that took mhaq_fq_bn_bwd (tests: the fallback is never silent)
+std::atomic<int64_t> g_bn_hip_backwards_x16{0};   // ... that took mhaq_fq_bn_bwd_x16
 
 class BatchNormTrainFn : public torch::autograd::Function<BatchNormTrainFn> {
  public:
   static Tensor forward(AutogradContext* ctx, const Tensor& x, const std::optional<Tensor>& w,
                         const std::optional<Tensor>& b, const std::optional<Tensor>& running_mean,
-                        const std::optional<Tensor>& running_var, double momentum, double eps, bool cudnn_enabled) {
+                        const std::optional<Tensor>& running_var, double momentum, double eps, bool cudnn_enabled,
+                        bool x16) {
     auto out = at::_batch_norm_impl_index(x, w, b, running_mean, running_var, /*training=*/true, momentum, eps,
                                           cudnn_enabled);
     const bool has_w = w.has_value() && w->defined();
     ctx->save_for_backward({x, has_w ? *w : Tensor(), std::get<1>(out), std::get<2>(out), std::get<3>(out)});
     ctx->saved_data["impl"] = std::get<4>(out);
     ctx->saved_data["eps"] = eps;
+    ctx->saved_data["x16"] = x16;
     // read by no training-mode backward; handed on as the framework's own node does, without its version check
     if (running_mean.has_value() && running_mean->defined()) ctx->saved_data["rm"] = *running_mean;
     if (running_var.has_value() && running_var->defined()) ctx->saved_data["rv"] = *running_var;
@@ -716,7 +734,7 @@ class BatchNormTrainFn : public torch::autograd::Function<BatchNormTrainFn> {
   }
 
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    variable_list out(8);
+    variable_list out(9);
     if (!grads[0].defined()) return out;
     TORCH_CHECK(!(at::GradMode::is_enabled() && grads[0].requires_grad()),
                 "bn_train: the node is once-differentiable (no double backward)");
@@ -725,6 +743,29 @@ class BatchNormTrainFn : public torch::autograd::Function<BatchNormTrainFn> {
     const Tensor &x = saved[0], &w = saved[1], &mean = saved[2], &invstd = saved[3], &reserve = saved[4];
     const std::array<bool, 3> mask = {ctx->needs_input_grad(0), w.defined() && ctx->needs_input_grad(1),
                                       ctx->needs_input_grad(2)};
+    if (ctx->saved_data["x16"].toBool() && x.is_cuda() && act_dtype(x) != 0 && grads[0].scalar_type() == x.scalar_type() &&
+        grads[0].sizes() == x.sizes()) {
+      const Tensor dy = like_layout(grads[0], x);
+      if (bn_bwd_x16_eligible(x, dy, w, mean, invstd)) {
+        need_lib();
+        const int64_t c = x.size(1), m = x.numel() / c;
+        Tensor dx = mask[0] ? at::empty_like(x) : Tensor();
+        Tensor dw = mask[1] ? at::empty_like(w) : Tensor();
+        Tensor db = mask[2] ? at::empty({c}, mean.options()) : Tensor();
+        const size_t nb = A.mhaq_fq_bn_bwd_x16_workspace_bytes(m, c);
+        Tensor ws = at::empty({(int64_t)nb}, x.options().dtype(at::kByte));
+        check(A.mhaq_fq_bn_bwd_x16(x.const_data_ptr(), dy.const_data_ptr(), fptr(mean), fptr(invstd), fptr_or_null(w),
+                                   mask[0] ? dx.mutable_data_ptr() : nullptr, mask[1] ? fptr_mut(dw) : nullptr,
+                                   mask[2] ? fptr_mut(db) : nullptr, m, c, act_dtype(x), ws.mutable_data_ptr(), nb,
+                                   cur_stream(x)),
+              "mhaq_fq_bn_bwd_x16");
+        g_bn_hip_backwards_x16.fetch_add(1, std::memory_order_relaxed);
+        out[0] = dx;
+        out[1] = dw;
+        out[2] = db;
+        return out;
+      }
+    }
     if (!bn_bwd_eligible(x, w, mean, invstd)) {
       auto opt = [](const Tensor& t) { return t.defined() ? std::optional<Tensor>(t) : std::nullopt; };
       auto get = [&](const char* k) {
@@ -760,11 +801,11 @@ class BatchNormTrainFn : public torch::autograd::Function<BatchNormTrainFn> {
 
 Tensor bn_train(const Tensor& x, const std::optional<Tensor>& w, const std::optional<Tensor>& b,
                 const std::optional<Tensor>& running_mean, const std::optional<Tensor>& running_var, double momentum,
-                double eps, bool cudnn_enabled) {
+                double eps, bool cudnn_enabled, bool x16) {
   TORCH_CHECK(w.has_value() && w->defined() && b.has_value() && b->defined(),
               "bn_train: an affine BatchNorm (weight and bias) is required");
   MHAQ_ON_DEVICE_OF(x);
-  return BatchNormTrainFn::apply(x, w, b, running_mean, running_var, momentum, eps, cudnn_enabled);
+  return BatchNormTrainFn::apply(x, w, b, running_mean, running_var, momentum, eps, cudnn_enabled, x16);
 }
 
 // ------------------------------------------------------------------------------------------------ BatchNorm + stem pool
@@ -850,7 +891,8 @@ Tensor bn_pool_train(const Tensor& x, const std::optional<Tensor>& w, const std:
               "bn_pool_train: an affine BatchNorm (weight and bias) is required");
   MHAQ_ON_DEVICE_OF(x);
   if (!bn_pool_eligible(x, *w))
-    return at::max_pool2d(BatchNormTrainFn::apply(x, w, b, running_mean, running_var, momentum, eps, cudnn_enabled),
+    return at::max_pool2d(BatchNormTrainFn::apply(x, w, b, running_mean, running_var, momentum, eps, cudnn_enabled,
+                                                  /*x16=*/false),
                           {3, 3}, {2, 2}, {1, 1});
   need_lib();
   return BatchNormPoolTrainFn::apply(x, *w, *b, running_mean, running_var, momentum, eps, cudnn_enabled);
@@ -1525,10 +1567,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
 
   // training BatchNorm: the framework's forward, the HIP backward
   m.def("bn_train", &bn_train, py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("running_mean"),
-        py::arg("running_var"), py::arg("momentum"), py::arg("eps"), py::arg("cudnn_enabled") = true);
+        py::arg("running_var"), py::arg("momentum"), py::arg("eps"), py::arg("cudnn_enabled") = true,
+        py::arg("x16") = false);
 
   m.def("bn_hip_backwards", []() { return g_bn_hip_backwards.load(); },
-        "number of BatchNorm backwards so far that ran the HIP kernels instead of the framework's backward");
+        "number of BatchNorm backwards so far that ran the fp32 HIP kernels instead of the framework's backward");
+  m.def("bn_hip_backwards_x16", []() { return g_bn_hip_backwards_x16.load(); },
+        "number of BatchNorm backwards so far that ran the 16-bit HIP kernels (mhaq_fq_bn_bwd_x16)");
   // ... with the stem's 3x3 / stride 2 max pool in the same node
   m.def("bn_pool_train", &bn_pool_train, py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("running_mean"),
         py::arg("running_var"), py::arg("momentum"), py::arg("eps"), py::arg("cudnn_enabled") = true);

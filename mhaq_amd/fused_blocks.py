@@ -39,7 +39,8 @@ fused path is the same under DDP and SyncBatchNorm.
     (HipBackwardBatchNorm2d.forward_pooled): the [N,64,112,112] BatchNorm output is not kept for the backward, no int64
     indices are written, and the BatchNorm backward gathers its dy from the pooled gradient instead of reading one the
     pool's backward wrote.  Same bits in every output and gradient.  fp32 only: under autocast
-    takes_node() is false and the stem runs maxpool(bn(c)) in front of the fused quantizer.
+    takes_pooled_node() is false and the stem runs maxpool(bn(c)) in front of the fused quantizer (a 16-bit input is refused
+    up front, also where the BatchNorm's own 16-bit backward is enabled).
 
 MHAQ_FUSE_BLOCKS=0 in the environment keeps QATTrainer from installing (A/B runs of an unchanged benchmark);
 QATConfig.fuse_blocks=False does the same per trainer.  MHAQ_STEM_POOL=0 / QATConfig.fuse_stem_pool=False keep only the
@@ -163,7 +164,7 @@ class FusedResNet18(nets.ResNet18):
             # (BatchNorm and pool keep dtype, device and density: what holds for the convolution's output holds for theirs)
             if q is not None and _hook_free(self.maxpool, self.layer1, first) and q.can_fuse_relu(c):
                 bn = self.bn1
-                if (self.__dict__.get(_STEM_POOL) and type(bn) is HipBackwardBatchNorm2d and bn.takes_node(c)
+                if (self.__dict__.get(_STEM_POOL) and type(bn) is HipBackwardBatchNorm2d and bn.takes_pooled_node(c)
                         and _is_stem_pool(self.maxpool) and _hook_free(bn)):
                     p = bn.forward_pooled(c)
                 else:

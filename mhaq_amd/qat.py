@@ -65,6 +65,9 @@ class QATConfig:
     # backward of every nn.BatchNorm2d on the HIP kernels of csrc/bn_bwd.hip; the forward stays the framework's, bit for bit
     # (bn_backward.py).  MHAQ_BN_BACKWARD=0 in the environment switches it off.
     hip_bn_backward: bool = True
+    # ... and on the 16-bit tensors of an autocast step (mhaq_fq_bn_bwd_x16: dx is the fp32 arithmetic rounded once, so the
+    # gradient bits of a bf16 run change).  Off by default; MHAQ_BN_BACKWARD_X16=1 / 0 in the environment overrides it.
+    hip_bn_backward_16bit: bool = False
     criterion: nn.Module = field(default_factory=nn.CrossEntropyLoss)
     # mixed precision (the reference trainer's `precision = "bf16-mixed"`, training/trainer.py:126): torch.bfloat16 runs
     # the teacher and student forwards, the loss and validate_step's forward under torch.autocast; the activation
@@ -223,7 +226,7 @@ class QATTrainer:
         if cfg.hip_bn_backward and layers is None and self.device.type == "cuda":
             from . import bn_backward
             if bn_backward.enabled_by_env():
-                bn_backward.install(net)
+                bn_backward.install(net, x16=bn_backward.x16_enabled(cfg.hip_bn_backward_16bit))
         self.net = net
         self.teacher_stream = None
         if cfg.distillation and cfg.overlap_teacher and self.device.type == "cuda":
