@@ -16,7 +16,9 @@
 // The element bodies below are COPIES of fq_pt.hip's fwd_elem (WRITE_Q = false) and bwd_elem / bwd_elem_fast
 // (COUNT = false), verbatim in arithmetic: fq_pt.hip stays untouched because the committed traffic profile
 // (profiles/r06_traffic.json) is tied to its hash.  tests/test_gpu_act16.py holds the copies to the fp32 kernels bit
-// for bit; folding both into a shared header belongs to the next change that re-measures traffic anyway.
+// for bit; folding both into a shared header belongs to the next change that re-measures traffic anyway.  Inside this
+// file nothing is kept twice: the plain and the ReLU backward kernel are one body (x16_bwd_body), and their entry
+// points share one validation / geometry / launch path (bwd_partials).
 //
 // ReLU (+ residual add) forms (mhaq_fq_act_relu_*_x16, further down): the NoisyAct behind a ReLU as ONE launch per direction,
 // as fq_pt.hip's pt_fwd_relu_kernel / pt_bwd_relu_kernel.  Their contract is NOT "the fp32 result rounded once" but the bits of
@@ -24,6 +26,8 @@
 // kernels above): z + addend is rounded to 16 bits before the ReLU, and the gradient gq is rounded to 16 bits BEFORE g_a is
 // added and the sum is rounded again -- two roundings, as the quantizer's 16-bit gx and autograd's 16-bit add give them.
 // Partial rows, geometry, sign tile and workspace rule are those of x16_act_bwd_kernel on (relu(z), g_y).
+#include <type_traits>
+
 #include "fq_io16.hpp"   // up2 / down2 / ld8 / st8: shared with bn_bwd.hip
 
 namespace mhaq {
@@ -244,155 +248,6 @@ __device__ inline void publish_act_scales(float* __restrict__ partials, const fl
   }
 }
 
-// occupancy by size as fq_pt.hip pt_bwd_kernel: at least 8 waves per SIMD on the latency-limited small tensors, at most
-// 6 on the bandwidth-limited big ones (the element kernel of unaligned views carries no lower bound)
-#define MHAQ_X16_BWD_OCC \
-  __attribute__((amdgpu_waves_per_eu(((BIG || !ALIGNED) ? 1 : 8), (BIG ? 6 : 8)))) __launch_bounds__(kBlock)
-
-template <int DT, int METHOD, bool RSIGN, bool ALIGNED, bool BIG>
-__global__ MHAQ_X16_BWD_OCC void x16_act_bwd_kernel(
-    const uint16_t* __restrict__ x, const uint16_t* __restrict__ g, uint16_t* __restrict__ gx, int64_t n,
-    const float* __restrict__ params, const int8_t* __restrict__ r_sign, uint64_t seed, uint64_t offset,
-    const uint64_t* __restrict__ offset_dev, float* __restrict__ partials) {
-  constexpr bool NEED_R = (METHOD != MHAQ_FQ_LSQ);
-  constexpr bool FAST_METHOD = (METHOD == MHAQ_FQ_STE || METHOD == MHAQ_FQ_LSQ);
-  constexpr int U = bwd_u(BIG);
-  constexpr int kTileCalls = 16 * U;              // 2048 * U elements per block / 128 per call
-  float acc[kAcc] = {0.f, 0.f, 0.f, 0.f};
-  const int64_t nvec = n >> 3;
-  const int64_t base = (int64_t)blockIdx.x * (kBlock * U) + threadIdx.x;
-  const bool full = ((int64_t)blockIdx.x + 1) * (kBlock * U) <= nvec;
-  vu4 a[U], b[U];
-  uint64_t rs[U];
-  if (ALIGNED) {
-    // unconditional loads, lanes past the end re-read the last vector (fq_pt.hip); the launcher sends n < 8 to the
-    // element kernel, so nvec >= 1 here
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int64_t idx = base + u * kBlock;
-      const int64_t idc = (full || idx < nvec) ? idx : nvec - 1;
-      a[u] = ld8<true>(x, idc);
-      b[u] = ld8<true>(g, idc);
-      if (NEED_R && RSIGN) rs[u] = reinterpret_cast<const uint64_t*>(r_sign)[idc];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  offset = stream_offset(offset, offset_dev);
-  const float p_s = params[0], p_zp = params[1], p_lo = params[2], p_hi = params[3];
-  __shared__ __align__(16) uint32_t stile[4 * kTileCalls];
-  if (ALIGNED && NEED_R && !RSIGN) {
-    sign_tile_fill(stile, (int64_t)blockIdx.x * kTileCalls, kTileCalls, seed, offset);
-    __syncthreads();
-  }
-  const BwdCtx k = make_bwd_ctx(p_s, p_zp, p_lo, p_hi);
-
-  if (ALIGNED) {
-    // this lane's sign byte: vector u*256 + t of the block = bits [8*(u*256 + t), +8) of the tile, inverted once
-    uint32_t nb[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      nb[u] = 0;
-      if (NEED_R && !RSIGN) nb[u] = ~(stile[(u * kBlock + (int)threadIdx.x) >> 2] >> (((int)threadIdx.x & 3) * 8));
-    }
-    const bool fast = FAST_METHOD && k.fast_div && (k.lo < k.hi) && (k.s > 0.f);      // wave-uniform
-    if (FAST_METHOD && fast) {
-      const float hcs = (MHAQ_INV_SQRT3 * k.s) * 0.5f;
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int64_t idx = base + u * kBlock;
-        if (full || idx < nvec) {
-          vu4 o;
-#pragma unroll
-          for (int w = 0; w < 4; ++w) {
-            float x0, x1, g0, g1;
-            up2<DT>(a[u][w], x0, x1);
-            up2<DT>(b[u][w], g0, g1);
-            float rc0 = 0.f, rc1 = 0.f;
-            if (NEED_R) {
-              if (RSIGN) {
-                rc0 = ((int8_t)((rs[u] >> (16 * w)) & 0xff) > 0) ? hcs : -hcs;
-                rc1 = ((int8_t)((rs[u] >> (16 * w + 8)) & 0xff) > 0) ? hcs : -hcs;
-              } else {
-                rc0 = signed_half_scale(nb[u], 2 * w, hcs);
-                rc1 = signed_half_scale(nb[u], 2 * w + 1, hcs);
-              }
-            }
-            const float y0 = bwd_elem_fast<METHOD>(x0, g0, rc0, k, acc);
-            const float y1 = bwd_elem_fast<METHOD>(x1, g1, rc1, k, acc);
-            o[w] = down2<DT>(y0, y1);
-          }
-          st8<true>(gx, idx, o);
-        }
-      }
-    } else {
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int64_t idx = base + u * kBlock;
-        if (full || idx < nvec) {
-          vu4 o;
-#pragma unroll
-          for (int w = 0; w < 4; ++w) {
-            float x0, x1, g0, g1;
-            up2<DT>(a[u][w], x0, x1);
-            up2<DT>(b[u][w], g0, g1);
-            float r0 = 0.f, r1 = 0.f;
-            if (NEED_R) {
-              if (RSIGN) {
-                r0 = sign_half((int8_t)((rs[u] >> (16 * w)) & 0xff));
-                r1 = sign_half((int8_t)((rs[u] >> (16 * w + 8)) & 0xff));
-              } else {
-                const uint32_t bits = ~nb[u];
-                r0 = ((bits >> (2 * w)) & 1u) ? 0.5f : -0.5f;
-                r1 = ((bits >> (2 * w + 1)) & 1u) ? 0.5f : -0.5f;
-              }
-            }
-            const float y0 = bwd_elem<METHOD>(x0, g0, r0, 0.f, k, acc);
-            const float y1 = bwd_elem<METHOD>(x1, g1, r1, 0.f, k, acc);
-            o[w] = down2<DT>(y0, y1);
-          }
-          st8<true>(gx, idx, o);
-        }
-      }
-    }
-    const int64_t t = (nvec << 3) + threadIdx.x;
-    if (blockIdx.x == 0 && t < n) {   // n % 8 tail elements
-      float r = 0.f;
-      if (NEED_R) r = RSIGN ? sign_half(r_sign[t]) : philox_r(t, seed, offset);
-      gx[t] = down1<DT>(bwd_elem<METHOD>(up1<DT>(x[t]), up1<DT>(g[t]), r, 0.f, k, acc));
-    }
-    if (BIG) {
-      __shared__ float smf[kAcc * (kBlock / 64)];
-      double tot[kAcc];
-      block_sum_f32<kAcc>(acc, tot, smf);
-      if (threadIdx.x == 0) write_act_partials(partials, tot, (int64_t)gridDim.x, (int64_t)blockIdx.x);
-      publish_act_scales(partials, params, (int64_t)gridDim.x);
-    } else {
-      float wsum[kAcc];
-#pragma unroll
-      for (int q = 0; q < kAcc; ++q) wsum[q] = wave_sum_dpp(acc[q]);
-      const int64_t nrows = (int64_t)gridDim.x * (kBlock / 64);
-      if ((threadIdx.x & 63) == 0)
-        write_act_partials(partials, wsum, nrows, (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6));
-      publish_act_scales(partials, params, nrows);
-    }
-  } else {
-    // unaligned tensor views / n < 8: element accesses, grid-stride, fp64 per-thread accumulators
-    double dacc[kAcc] = {0, 0, 0, 0};
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-      float r = 0.f;
-      if (NEED_R) r = RSIGN ? sign_half(r_sign[i]) : philox_r(i, seed, offset);
-      float a1[kAcc] = {0.f, 0.f, 0.f, 0.f};
-      gx[i] = down1<DT>(bwd_elem<METHOD>(up1<DT>(x[i]), up1<DT>(g[i]), r, 0.f, k, a1));
-#pragma unroll
-      for (int q = 0; q < kAcc; ++q) dacc[q] += (double)a1[q];
-    }
-    __shared__ double sm[kAcc * (kBlock / 64)];
-    block_sum<kAcc>(dacc, sm);
-    if (threadIdx.x == 0) write_act_partials(partials, dacc, (int64_t)gridDim.x, (int64_t)blockIdx.x);
-    publish_act_scales(partials, params, (int64_t)gridDim.x);
-  }
-}
-
 // =============================================================== ReLU (+ residual add) fused in, 16-bit
 // fq_pt.hip's pt_fwd_relu_kernel / pt_bwd_relu_kernel on 16-bit tensors (mhaq_fq_act_relu_*_x16): the NoisyAct behind a
 // ReLU under torch.autocast.  The target is the BITS of the separate 16-bit launches -- torch's add, relu,
@@ -405,7 +260,7 @@ __global__ MHAQ_X16_BWD_OCC void x16_act_bwd_kernel(
 // gs is rounded TWICE on purpose: unfused, the quantizer writes a 16-bit gq and autograd adds the other consumer's 16-bit
 // gradient to it with a 16-bit add.  R(fp32 gq + g_a) would be closer to the exact sum and a different training run.
 // The parameter sums take the fp32 (a, up(g_y)) of every element, masked or not: geometry, sign tile and partial rows are
-// x16_act_bwd_kernel's on (a, g_y), byte for byte.
+// the plain backward's on (a, g_y), byte for byte -- both kernels are x16_bwd_body below.
 __device__ __forceinline__ float relu_elem(float x) { return (x <= 0.f) ? 0.f : x; }
 
 // keep-masks of a packed pair: threshold_backward / relu zero the halves whose value is <= 0 (a NaN keeps its half)
@@ -512,50 +367,73 @@ __global__ __launch_bounds__(kBlock) void x16_act_relu_fwd_kernel(
   }
 }
 
-// x16_act_bwd_kernel<DT, METHOD, RSIGN = false, ALIGNED, BIG> on (relu(z), g) with a third input stream (g_a) and the
-// ReLU's mask on the elementwise output; everything that reaches the partial rows is that kernel's, line for line
-template <int DT, int METHOD, bool ALIGNED, bool HAS_GA, bool BIG>
-__global__ MHAQ_X16_BWD_OCC void x16_act_relu_bwd_kernel(
-    const uint16_t* __restrict__ z, const uint16_t* __restrict__ g, const uint16_t* __restrict__ ga,
-    uint16_t* __restrict__ gx, int64_t n, const float* __restrict__ params, uint64_t seed, uint64_t offset,
-    const uint64_t* __restrict__ offset_dev, float* __restrict__ partials) {
+// =============================================================== backward, plain and ReLU forms
+// what the two forms feed the element bodies and store: x or relu(z); the rounded result, or that with g_a and the mask
+template <bool RELU>
+__device__ __forceinline__ float act_in(float x) { return RELU ? relu_elem(x) : x; }
+template <int DT, bool RELU, bool HAS_GA>
+__device__ __forceinline__ uint32_t bwd_out2(float q0, float q1, uint32_t cw, float x0, float x1) {
+  return RELU ? relu_out2<DT, HAS_GA>(q0, q1, cw, x0, x1) : down2<DT>(q0, q1);
+}
+template <int DT, bool RELU, bool HAS_GA>
+__device__ __forceinline__ uint16_t bwd_out1(float q, uint16_t c, float x) {
+  return RELU ? relu_out1<DT, HAS_GA>(q, c, x) : down1<DT>(q);
+}
+
+// The backward of both forms.  RELU: x is the ReLU's input z, the element bodies see relu(z) and the store adds g_a
+// (HAS_GA) and masks; everything that reaches the partial rows is the same code either way.  RSIGN: the caller's signs
+// (r_sign, one int8 per element) instead of the in-kernel stream.  Instantiated for the plain kernel with
+// <RELU = false, HAS_GA = false> and for the ReLU kernel with <RSIGN = false>; BIG only with ALIGNED.
+// nblk is gridDim.x, read by the kernel: read in here, the compiler no longer reduces the launch-geometry queries of
+// the epilogues (this one and block_sum_f32's blockDim.x) to one scalar load each, and every wave of the BIG form then
+// waits on a dependent global load, and with it on its own stores, before the block sum (1-3 % of the launch).
+template <int DT, int METHOD, bool RELU, bool RSIGN, bool ALIGNED, bool HAS_GA, bool BIG>
+__device__ __forceinline__ void x16_bwd_body(
+    const uint16_t* __restrict__ x, const uint16_t* __restrict__ g, const uint16_t* __restrict__ ga,
+    uint16_t* __restrict__ gx, int64_t n, const float* __restrict__ params, const int8_t* __restrict__ r_sign,
+    uint64_t seed, uint64_t offset, const uint64_t* __restrict__ offset_dev, float* __restrict__ partials,
+    const int64_t nblk) {
   constexpr bool NEED_R = (METHOD != MHAQ_FQ_LSQ);
   constexpr bool FAST_METHOD = (METHOD == MHAQ_FQ_STE || METHOD == MHAQ_FQ_LSQ);
   constexpr int U = bwd_u(BIG);
-  constexpr int kTileCalls = 16 * U;
+  constexpr int kTileCalls = 16 * U;              // 2048 * U elements per block / 128 per call
   float acc[kAcc] = {0.f, 0.f, 0.f, 0.f};
   const int64_t nvec = n >> 3;
   const int64_t base = (int64_t)blockIdx.x * (kBlock * U) + threadIdx.x;
   const bool full = ((int64_t)blockIdx.x + 1) * (kBlock * U) <= nvec;
   vu4 a[U], b[U], c[U];
+  uint64_t rs[U];
   if (ALIGNED) {
-    // unconditional, clamped loads: all 3 * U in flight before anything waits (nvec >= 1 here)
+    // unconditional loads, all in flight before anything waits; lanes past the end re-read the last vector (fq_pt.hip);
+    // the launcher sends n < 8 to the element kernel, so nvec >= 1 here
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int64_t idx = base + u * kBlock;
       const int64_t idc = (full || idx < nvec) ? idx : nvec - 1;
-      a[u] = ld8<true>(z, idc);
+      a[u] = ld8<true>(x, idc);
       b[u] = ld8<true>(g, idc);
       if (HAS_GA) c[u] = ld8<true>(ga, idc);
       else c[u] = vu4{0u, 0u, 0u, 0u};
+      if (NEED_R && RSIGN) rs[u] = reinterpret_cast<const uint64_t*>(r_sign)[idc];
     }
     __builtin_amdgcn_sched_barrier(0);
   }
   offset = stream_offset(offset, offset_dev);
   const float p_s = params[0], p_zp = params[1], p_lo = params[2], p_hi = params[3];
   __shared__ __align__(16) uint32_t stile[4 * kTileCalls];
-  if (ALIGNED && NEED_R) {
+  if (ALIGNED && NEED_R && !RSIGN) {
     sign_tile_fill(stile, (int64_t)blockIdx.x * kTileCalls, kTileCalls, seed, offset);
     __syncthreads();
   }
   const BwdCtx k = make_bwd_ctx(p_s, p_zp, p_lo, p_hi);
 
   if (ALIGNED) {
+    // this lane's sign byte: vector u*256 + t of the block = bits [8*(u*256 + t), +8) of the tile, inverted once
     uint32_t nb[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       nb[u] = 0;
-      if (NEED_R) nb[u] = ~(stile[(u * kBlock + (int)threadIdx.x) >> 2] >> (((int)threadIdx.x & 3) * 8));
+      if (NEED_R && !RSIGN) nb[u] = ~(stile[(u * kBlock + (int)threadIdx.x) >> 2] >> (((int)threadIdx.x & 3) * 8));
     }
     const bool fast = FAST_METHOD && k.fast_div && (k.lo < k.hi) && (k.s > 0.f);      // wave-uniform
     if (FAST_METHOD && fast) {
@@ -567,17 +445,22 @@ __global__ MHAQ_X16_BWD_OCC void x16_act_relu_bwd_kernel(
           vu4 o;
 #pragma unroll
           for (int w = 0; w < 4; ++w) {
-            float z0, z1, g0, g1;
-            up2<DT>(a[u][w], z0, z1);
+            float x0, x1, g0, g1;
+            up2<DT>(a[u][w], x0, x1);
             up2<DT>(b[u][w], g0, g1);
             float rc0 = 0.f, rc1 = 0.f;
             if (NEED_R) {
-              rc0 = signed_half_scale(nb[u], 2 * w, hcs);
-              rc1 = signed_half_scale(nb[u], 2 * w + 1, hcs);
+              if (RSIGN) {
+                rc0 = ((int8_t)((rs[u] >> (16 * w)) & 0xff) > 0) ? hcs : -hcs;
+                rc1 = ((int8_t)((rs[u] >> (16 * w + 8)) & 0xff) > 0) ? hcs : -hcs;
+              } else {
+                rc0 = signed_half_scale(nb[u], 2 * w, hcs);
+                rc1 = signed_half_scale(nb[u], 2 * w + 1, hcs);
+              }
             }
-            const float y0 = bwd_elem_fast<METHOD>(relu_elem(z0), g0, rc0, k, acc);
-            const float y1 = bwd_elem_fast<METHOD>(relu_elem(z1), g1, rc1, k, acc);
-            o[w] = relu_out2<DT, HAS_GA>(y0, y1, c[u][w], z0, z1);
+            const float y0 = bwd_elem_fast<METHOD>(act_in<RELU>(x0), g0, rc0, k, acc);
+            const float y1 = bwd_elem_fast<METHOD>(act_in<RELU>(x1), g1, rc1, k, acc);
+            o[w] = bwd_out2<DT, RELU, HAS_GA>(y0, y1, c[u][w], x0, x1);
           }
           st8<true>(gx, idx, o);
         }
@@ -590,18 +473,23 @@ __global__ MHAQ_X16_BWD_OCC void x16_act_relu_bwd_kernel(
           vu4 o;
 #pragma unroll
           for (int w = 0; w < 4; ++w) {
-            float z0, z1, g0, g1;
-            up2<DT>(a[u][w], z0, z1);
+            float x0, x1, g0, g1;
+            up2<DT>(a[u][w], x0, x1);
             up2<DT>(b[u][w], g0, g1);
             float r0 = 0.f, r1 = 0.f;
             if (NEED_R) {
-              const uint32_t bits = ~nb[u];
-              r0 = ((bits >> (2 * w)) & 1u) ? 0.5f : -0.5f;
-              r1 = ((bits >> (2 * w + 1)) & 1u) ? 0.5f : -0.5f;
+              if (RSIGN) {
+                r0 = sign_half((int8_t)((rs[u] >> (16 * w)) & 0xff));
+                r1 = sign_half((int8_t)((rs[u] >> (16 * w + 8)) & 0xff));
+              } else {
+                const uint32_t bits = ~nb[u];
+                r0 = ((bits >> (2 * w)) & 1u) ? 0.5f : -0.5f;
+                r1 = ((bits >> (2 * w + 1)) & 1u) ? 0.5f : -0.5f;
+              }
             }
-            const float y0 = bwd_elem<METHOD>(relu_elem(z0), g0, r0, 0.f, k, acc);
-            const float y1 = bwd_elem<METHOD>(relu_elem(z1), g1, r1, 0.f, k, acc);
-            o[w] = relu_out2<DT, HAS_GA>(y0, y1, c[u][w], z0, z1);
+            const float y0 = bwd_elem<METHOD>(act_in<RELU>(x0), g0, r0, 0.f, k, acc);
+            const float y1 = bwd_elem<METHOD>(act_in<RELU>(x1), g1, r1, 0.f, k, acc);
+            o[w] = bwd_out2<DT, RELU, HAS_GA>(y0, y1, c[u][w], x0, x1);
           }
           st8<true>(gx, idx, o);
         }
@@ -609,43 +497,71 @@ __global__ MHAQ_X16_BWD_OCC void x16_act_relu_bwd_kernel(
     }
     const int64_t t = (nvec << 3) + threadIdx.x;
     if (blockIdx.x == 0 && t < n) {   // n % 8 tail elements
-      const float zz = up1<DT>(z[t]);
-      const float r = NEED_R ? philox_r(t, seed, offset) : 0.f;
-      const float v = bwd_elem<METHOD>(relu_elem(zz), up1<DT>(g[t]), r, 0.f, k, acc);
-      gx[t] = relu_out1<DT, HAS_GA>(v, HAS_GA ? ga[t] : (uint16_t)0, zz);
+      float r = 0.f;
+      if (NEED_R) r = RSIGN ? sign_half(r_sign[t]) : philox_r(t, seed, offset);
+      const float xx = up1<DT>(x[t]);
+      const float v = bwd_elem<METHOD>(act_in<RELU>(xx), up1<DT>(g[t]), r, 0.f, k, acc);
+      gx[t] = bwd_out1<DT, RELU, HAS_GA>(v, HAS_GA ? ga[t] : (uint16_t)0, xx);
     }
+    // partial rows in the ACT layout: one per block (fp64 totals) in the BIG form, one per wave below it
     if (BIG) {
       __shared__ float smf[kAcc * (kBlock / 64)];
       double tot[kAcc];
       block_sum_f32<kAcc>(acc, tot, smf);
-      if (threadIdx.x == 0) write_act_partials(partials, tot, (int64_t)gridDim.x, (int64_t)blockIdx.x);
-      publish_act_scales(partials, params, (int64_t)gridDim.x);
+      if (threadIdx.x == 0) write_act_partials(partials, tot, nblk, (int64_t)blockIdx.x);
+      publish_act_scales(partials, params, nblk);
     } else {
       float wsum[kAcc];
 #pragma unroll
       for (int q = 0; q < kAcc; ++q) wsum[q] = wave_sum_dpp(acc[q]);
-      const int64_t nrows = (int64_t)gridDim.x * (kBlock / 64);
+      const int64_t nrows = nblk * (kBlock / 64);
       if ((threadIdx.x & 63) == 0)
         write_act_partials(partials, wsum, nrows, (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6));
       publish_act_scales(partials, params, nrows);
     }
   } else {
-    // unaligned tensor views / n < 8: element accesses, grid-stride, fp64 per-thread accumulators
+    // unaligned tensor views / n < 8: element accesses, grid-stride, fp64 per-thread accumulators, one row per block
     double dacc[kAcc] = {0, 0, 0, 0};
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-      const float zz = up1<DT>(z[i]);
-      const float r = NEED_R ? philox_r(i, seed, offset) : 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += nblk * kBlock) {
+      float r = 0.f;
+      if (NEED_R) r = RSIGN ? sign_half(r_sign[i]) : philox_r(i, seed, offset);
+      const float xx = up1<DT>(x[i]);
       float a1[kAcc] = {0.f, 0.f, 0.f, 0.f};
-      const float v = bwd_elem<METHOD>(relu_elem(zz), up1<DT>(g[i]), r, 0.f, k, a1);
-      gx[i] = relu_out1<DT, HAS_GA>(v, HAS_GA ? ga[i] : (uint16_t)0, zz);
+      const float v = bwd_elem<METHOD>(act_in<RELU>(xx), up1<DT>(g[i]), r, 0.f, k, a1);
+      gx[i] = bwd_out1<DT, RELU, HAS_GA>(v, HAS_GA ? ga[i] : (uint16_t)0, xx);
 #pragma unroll
       for (int q = 0; q < kAcc; ++q) dacc[q] += (double)a1[q];
     }
     __shared__ double sm[kAcc * (kBlock / 64)];
     block_sum<kAcc>(dacc, sm);
-    if (threadIdx.x == 0) write_act_partials(partials, dacc, (int64_t)gridDim.x, (int64_t)blockIdx.x);
-    publish_act_scales(partials, params, (int64_t)gridDim.x);
+    if (threadIdx.x == 0) write_act_partials(partials, dacc, nblk, (int64_t)blockIdx.x);
+    publish_act_scales(partials, params, nblk);
   }
+}
+
+// The two kernels are that body behind their own names and argument lists (profiles name them; with kernarg preload the
+// argument layout is part of the code).  Occupancy by size as fq_pt.hip pt_bwd_kernel: at least 8 waves per SIMD on the
+// latency-limited small tensors, at most 6 on the bandwidth-limited big ones (the element kernel of unaligned views
+// carries no lower bound).
+#define MHAQ_X16_BWD_OCC \
+  __attribute__((amdgpu_waves_per_eu(((BIG || !ALIGNED) ? 1 : 8), (BIG ? 6 : 8)))) __launch_bounds__(kBlock)
+
+template <int DT, int METHOD, bool RSIGN, bool ALIGNED, bool BIG>
+__global__ MHAQ_X16_BWD_OCC void x16_act_bwd_kernel(
+    const uint16_t* __restrict__ x, const uint16_t* __restrict__ g, uint16_t* __restrict__ gx, int64_t n,
+    const float* __restrict__ params, const int8_t* __restrict__ r_sign, uint64_t seed, uint64_t offset,
+    const uint64_t* __restrict__ offset_dev, float* __restrict__ partials) {
+  x16_bwd_body<DT, METHOD, false, RSIGN, ALIGNED, false, BIG>(x, g, nullptr, gx, n, params, r_sign, seed, offset,
+                                                              offset_dev, partials, (int64_t)gridDim.x);
+}
+
+template <int DT, int METHOD, bool ALIGNED, bool HAS_GA, bool BIG>
+__global__ MHAQ_X16_BWD_OCC void x16_act_relu_bwd_kernel(
+    const uint16_t* __restrict__ z, const uint16_t* __restrict__ g, const uint16_t* __restrict__ ga,
+    uint16_t* __restrict__ gx, int64_t n, const float* __restrict__ params, uint64_t seed, uint64_t offset,
+    const uint64_t* __restrict__ offset_dev, float* __restrict__ partials) {
+  x16_bwd_body<DT, METHOD, true, false, ALIGNED, HAS_GA, BIG>(z, g, ga, gx, n, params, nullptr, seed, offset,
+                                                              offset_dev, partials, (int64_t)gridDim.x);
 }
 
 // fq_pt.hip act_finalize_kernel: column sums -> {dL/dlog_act_s, dL/dlog_act_q, dL/dact_b}, same partition and order
@@ -690,100 +606,107 @@ inline int64_t simple_grid(int64_t n) {            // fq_pt.hip simple_grid
   return b;
 }
 
-template <int DT>
-void launch_fwd(const uint16_t* x, uint16_t* y, int64_t n, const float* ps, const float* pq, const float* pb,
-                float* params_out, float* parts, int grid, bool al, bool stats, bool ntld, hipStream_t st) {
-#define MHAQ_X16_FWD(ST, AL, NL)                                                                                   \
-  MHAQ_LAUNCH((x16_act_fwd_kernel<DT, ST, AL, NL, (ST ? kFwdStatsU : kFwdU)>), dim3(grid), dim3(kBlock), 0, st, x, y, \
-              n, ps, pq, pb, parts, params_out)
-  if (stats) {
-    if (!al) MHAQ_X16_FWD(true, false, false);
-    else if (ntld) MHAQ_X16_FWD(true, true, true);
-    else MHAQ_X16_FWD(true, true, false);
-  } else {
-    if (!al) MHAQ_X16_FWD(false, false, false);
-    else if (ntld) MHAQ_X16_FWD(false, true, true);
-    else MHAQ_X16_FWD(false, true, false);
-  }
-#undef MHAQ_X16_FWD
+// A runtime value as a template argument: f receives it as a std::integral_constant.  The entry points have checked
+// dtype and method before they get here.
+template <class F>
+void with_dtype(int dtype, F f) {
+  if (dtype == MHAQ_FQ_DT_BF16) f(std::integral_constant<int, MHAQ_FQ_DT_BF16>{});
+  else f(std::integral_constant<int, MHAQ_FQ_DT_F16>{});
 }
-
-template <int DT, int METHOD>
-void launch_bwd(const uint16_t* x, const uint16_t* g, uint16_t* gx, int64_t n, const float* params,
-                const int8_t* r_sign, uint64_t seed, uint64_t offset, const uint64_t* offset_dev, float* parts,
-                int grid, bool al, bool big, hipStream_t st) {
-#define MHAQ_X16_BWD(RS, AL, BG)                                                                                   \
-  MHAQ_LAUNCH((x16_act_bwd_kernel<DT, METHOD, RS, AL, BG>), dim3(grid), dim3(kBlock), 0, st, x, g, gx, n, params, \
-              r_sign, seed, offset, offset_dev, parts)
-  if (r_sign) {
-    if (!al) MHAQ_X16_BWD(true, false, false);
-    else if (big) MHAQ_X16_BWD(true, true, true);
-    else MHAQ_X16_BWD(true, true, false);
-  } else {
-    if (!al) MHAQ_X16_BWD(false, false, false);
-    else if (big) MHAQ_X16_BWD(false, true, true);
-    else MHAQ_X16_BWD(false, true, false);
-  }
-#undef MHAQ_X16_BWD
-}
-
-template <int DT>
-void launch_bwd_method(int method, const uint16_t* x, const uint16_t* g, uint16_t* gx, int64_t n, const float* params,
-                       const int8_t* r_sign, uint64_t seed, uint64_t offset, const uint64_t* offset_dev, float* parts,
-                       int grid, bool al, bool big, hipStream_t st) {
+template <class F>
+void with_method(int method, F f) {
   switch (method) {
-    case MHAQ_FQ_STE: launch_bwd<DT, MHAQ_FQ_STE>(x, g, gx, n, params, r_sign, seed, offset, offset_dev, parts, grid, al, big, st); break;
-    case MHAQ_FQ_EWGS: launch_bwd<DT, MHAQ_FQ_EWGS>(x, g, gx, n, params, r_sign, seed, offset, offset_dev, parts, grid, al, big, st); break;
-    default: launch_bwd<DT, MHAQ_FQ_LSQ>(x, g, gx, n, params, r_sign, seed, offset, offset_dev, parts, grid, al, big, st); break;
+    case MHAQ_FQ_STE: f(std::integral_constant<int, MHAQ_FQ_STE>{}); break;
+    case MHAQ_FQ_EWGS: f(std::integral_constant<int, MHAQ_FQ_EWGS>{}); break;
+    default: f(std::integral_constant<int, MHAQ_FQ_LSQ>{}); break;
   }
 }
-
-template <int DT>
-void launch_relu_fwd(const uint16_t* z, const uint16_t* addend, uint16_t* y, uint16_t* a_out, int64_t n,
-                     const float* ps, const float* pq, const float* pb, float* params_out, int grid, bool al, bool ntld,
-                     hipStream_t st) {
-#define MHAQ_X16_RFWD_(HA, WA, AL, NL)                                                                               \
-  MHAQ_LAUNCH((x16_act_relu_fwd_kernel<DT, HA, WA, AL, NL>), dim3(grid), dim3(kBlock), 0, st, z, addend, y, a_out, n, \
-              ps, pq, pb, params_out)
-#define MHAQ_X16_RFWD(HA, WA)                                \
-  do {                                                       \
-    if (!al) MHAQ_X16_RFWD_(HA, WA, false, false);           \
-    else if (ntld) MHAQ_X16_RFWD_(HA, WA, true, true);       \
-    else MHAQ_X16_RFWD_(HA, WA, true, false);                \
-  } while (0)
-  if (addend) { if (a_out) MHAQ_X16_RFWD(true, true); else MHAQ_X16_RFWD(true, false); }
-  else        { if (a_out) MHAQ_X16_RFWD(false, true); else MHAQ_X16_RFWD(false, false); }
-#undef MHAQ_X16_RFWD
-#undef MHAQ_X16_RFWD_
+// f(ALIGNED, SECOND): the element kernel has one form, the aligned kernel two by size (NTLD forward, BIG backward)
+template <class F>
+void with_form(bool aligned, bool second, F f) {
+  if (!aligned) f(std::false_type{}, std::false_type{});
+  else if (second) f(std::true_type{}, std::true_type{});
+  else f(std::true_type{}, std::false_type{});
 }
 
-template <int DT, int METHOD>
-void launch_relu_bwd(const uint16_t* z, const uint16_t* g, const uint16_t* ga, uint16_t* gx, int64_t n,
-                     const float* params, uint64_t seed, uint64_t offset, const uint64_t* offset_dev, float* parts,
-                     int grid, bool al, bool big, hipStream_t st) {
-#define MHAQ_X16_RBWD_(AL, GA, BG)                                                                                 \
-  MHAQ_LAUNCH((x16_act_relu_bwd_kernel<DT, METHOD, AL, GA, BG>), dim3(grid), dim3(kBlock), 0, st, z, g, ga, gx, n, \
-              params, seed, offset, offset_dev, parts)
-#define MHAQ_X16_RBWD(GA)                                    \
-  do {                                                       \
-    if (!al) MHAQ_X16_RBWD_(false, GA, false);               \
-    else if (big) MHAQ_X16_RBWD_(true, GA, true);            \
-    else MHAQ_X16_RBWD_(true, GA, false);                    \
-  } while (0)
-  if (ga) MHAQ_X16_RBWD(true); else MHAQ_X16_RBWD(false);
-#undef MHAQ_X16_RBWD
-#undef MHAQ_X16_RBWD_
+// One backward call of either form: the plain one has no g_a, the ReLU one no caller-supplied signs.
+struct BwdCall {
+  const void *x, *g, *ga;
+  void* gx;
+  int64_t n;
+  int dtype;
+  const float* params;
+  int method;
+  bool relu;
+  const int8_t* r_sign;
+  uint64_t seed, offset;
+  const uint64_t* offset_dev;
+  void* workspace;
+  size_t workspace_bytes;
+  void* stream;
+};
+
+// (dtype, method, relu, r_sign, g_a, aligned, big) -> the instantiation.  Nothing else instantiates a backward kernel,
+// so there is no <RELU, RSIGN = true> and no <ALIGNED = false, BIG = true> in the library.
+inline void launch_bwd(const BwdCall& c, int grid, bool al, bool big) {
+  const uint16_t *x = (const uint16_t*)c.x, *g = (const uint16_t*)c.g, *ga = (const uint16_t*)c.ga;
+  uint16_t* gx = (uint16_t*)c.gx;
+  float* parts = (float*)c.workspace;
+  hipStream_t st = (hipStream_t)c.stream;
+  with_dtype(c.dtype, [&](auto dt) {
+    with_method(c.method, [&](auto m) {
+      with_form(al, big, [&](auto a, auto bg) {
+        constexpr int DT = decltype(dt)::value, M = decltype(m)::value;
+        constexpr bool AL = decltype(a)::value, BG = decltype(bg)::value;
+        if (c.relu)
+          MHAQ_LAUNCH((ga ? x16_act_relu_bwd_kernel<DT, M, AL, true, BG>
+                          : x16_act_relu_bwd_kernel<DT, M, AL, false, BG>),
+                      dim3(grid), dim3(kBlock), 0, st, x, g, ga, gx, c.n, c.params, c.seed, c.offset, c.offset_dev,
+                      parts);
+        else
+          MHAQ_LAUNCH((c.r_sign ? x16_act_bwd_kernel<DT, M, true, AL, BG>
+                                : x16_act_bwd_kernel<DT, M, false, AL, BG>),
+                      dim3(grid), dim3(kBlock), 0, st, x, g, gx, c.n, c.params, c.r_sign, c.seed, c.offset,
+                      c.offset_dev, parts);
+      });
+    });
+  });
 }
 
-template <int DT>
-void launch_relu_bwd_method(int method, const uint16_t* z, const uint16_t* g, const uint16_t* ga, uint16_t* gx,
-                            int64_t n, const float* params, uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
-                            float* parts, int grid, bool al, bool big, hipStream_t st) {
-  switch (method) {
-    case MHAQ_FQ_STE: launch_relu_bwd<DT, MHAQ_FQ_STE>(z, g, ga, gx, n, params, seed, offset, offset_dev, parts, grid, al, big, st); break;
-    case MHAQ_FQ_EWGS: launch_relu_bwd<DT, MHAQ_FQ_EWGS>(z, g, ga, gx, n, params, seed, offset, offset_dev, parts, grid, al, big, st); break;
-    default: launch_relu_bwd<DT, MHAQ_FQ_LSQ>(z, g, ga, gx, n, params, seed, offset, offset_dev, parts, grid, al, big, st); break;
-  }
+// mhaq_fq_act_bwd_partials_x16 / mhaq_fq_act_relu_bwd_partials_x16: checks (in the order include/mhaq_fq.h gives their
+// codes), geometry, launch.
+inline int bwd_partials(const BwdCall& c, int32_t* nparts_out) {
+  const int64_t n = c.n;
+  if (n < 0 || !c.params || (n > 0 && (!c.x || !c.g || !c.gx))) return MHAQ_FQ_EINVAL;
+  if (!known_dtype(c.dtype)) return MHAQ_FQ_EINVAL;
+  if (c.method != MHAQ_FQ_STE && c.method != MHAQ_FQ_LSQ && c.method != MHAQ_FQ_EWGS)
+    return (c.method == MHAQ_FQ_AEWGS) ? MHAQ_FQ_EUNSUPPORTED : MHAQ_FQ_EINVAL;
+  if (!aligned2(c.x) || !aligned2(c.g) || !aligned2(c.ga) || !aligned2(c.gx)) return MHAQ_FQ_EALIGN;
+  if (!c.workspace || c.workspace_bytes < mhaq_fq_act_bwd_workspace_bytes(n)) return MHAQ_FQ_EWORKSPACE;
+  const bool al = n >= 8 && aligned16(c.x) && aligned16(c.g) && aligned16(c.gx) && (!c.ga || aligned16(c.ga)) &&
+                  (!c.r_sign || aligned8(c.r_sign));
+  const bool big = al && n >= kBwdBigElems;
+  const int64_t grid64 = al ? blocks8(n, bwd_u(big)) : simple_grid(n);
+  if (grid64 > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
+  // partial rows: one per wave of the aligned kernel below kBwdBigElems, one per block from there up and in the element
+  // kernel -- at most the fp32 launch's count, so the fp32 workspace query serves (checked, not assumed)
+  const int64_t rows64 = (al && !big) ? grid64 * (kBlock / 64) : grid64;
+  if (rows64 > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
+  if ((size_t)(3 * rows64 + 2) * sizeof(float) > c.workspace_bytes) return MHAQ_FQ_EWORKSPACE;
+  if (nparts_out) *nparts_out = (int32_t)rows64;
+  launch_bwd(c, (int)grid64, al, big);
+  return launch_status();
+}
+
+// mhaq_fq_act_bwd_x16 / mhaq_fq_act_relu_bwd_x16: the partial rows, then their column sums
+inline int bwd_with_finalize(const BwdCall& c, float* grads) {
+  if (!grads) return MHAQ_FQ_EINVAL;
+  int32_t nparts = 0;
+  const int rc = bwd_partials(c, &nparts);
+  if (rc) return rc;
+  MHAQ_LAUNCH(x16_act_finalize_kernel, dim3(3), dim3(kFinalThreads), 0, (hipStream_t)c.stream,
+              (const float*)c.workspace, (int)nparts, c.params, grads);
+  return launch_status();
 }
 
 }  // namespace io16
@@ -809,13 +732,17 @@ int mhaq_fq_act_fwd_x16(const void* x, void* y, int64_t n, int dtype, const floa
   const int grid = (int)grid64;
   hipStream_t st = (hipStream_t)stream;
   float* parts = (float*)workspace;
-  const bool ntld = n > io16::kFwdPlainLoadElems;
   const uint16_t* xs = (const uint16_t*)x;
   uint16_t* ys = (uint16_t*)y;
-  if (dtype == MHAQ_FQ_DT_BF16)
-    io16::launch_fwd<MHAQ_FQ_DT_BF16>(xs, ys, n, log_s, log_q, b, params_out, parts, grid, al, stats, ntld, st);
-  else
-    io16::launch_fwd<MHAQ_FQ_DT_F16>(xs, ys, n, log_s, log_q, b, params_out, parts, grid, al, stats, ntld, st);
+  io16::with_dtype(dtype, [&](auto dt) {
+    io16::with_form(al, n > io16::kFwdPlainLoadElems, [&](auto a, auto nt) {
+      constexpr int DT = decltype(dt)::value;
+      constexpr bool AL = decltype(a)::value, NT = decltype(nt)::value;
+      MHAQ_LAUNCH((stats ? io16::x16_act_fwd_kernel<DT, true, AL, NT, io16::kFwdStatsU>
+                         : io16::x16_act_fwd_kernel<DT, false, AL, NT, io16::kFwdU>),
+                  dim3(grid), dim3(kBlock), 0, st, xs, ys, n, log_s, log_q, b, parts, params_out);
+    });
+  });
   int rc = launch_status();
   if (rc) return rc;
   if (stats) {
@@ -829,49 +756,15 @@ int mhaq_fq_act_bwd_partials_x16(const void* x, const void* g, void* gx, int64_t
                                  int method, const int8_t* r_sign, uint64_t seed, uint64_t offset,
                                  const uint64_t* offset_dev, void* workspace, size_t workspace_bytes,
                                  int32_t* nparts_out, void* stream) {
-  if (n < 0 || !params || (n > 0 && (!x || !g || !gx))) return MHAQ_FQ_EINVAL;
-  if (!io16::known_dtype(dtype)) return MHAQ_FQ_EINVAL;
-  if (method != MHAQ_FQ_STE && method != MHAQ_FQ_LSQ && method != MHAQ_FQ_EWGS)
-    return (method == MHAQ_FQ_AEWGS) ? MHAQ_FQ_EUNSUPPORTED : MHAQ_FQ_EINVAL;
-  if (!io16::aligned2(x) || !io16::aligned2(g) || !io16::aligned2(gx)) return MHAQ_FQ_EALIGN;
-  if (!workspace || workspace_bytes < mhaq_fq_act_bwd_workspace_bytes(n)) return MHAQ_FQ_EWORKSPACE;
-  const bool al = n >= 8 && io16::aligned16(x) && io16::aligned16(g) && io16::aligned16(gx) &&
-                  (!r_sign || io16::aligned8(r_sign));
-  const bool big = al && n >= io16::kBwdBigElems;
-  const int64_t grid64 = al ? io16::blocks8(n, io16::bwd_u(big)) : io16::simple_grid(n);
-  if (grid64 > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
-  // partial rows: one per wave of the aligned kernel below kBwdBigElems, one per block from there up and in the element
-  // kernel -- at most the fp32 launch's count, so the fp32 workspace query serves (checked, not assumed)
-  const int64_t rows64 = (al && !big) ? grid64 * (kBlock / 64) : grid64;
-  if (rows64 > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
-  if ((size_t)(3 * rows64 + 2) * sizeof(float) > workspace_bytes) return MHAQ_FQ_EWORKSPACE;
-  if (nparts_out) *nparts_out = (int32_t)rows64;
-  const int grid = (int)grid64;
-  hipStream_t st = (hipStream_t)stream;
-  float* parts = (float*)workspace;
-  const uint16_t* xs = (const uint16_t*)x;
-  const uint16_t* gs = (const uint16_t*)g;
-  uint16_t* gxs = (uint16_t*)gx;
-  if (dtype == MHAQ_FQ_DT_BF16)
-    io16::launch_bwd_method<MHAQ_FQ_DT_BF16>(method, xs, gs, gxs, n, params, r_sign, seed, offset, offset_dev, parts,
-                                             grid, al, big, st);
-  else
-    io16::launch_bwd_method<MHAQ_FQ_DT_F16>(method, xs, gs, gxs, n, params, r_sign, seed, offset, offset_dev, parts,
-                                            grid, al, big, st);
-  return launch_status();
+  return io16::bwd_partials({x, g, nullptr, gx, n, dtype, params, method, false, r_sign, seed, offset, offset_dev,
+                             workspace, workspace_bytes, stream}, nparts_out);
 }
 
 int mhaq_fq_act_bwd_x16(const void* x, const void* g, void* gx, int64_t n, int dtype, const float* params, int method,
                         const int8_t* r_sign, uint64_t seed, uint64_t offset, const uint64_t* offset_dev, float* grads,
                         void* workspace, size_t workspace_bytes, void* stream) {
-  if (!grads) return MHAQ_FQ_EINVAL;
-  int32_t nparts = 0;
-  int rc = mhaq_fq_act_bwd_partials_x16(x, g, gx, n, dtype, params, method, r_sign, seed, offset, offset_dev,
-                                        workspace, workspace_bytes, &nparts, stream);
-  if (rc) return rc;
-  MHAQ_LAUNCH(io16::x16_act_finalize_kernel, dim3(3), dim3(io16::kFinalThreads), 0, (hipStream_t)stream,
-              (const float*)workspace, (int)nparts, params, grads);
-  return launch_status();
+  return io16::bwd_with_finalize({x, g, nullptr, gx, n, dtype, params, method, false, r_sign, seed, offset, offset_dev,
+                                  workspace, workspace_bytes, stream}, grads);
 }
 
 // ---- ReLU (+ residual add) fused into the 16-bit NoisyAct launches (x16_act_relu_fwd_kernel / x16_act_relu_bwd_kernel)
@@ -887,13 +780,19 @@ int mhaq_fq_act_relu_fwd_x16(const void* z, const void* addend, void* y, void* a
   if (grid64 > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
   const int grid = (int)grid64;
   hipStream_t st = (hipStream_t)stream;
-  const bool ntld = n > io16::kFwdPlainLoadElems;
   const uint16_t *zs = (const uint16_t*)z, *ds = (const uint16_t*)addend;
   uint16_t *ys = (uint16_t*)y, *as = (uint16_t*)a_out;
-  if (dtype == MHAQ_FQ_DT_BF16)
-    io16::launch_relu_fwd<MHAQ_FQ_DT_BF16>(zs, ds, ys, as, n, log_s, log_q, b, params_out, grid, al, ntld, st);
-  else
-    io16::launch_relu_fwd<MHAQ_FQ_DT_F16>(zs, ds, ys, as, n, log_s, log_q, b, params_out, grid, al, ntld, st);
+  io16::with_dtype(dtype, [&](auto dt) {
+    io16::with_form(al, n > io16::kFwdPlainLoadElems, [&](auto a, auto nt) {
+      constexpr int DT = decltype(dt)::value;
+      constexpr bool AL = decltype(a)::value, NT = decltype(nt)::value;
+      MHAQ_LAUNCH((ds ? (as ? io16::x16_act_relu_fwd_kernel<DT, true, true, AL, NT>
+                            : io16::x16_act_relu_fwd_kernel<DT, true, false, AL, NT>)
+                      : (as ? io16::x16_act_relu_fwd_kernel<DT, false, true, AL, NT>
+                            : io16::x16_act_relu_fwd_kernel<DT, false, false, AL, NT>)),
+                  dim3(grid), dim3(kBlock), 0, st, zs, ds, ys, as, n, log_s, log_q, b, params_out);
+    });
+  });
   return launch_status();
 }
 
@@ -901,48 +800,17 @@ int mhaq_fq_act_relu_bwd_partials_x16(const void* z, const void* g_y, const void
                                       const float* params, int method, uint64_t seed, uint64_t offset,
                                       const uint64_t* offset_dev, void* workspace, size_t workspace_bytes,
                                       int32_t* nparts_out, void* stream) {
-  if (n < 0 || !params || (n > 0 && (!z || !g_y || !gx))) return MHAQ_FQ_EINVAL;
-  if (!io16::known_dtype(dtype)) return MHAQ_FQ_EINVAL;
-  if (method != MHAQ_FQ_STE && method != MHAQ_FQ_LSQ && method != MHAQ_FQ_EWGS)
-    return (method == MHAQ_FQ_AEWGS) ? MHAQ_FQ_EUNSUPPORTED : MHAQ_FQ_EINVAL;
-  if (!io16::aligned2(z) || !io16::aligned2(g_y) || !io16::aligned2(g_a) || !io16::aligned2(gx)) return MHAQ_FQ_EALIGN;
-  if (!workspace || workspace_bytes < mhaq_fq_act_bwd_workspace_bytes(n)) return MHAQ_FQ_EWORKSPACE;
-  const bool al = n >= 8 && io16::aligned16(z) && io16::aligned16(g_y) && io16::aligned16(gx) &&
-                  (!g_a || io16::aligned16(g_a));
-  const bool big = al && n >= io16::kBwdBigElems;
-  const int64_t grid64 = al ? io16::blocks8(n, io16::bwd_u(big)) : io16::simple_grid(n);
-  if (grid64 > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
-  // partial rows: those of mhaq_fq_act_bwd_partials_x16 over the same n and alignment
-  const int64_t rows64 = (al && !big) ? grid64 * (kBlock / 64) : grid64;
-  if (rows64 > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
-  if ((size_t)(3 * rows64 + 2) * sizeof(float) > workspace_bytes) return MHAQ_FQ_EWORKSPACE;
-  if (nparts_out) *nparts_out = (int32_t)rows64;
-  const int grid = (int)grid64;
-  hipStream_t st = (hipStream_t)stream;
-  float* parts = (float*)workspace;
-  const uint16_t *zs = (const uint16_t*)z, *gs = (const uint16_t*)g_y, *gas = (const uint16_t*)g_a;
-  uint16_t* gxs = (uint16_t*)gx;
-  if (dtype == MHAQ_FQ_DT_BF16)
-    io16::launch_relu_bwd_method<MHAQ_FQ_DT_BF16>(method, zs, gs, gas, gxs, n, params, seed, offset, offset_dev, parts,
-                                                  grid, al, big, st);
-  else
-    io16::launch_relu_bwd_method<MHAQ_FQ_DT_F16>(method, zs, gs, gas, gxs, n, params, seed, offset, offset_dev, parts,
-                                                 grid, al, big, st);
-  return launch_status();
+  return io16::bwd_partials({z, g_y, g_a, gx, n, dtype, params, method, true, nullptr, seed, offset, offset_dev,
+                             workspace, workspace_bytes, stream}, nparts_out);
 }
 
 int mhaq_fq_act_relu_bwd_x16(const void* z, const void* g_y, const void* g_a, void* gx, int64_t n, int dtype,
                              const float* params, int method, uint64_t seed, uint64_t offset,
                              const uint64_t* offset_dev, float* grads, void* workspace, size_t workspace_bytes,
                              void* stream) {
-  if (!grads) return MHAQ_FQ_EINVAL;
-  int32_t nparts = 0;
-  int rc = mhaq_fq_act_relu_bwd_partials_x16(z, g_y, g_a, gx, n, dtype, params, method, seed, offset, offset_dev,
-                                             workspace, workspace_bytes, &nparts, stream);
-  if (rc) return rc;
-  MHAQ_LAUNCH(io16::x16_act_finalize_kernel, dim3(3), dim3(io16::kFinalThreads), 0, (hipStream_t)stream,
-              (const float*)workspace, (int)nparts, params, grads);
-  return launch_status();
+  return io16::bwd_with_finalize({z, g_y, g_a, gx, n, dtype, params, method, true, nullptr, seed, offset, offset_dev,
+                                  workspace, workspace_bytes, stream}, grads);
 }
 
 }  // extern "C"
+

@@ -135,6 +135,32 @@ def test_in_kernel_signs_equal_the_fp32_kernel_on_the_upcast_tensors(ops, dtype,
     _check_params(pg, (ls2.grad, lq2.grad, bb2.grad), tuple(2 * t for t in yard), signed)
 
 
+_BIG = (20 << 20) + 4099
+# (n, storage offset of the gradient view): the smallest sizes at which the caller's signs are read on another path
+_RSIGN_CASES = [pytest.param(dt, n, off, id=f"{name}-{n}+{off}")
+                for n, off, dts in [(7, 0, DTYPES), (2053, 0, DTYPES), (5000, 1, DTYPES), (_BIG, 0, DTYPES[:1])]
+                for dt, name in zip(DTYPES, ["bf16", "fp16"]) if dt in dts]
+
+
+@pytest.mark.parametrize("method", ["STE", "EWGS"])           # LSQ reads no signs
+@pytest.mark.parametrize("dtype,n,offset", _RSIGN_CASES)
+def test_caller_supplied_signs_on_every_backward_path(ops, dtype, n, offset, method):
+    """The explicit sign tensor (RSIGN) away from the aligned, tail-free small form of the test above: n = 7 takes the
+    element kernel (n < 8); 2053 = one block of 256 vectors and 5 tail elements that read r_sign[t]; a gradient that is
+    a view one element into its buffer is 2-byte aligned only and sends the backward to the element kernel, r_sign[i]
+    per element; above 20 Mi elements the BIG form reads two 8-byte sign words per lane."""
+    xb, gb, rb = _inputs((n + offset,), dtype, True, n % 1000, scale=2.0)
+    x16, g16, r = xb[offset:], gb[offset:], rb[offset:]
+    assert (g16.data_ptr() % 16 != 0) == bool(offset)
+    logs, b, signed = PARAM_SETS[0]
+    y, gx, pg, (ls, lq, bb) = _fused16(ops, x16, g16, logs, b, signed, method, r)
+    y_r, gx_r, pg_r = _oracle(x16, g16, logs, b, signed, method, r)
+    assert y.dtype == dtype and gx.dtype == dtype
+    assert same_bits(y, y_r.to(dtype))
+    assert same_values(gx, gx_r)
+    _check_params(pg, pg_r, yardsticks(x16, g16, r, ls, lq, bb, method), signed)
+
+
 def _vs_fp32_kernel(ops, x16, g16, logs=(-3.0, 1.0), b=-1.0, method="STE", seed=99):
     """16-bit path against the fp32 kernels on the upcast tensors, in-kernel signs at the same seed."""
     ops.manual_seed(seed)
