@@ -360,6 +360,40 @@ int mhaq_fq_bn_pool_bwd(const float* x, const float* g, const uint8_t* code, con
                         const float* weight, float* dx, float* dweight, float* dbias, int64_t n, int64_t h, int64_t w,
                         int64_t c, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * The stem's max pool and the gathering BatchNorm backward on 16-bit tensors (the stem under torch.autocast).  Additive to
+ * ABI v4 -- MHAQ_FQ_ABI_VERSION stays 4.  t, p, x, g and dx are dense NHWC tensors of the type named by `dtype`
+ * (MHAQ_FQ_DT_BF16 or MHAQ_FQ_DT_F16, anything else: MHAQ_FQ_EINVAL); c % 8 == 0, c <= 2^22 and n * h * w < 2^31 (else
+ * MHAQ_FQ_EUNSUPPORTED); t, p, x, g, dx and `workspace` 16-byte aligned, `code` 8-byte aligned (else MHAQ_FQ_EALIGN).  mean,
+ * invstd, weight, dweight, dbias and everything in `workspace` are fp32 / fp64; weight and each of the three outputs may be
+ * NULL.  Argument checks, their codes and their order are those of mhaq_fq_bn_pool_bwd (the dtype check follows the NULL
+ * checks), all before any launch.  Stream-ordered, capture-safe, stateless.
+ *
+ * mhaq_fq_maxpool3s2_fwd_x16: p and code as mhaq_fq_maxpool3s2_fwd gives them -- the same selection, compared on the exactly
+ * upcast values, the same code 4 / code 9 rule -- and p holds the chosen element's ORIGINAL 16 bits (a NaN keeps its payload):
+ * the bits of torch's max_pool2d on the 16-bit tensor.
+ *
+ * mhaq_fq_bn_pool_bwd_x16: mhaq_fq_bn_bwd_x16 on x[n, h, w, c] whose 16-bit dy is torch's max_pool2d backward of the 16-bit
+ * pooled gradient g[n, oh, ow, c], computed on the fly and never stored, bit for bit:
+ *   where ONE window covers (ih, iw):   dy = that window's g, unchanged (-0.0 stays -0.0), if its code names (ih, iw); +0.0 if not
+ *   where two or four windows do:       dy = R16(0.0f + sum of up(g)), an fp32 sum over the covering windows whose code names
+ *                                       (ih, iw), in ascending oh, then ascending ow, rounded to nearest-even ONCE
+ *   on a 1 x 1 plane (h == w == 1):   dy = R16(0.0f + up(g)) or +0.0: NHWC and NCHW are the same memory there, torch takes its
+ *                                       contiguous kernel, and that one sums and rounds even a single window's g
+ * R16 is torch's own conversion: for fp16 the hardware's (NaN stays NaN, overflow gives +-inf), for bf16 its software
+ * rounding, under which EVERY NaN sum becomes the quiet NaN 0x7FC0.  dy is upcast again, exactly, before it enters the fp64
+ * sums and the dx expression of mhaq_fq_bn_bwd_x16.  Same partition, sums and workspace layout as
+ * mhaq_fq_bn_bwd_x16(m = n * h * w): mhaq_fq_bn_pool_bwd_x16_workspace_bytes(n, h, w, c) equals
+ * mhaq_fq_bn_bwd_x16_workspace_bytes(n * h * w, c), and dx, dweight, dbias and every byte of the workspace are what that call
+ * gives on the materialized dy.
+ * ---------------------------------------------------------------------- */
+int mhaq_fq_maxpool3s2_fwd_x16(const void* t, void* p, uint8_t* code, int64_t n, int64_t h, int64_t w, int64_t c, int dtype,
+                               void* stream);
+size_t mhaq_fq_bn_pool_bwd_x16_workspace_bytes(int64_t n, int64_t h, int64_t w, int64_t c);
+int mhaq_fq_bn_pool_bwd_x16(const void* x, const void* g, const uint8_t* code, const float* mean, const float* invstd,
+                            const float* weight, void* dx, float* dweight, float* dbias, int64_t n, int64_t h, int64_t w,
+                            int64_t c, int dtype, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Whole-tensor min / max (zero point of a PER_TENSOR weight quantizer,
  * gdnsq_conv2d.py:82-83; min/max observer, calib/minmaxobserver.py:19-36).
  * out[0] = min, out[1] = max. */

@@ -64,6 +64,10 @@ SIGNATURES = {
     "mhaq_fq_maxpool3s2_fwd": (_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _p]),
     "mhaq_fq_bn_pool_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "mhaq_fq_bn_pool_bwd": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _sz, _p]),
+    # ... and on 16-bit tensors: `dtype` after c (additive, ABI v4 kept)
+    "mhaq_fq_maxpool3s2_fwd_x16": (_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _int, _p]),
+    "mhaq_fq_bn_pool_bwd_x16_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "mhaq_fq_bn_pool_bwd_x16": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _int, _p, _sz, _p]),
     "mhaq_fq_minmax_workspace_bytes": (_sz, [_i64]),
     "mhaq_fq_minmax": (_int, [_p, _i64, _p, _p, _sz, _p]),
     "mhaq_fq_row_minmax": (_int, [_p, _i64, _i64, _p, _p, _p]),

@@ -20,10 +20,20 @@
 // mhaq_fq_bn_bwd_x16).  A 16-bit element is converted UP exactly and takes the fp32 arithmetic unchanged -- the same fp64
 // sums, the same finalize, the same dx expression in the same order --; dx is rounded to nearest-even ONCE on the way out
 // (io16::down2: a plain cast, NaN stays NaN, fp16 overflow gives +-inf).  Statistics, weight, dweight, dbias and the
-// workspace stay fp32 / fp64.
-#include <type_traits>
-
+// workspace stay fp32 / fp64.  The pool's gather on 16-bit tensors (DyPool16, mhaq_fq_bn_pool_bwd_x16) rounds its dy to
+// 16 bits in registers where the framework's pool backward rounds the tensor it would have written.
 #include "fq_io16.hpp"
+
+// The two tunables of the 16-bit pool gather (DyPool16), overridable at build time: tools/stem_pool_bench.py --dtype bf16 times
+// builds with other values next to the product's.  Rows in flight in the reduction (2: 163 VGPRs, 3 waves / SIMD; 4: 229 VGPRs,
+// 2 waves; neither spills) and the cache policy of the loads of g and the codes (default: their 2.25-fold re-read has to hit
+// cache).
+#ifndef MHAQ_BN_POOL16_RED_U
+#define MHAQ_BN_POOL16_RED_U 2
+#endif
+#ifndef MHAQ_BN_POOL16_G_NT
+#define MHAQ_BN_POOL16_G_NT 0
+#endif
 
 namespace mhaq {
 
@@ -79,6 +89,7 @@ struct DyMem {
   using IO = IoF32;
   const float* __restrict__ dy;
   static constexpr int kDxWaves = 8;               // the occupancy the dx kernel is held to below kBnBigElems
+  static constexpr bool kGather = false;           // (the dx kernel hands a gathering source the pixel of each vector)
   struct Walk {
     __device__ __forceinline__ Walk(const DyMem&, uint32_t, uint32_t) {}
     __device__ __forceinline__ void next() {}
@@ -103,6 +114,7 @@ struct DyMem16 {
   using IO = Io16<DT>;
   const uint16_t* __restrict__ dy;
   static constexpr int kDxWaves = 6;               // 70 VGPRs (40 of them the constants of 8 channels): 8 waves would spill
+  static constexpr bool kGather = false;
   struct Walk {
     __device__ __forceinline__ Walk(const DyMem16&, uint32_t, uint32_t) {}
     __device__ __forceinline__ void next() {}
@@ -136,10 +148,12 @@ struct DyPool {
   const uint8_t* __restrict__ code;
   uint32_t h, w, oh, ow;
   static constexpr int kDxWaves = 5;               // 84 VGPRs with the gather's loads in flight: 8 waves would spill
+  static constexpr bool kGather = true;
   struct Walk {
     uint32_t n, ih, iw, dn, dh, dw, h, w;
     // row -> (n, ih, iw) once per lane; step = dn * h * w + dh * w + dw
-    __device__ __forceinline__ Walk(const DyPool& s, uint32_t row, uint32_t step) : h(s.h), w(s.w) {
+    template <class Src>
+    __device__ __forceinline__ Walk(const Src& s, uint32_t row, uint32_t step) : h(s.h), w(s.w) {
       const uint32_t q = row / w, sq = step / w;
       iw = row - q * w;
       n = q / h;
@@ -159,7 +173,9 @@ struct DyPool {
     }
   };
   struct Loads { vf4 g[4]; uint32_t c[4]; uint32_t want; };      // want: the four codes to match, one byte each
-  __device__ __forceinline__ Loads load_at(uint32_t n, uint32_t ih, uint32_t iw, bool ok, uint32_t col, uint32_t cv) const {
+  // the four candidate windows of (n, ih, iw): their pixels in g / code, and the code of each that names (ih, iw)
+  struct Cand { uint32_t px[4]; uint32_t want; };
+  static __device__ __forceinline__ Cand candidates(uint32_t n, uint32_t ih, uint32_t iw, bool ok, uint32_t oh, uint32_t ow) {
     if (!ok) n = ih = iw = 0u;                      // (a dropped row: any valid address)
     const uint32_t oa = ih >> 1, pa = iw >> 1;
     const bool vh = (ih & 1u) && oa + 1u < oh, vw = (iw & 1u) && pa + 1u < ow;
@@ -168,12 +184,31 @@ struct DyPool {
     const uint32_t w00 = kh * 3u + kw, w01 = vw ? kh * 3u : kPoolNoCode, w10 = vh ? kw : kPoolNoCode,
                    w11 = (vh && vw) ? 0u : kPoolNoCode;
     const uint32_t ra = (n * oh + oa) * ow, rb = (n * oh + ob) * ow;      // < n * h * w < 2^31
-    const uint32_t px[4] = {ra + pa, ra + pb, rb + pa, rb + pb};
-    Loads l;
-    l.want = w00 | (w01 << 8) | (w10 << 16) | (w11 << 24);
+    return Cand{{ra + pa, ra + pb, rb + pa, rb + pb}, w00 | (w01 << 8) | (w10 << 16) | (w11 << 24)};
+  }
+  // one candidate window: its g is passed on, not added to 0.0f
+  static __device__ __forceinline__ bool single(uint32_t want) { return (want >> 8) == 0xFFFFFFu; }
+  // byte j of the result == 0: candidate k is the argmax of channel j (c: four codes of candidate k)
+  static __device__ __forceinline__ uint32_t miss(uint32_t c, uint32_t want, int k) {
+    return c ^ (((want >> (8 * k)) & 0xFFu) * 0x01010101u);
+  }
+  // dy of one channel from g of its four candidates: hit bit k says that candidate k's code names the element
+  static __device__ __forceinline__ float gather(const float (&gk)[4], const bool (&hit)[4], bool one) {
+    float acc = 0.0f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const int64_t vidx = (int64_t)px[k] * cv + col;
+      const float sum = (k == 0 && one) ? gk[k] : acc + gk[k];
+      acc = hit[k] ? sum : acc;                    // a select: an unselected NaN stays out
+    }
+    return acc;
+  }
+  __device__ __forceinline__ Loads load_at(uint32_t n, uint32_t ih, uint32_t iw, bool ok, uint32_t col, uint32_t cv) const {
+    const Cand cd = candidates(n, ih, iw, ok, oh, ow);
+    Loads l;
+    l.want = cd.want;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int64_t vidx = (int64_t)cd.px[k] * cv + col;
       l.g[k] = bn_ld4<false>(g, vidx);
       l.c[k] = reinterpret_cast<const uint32_t*>(code)[vidx];
     }
@@ -191,20 +226,86 @@ struct DyPool {
   __device__ __forceinline__ void value(const Loads& l, float (&o)[4]) const {
     uint32_t d[4];                                  // byte j of d[k] == 0: candidate k is the argmax of channel j
 #pragma unroll
-    for (int k = 0; k < 4; ++k) d[k] = l.c[k] ^ (((l.want >> (8 * k)) & 0xFFu) * 0x01010101u);
-    const float gk[4][4] = {{l.g[0].x, l.g[0].y, l.g[0].z, l.g[0].w}, {l.g[1].x, l.g[1].y, l.g[1].z, l.g[1].w},
-                            {l.g[2].x, l.g[2].y, l.g[2].z, l.g[2].w}, {l.g[3].x, l.g[3].y, l.g[3].z, l.g[3].w}};
-    const bool single = (l.want >> 8) == 0xFFFFFFu;      // one candidate window: its g is passed on, not added to 0.0f
+    for (int k = 0; k < 4; ++k) d[k] = miss(l.c[k], l.want, k);
+    const float gk[4][4] = {{l.g[0].x, l.g[1].x, l.g[2].x, l.g[3].x}, {l.g[0].y, l.g[1].y, l.g[2].y, l.g[3].y},
+                            {l.g[0].z, l.g[1].z, l.g[2].z, l.g[3].z}, {l.g[0].w, l.g[1].w, l.g[2].w, l.g[3].w}};
+    const bool one = single(l.want);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      float acc = 0.0f;
+      bool hit[4];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const bool hit = ((d[k] >> (8 * j)) & 0xFFu) == 0u;
-        const float sum = (k == 0 && single) ? gk[k][j] : acc + gk[k][j];
-        acc = hit ? sum : acc;                     // a select: an unselected NaN stays out
-      }
-      o[j] = acc;
+      for (int k = 0; k < 4; ++k) hit[k] = ((d[k] >> (8 * j)) & 0xFFu) == 0u;
+      o[j] = gather(gk[j], hit, one);
+    }
+  }
+};
+
+// The same gather on 16-bit tensors: g and dy of the element type DT, a lane owns 8 channels (one 16-byte load of g and one
+// 8-byte load of codes per candidate window).  The framework's pool backward writes a 16-bit dy, and this source hands out
+// the bits of that tensor, upcast: where ONE window covers (ih, iw) its g passes through unchanged (or +0.0); where two or
+// four do, the framework adds up(g) of the windows whose code names the element in an fp32 accumulator that starts at 0.0f,
+// in ascending oh, then ascending ow, and rounds the sum to 16 bits ONCE -- with its own conversions: fp16 the hardware's
+// (io16::down1), bf16 the framework's software rounding, which gives the one quiet NaN 0x7FC0 for every NaN.
+// A 1 x 1 plane is the exception to the first rule (`summed`): NHWC and NCHW are the same memory there, the framework takes
+// its contiguous kernel, and that one sums and rounds every element: dy = R16(0.0f + up(g)), a -0.0 arrives as +0.0.
+template <int DT>
+struct DyPool16 {
+  using IO = Io16<DT>;
+  typedef uint32_t vu2 __attribute__((ext_vector_type(2)));
+  const uint16_t* __restrict__ g;
+  const uint8_t* __restrict__ code;
+  uint32_t h, w, oh, ow;
+  bool summed;                                     // h == w == 1
+  static constexpr int kDxWaves = 3;               // 133 VGPRs with the gather's loads of two vectors in flight: 4 waves spill
+  static constexpr bool kGather = true;
+  static constexpr bool kGNt = MHAQ_BN_POOL16_G_NT != 0;
+  using Walk = DyPool::Walk;
+  struct Loads { io16::vu4 g[4]; vu2 c[4]; uint32_t want; };
+  __device__ __forceinline__ Loads load_at(uint32_t n, uint32_t ih, uint32_t iw, bool ok, uint32_t col, uint32_t cv) const {
+    const DyPool::Cand cd = DyPool::candidates(n, ih, iw, ok, oh, ow);
+    Loads l;
+    l.want = cd.want;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int64_t vidx = (int64_t)cd.px[k] * cv + col;
+      l.g[k] = io16::ld8<kGNt>(g, vidx);
+      const vu2* cq = reinterpret_cast<const vu2*>(code) + vidx;
+      l.c[k] = kGNt ? __builtin_nontemporal_load(cq) : *cq;
+    }
+    return l;
+  }
+  template <bool NT>
+  __device__ __forceinline__ Loads load(int64_t, const Walk& k, bool ok, uint32_t col, uint32_t cv) const {
+    return load_at(k.n, k.ih, k.iw, ok, col, cv);
+  }
+  template <bool NT>
+  __device__ __forceinline__ Loads load_at_pixel(int64_t, uint32_t pixel, bool ok, uint32_t col, uint32_t cv) const {
+    const uint32_t q = pixel / w, n = q / h;
+    return load_at(n, q - n * h, pixel - q * w, ok, col, cv);
+  }
+  // the fp32 sum as the framework stores it in a 16-bit dy, upcast again
+  static __device__ __forceinline__ float round16(float f) {
+    if constexpr (DT == MHAQ_FQ_DT_BF16) return io16::up1<DT>(f != f ? (uint16_t)0x7FC0u : io16::down1<DT>(f));
+    else return io16::up1<DT>(io16::down1<DT>(f));
+  }
+  __device__ __forceinline__ void value(const Loads& l, float (&o)[8]) const {
+    uint32_t d[4][2];                               // byte j of d[k][j / 4]: DyPool::miss
+    float gk[4][8];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      d[k][0] = DyPool::miss(l.c[k].x, l.want, k);
+      d[k][1] = DyPool::miss(l.c[k].y, l.want, k);
+      IO::unpack(l.g[k], gk[k]);
+    }
+    const bool one = DyPool::single(l.want) && !summed;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float gj[4] = {gk[0][j], gk[1][j], gk[2][j], gk[3][j]};
+      bool hit[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) hit[k] = ((d[k][j >> 2] >> (8 * (j & 3))) & 0xFFu) == 0u;
+      const float acc = DyPool::gather(gj, hit, one);
+      o[j] = one ? acc : round16(acc);             // (one window: g itself or +0.0, already a 16-bit value)
     }
   }
 };
@@ -219,6 +320,7 @@ struct DyPool {
 constexpr int kBnCols = 16;
 constexpr int kBnRedU = 4;
 constexpr int kBnPoolRedU = 4;        // rows in flight with the pool's gather (9 loads per row, 163 VGPRs, no scratch); 2 measured the same
+constexpr int kBnPool16RedU = MHAQ_BN_POOL16_RED_U;      // ... and with the 16-bit gather (DyPool16)
 constexpr int kBnMinRows = 448;
 constexpr int kBnMaxChunks = 2048;
 constexpr int kBnDxU = 2;             // float4 per lane and stream in the dx kernel (kBwdU of fq_pt.hip)
@@ -418,7 +520,7 @@ __launch_bounds__(kBlock) void bn_bwd_dx_kernel(
   typename IO::Vec a[kBnDxU];
   typename Dy::Loads b[kBnDxU];
   uint32_t pix0 = 0, col0 = 0;
-  if constexpr (std::is_same<Dy, DyPool>::value) {
+  if constexpr (Dy::kGather) {
     const uint32_t q = blockIdx.x / (uint32_t)cv, r = (blockIdx.x - q * (uint32_t)cv) * (uint32_t)(kBlock * kBnDxU);
     const uint32_t rq = r / (uint32_t)cv;
     pix0 = q * (uint32_t)(kBlock * kBnDxU) + rq;
@@ -561,13 +663,69 @@ __global__ __launch_bounds__(kBlock) void maxpool3s2_fwd_kernel(
   reinterpret_cast<uint32_t*>(code)[idx] = cd[0] | (cd[1] << 8) | (cd[2] << 16) | (cd[3] << 24);
 }
 
+// The same pool on a dense 16-bit NHWC tensor of the element type DT: one lane per 8 output channels, nine 16-byte loads, a
+// 16-byte store of p and an 8-byte store of codes.  Selection and codes as above, compared on the exactly upcast values (the
+// framework's kernel compares in fp32 too); what is stored is the chosen element's ORIGINAL 16 bits, so a NaN keeps its payload.
+template <int DT>
+__global__ __launch_bounds__(kBlock) void maxpool3s2_fwd16_kernel(
+    const uint16_t* __restrict__ t, uint16_t* __restrict__ p, uint8_t* __restrict__ code, uint32_t h, uint32_t w, uint32_t oh,
+    uint32_t ow, uint32_t cv, int64_t nvec) {
+  typedef uint32_t vu2 __attribute__((ext_vector_type(2)));
+  const uint32_t bq = blockIdx.x / cv, br = (blockIdx.x - bq * cv) * (uint32_t)kBlock, brq = br / cv;
+  const uint32_t tt = br - brq * cv + threadIdx.x, tq = tt / cv;
+  const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool ok = idx < nvec;
+  const uint32_t pixel = ok ? bq * (uint32_t)kBlock + brq + tq : 0u, col = tt - tq * cv;
+  const uint32_t q = pixel / ow, n = q / oh, po = q - n * oh, pw = pixel - q * ow;
+  const int ih0 = (int)(po * 2u) - 1, iw0 = (int)(pw * 2u) - 1;
+  io16::vu4 v[9];
+  bool in[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const int ih = ih0 + k / 3, iw = iw0 + k % 3;
+    in[k] = ih >= 0 && ih < (int)h && iw >= 0 && iw < (int)w;
+    const uint32_t ihc = (uint32_t)(ih < 0 ? 0 : (ih < (int)h ? ih : (int)h - 1));
+    const uint32_t iwc = (uint32_t)(iw < 0 ? 0 : (iw < (int)w ? iw : (int)w - 1));
+    v[k] = io16::ld8<false>(t, (int64_t)((n * h + ihc) * w + iwc) * cv + col);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  if (!ok) return;
+  const uint32_t start = (po == 0u && pw == 0u) ? 4u : kPoolNoneChosen;     // the framework's initial index 0
+  float mx[8];
+  uint32_t raw[8], cd[8];                         // raw: the chosen element's 16 bits (-inf until one is chosen)
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    mx[j] = -INFINITY;
+    raw[j] = DT == MHAQ_FQ_DT_BF16 ? 0xFF80u : 0xFC00u;
+    cd[j] = start;
+  }
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    float e[8];
+    Io16<DT>::unpack(v[k], e);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const bool take = in[k] && (e[j] > mx[j] || e[j] != e[j]);
+      mx[j] = take ? e[j] : mx[j];
+      raw[j] = take ? (v[k][j >> 1] >> (16 * (j & 1))) & 0xFFFFu : raw[j];
+      cd[j] = take ? (uint32_t)k : cd[j];
+    }
+  }
+  io16::vu4 pv;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) pv[i] = raw[2 * i] | (raw[2 * i + 1] << 16);
+  reinterpret_cast<io16::vu4*>(p)[idx] = pv;
+  reinterpret_cast<vu2*>(code)[idx] = vu2{cd[0] | (cd[1] << 8) | (cd[2] << 16) | (cd[3] << 24),
+                                          cd[4] | (cd[5] << 8) | (cd[6] << 16) | (cd[7] << 24)};
+}
+
 // pooled extent of kernel 3, stride 2, padding 1, dilation 1, ceil_mode = false
 static inline int64_t pool_out(int64_t in) { return (in - 1) / 2 + 1; }
-// n, h, w, c of either pool entry point: 0, or the error code
-static inline int pool_dims_status(int64_t n, int64_t h, int64_t w, int64_t c) {
+// n, h, w, c of a pool entry point (cmask: 3 for fp32, a lane owns 4 channels; 7 for 16-bit elements): 0, or the error code
+static inline int pool_dims_status(int64_t n, int64_t h, int64_t w, int64_t c, int64_t cmask = 3) {
   if (n <= 0 || h <= 0 || w <= 0 || c <= 0) return MHAQ_FQ_EINVAL;
   // the pixel arithmetic of the kernels is 32-bit: n * h * w < 2^31
-  if ((c & 3) || c > kBnMaxChannels || h >= (1ll << 31) || w >= (1ll << 31) || n >= (1ll << 31) ||
+  if ((c & cmask) || c > kBnMaxChannels || h >= (1ll << 31) || w >= (1ll << 31) || n >= (1ll << 31) ||
       n * h >= (1ll << 31) || n * h * w >= (1ll << 31))
     return MHAQ_FQ_EUNSUPPORTED;
   return 0;
@@ -658,6 +816,55 @@ int mhaq_fq_bn_pool_bwd(const float* x, const float* g, const uint8_t* code, con
   const DyPool src{g, code, (uint32_t)h, (uint32_t)w, (uint32_t)pool_out(h), (uint32_t)pool_out(w)};
   return bn_bwd_launch<DyPool, kBnPoolRedU>(x, src, mean, invstd, weight, dx, dweight, dbias, n * h * w, c, workspace,
                                             (hipStream_t)stream);
+}
+
+int mhaq_fq_maxpool3s2_fwd_x16(const void* t, void* p, uint8_t* code, int64_t n, int64_t h, int64_t w, int64_t c, int dtype,
+                               void* stream) {
+  if (!t || !p || !code) return MHAQ_FQ_EINVAL;
+  if (dtype != MHAQ_FQ_DT_BF16 && dtype != MHAQ_FQ_DT_F16) return MHAQ_FQ_EINVAL;
+  if (const int rc = pool_dims_status(n, h, w, c, 7)) return rc;
+  if (!bn_aligned(t, 16) || !bn_aligned(p, 16) || !bn_aligned(code, 8)) return MHAQ_FQ_EALIGN;
+  const int64_t oh = pool_out(h), ow = pool_out(w), nvec = n * oh * ow * (c >> 3);
+  const int64_t grid = (nvec + kBlock - 1) / kBlock;
+  if (grid > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
+  const uint16_t* t16 = (const uint16_t*)t;
+  if (dtype == MHAQ_FQ_DT_BF16)
+    MHAQ_LAUNCH(maxpool3s2_fwd16_kernel<MHAQ_FQ_DT_BF16>, dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream, t16,
+                (uint16_t*)p, code, (uint32_t)h, (uint32_t)w, (uint32_t)oh, (uint32_t)ow, (uint32_t)(c >> 3), nvec);
+  else
+    MHAQ_LAUNCH(maxpool3s2_fwd16_kernel<MHAQ_FQ_DT_F16>, dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream, t16,
+                (uint16_t*)p, code, (uint32_t)h, (uint32_t)w, (uint32_t)oh, (uint32_t)ow, (uint32_t)(c >> 3), nvec);
+  return launch_status();
+}
+
+size_t mhaq_fq_bn_pool_bwd_x16_workspace_bytes(int64_t n, int64_t h, int64_t w, int64_t c) {
+  if (pool_dims_status(n, h, w, c, 7)) return 0;
+  return mhaq_fq_bn_bwd_x16_workspace_bytes(n * h * w, c);
+}
+
+int mhaq_fq_bn_pool_bwd_x16(const void* x, const void* g, const uint8_t* code, const float* mean, const float* invstd,
+                            const float* weight, void* dx, float* dweight, float* dbias, int64_t n, int64_t h, int64_t w,
+                            int64_t c, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!x || !g || !code || !mean || !invstd || !workspace) return MHAQ_FQ_EINVAL;
+  if (dtype != MHAQ_FQ_DT_BF16 && dtype != MHAQ_FQ_DT_F16) return MHAQ_FQ_EINVAL;
+  if (const int rc = pool_dims_status(n, h, w, c, 7)) return rc;
+  if (workspace_bytes < mhaq_fq_bn_pool_bwd_x16_workspace_bytes(n, h, w, c)) return MHAQ_FQ_EWORKSPACE;
+  if (!bn_aligned(x, 16) || !bn_aligned(g, 16) || !bn_aligned(code, 8) || !bn_aligned(dx, 16) ||
+      !bn_aligned(workspace, 16) || !bn_aligned(mean, 4) || !bn_aligned(invstd, 4) || !bn_aligned(weight, 4) ||
+      !bn_aligned(dweight, 4) || !bn_aligned(dbias, 4))
+    return MHAQ_FQ_EALIGN;
+  const uint16_t* x16 = (const uint16_t*)x;
+  const uint16_t* g16 = (const uint16_t*)g;
+  const uint32_t uh = (uint32_t)h, uw = (uint32_t)w, oh = (uint32_t)pool_out(h), ow = (uint32_t)pool_out(w);
+  const bool plane1 = h == 1 && w == 1;
+  if (dtype == MHAQ_FQ_DT_BF16) {
+    const DyPool16<MHAQ_FQ_DT_BF16> src{g16, code, uh, uw, oh, ow, plane1};
+    return bn_bwd_launch<DyPool16<MHAQ_FQ_DT_BF16>, kBnPool16RedU>(x16, src, mean, invstd, weight, (uint16_t*)dx, dweight, dbias,
+                                                                   n * h * w, c, workspace, (hipStream_t)stream);
+  }
+  const DyPool16<MHAQ_FQ_DT_F16> src{g16, code, uh, uw, oh, ow, plane1};
+  return bn_bwd_launch<DyPool16<MHAQ_FQ_DT_F16>, kBnPool16RedU>(x16, src, mean, invstd, weight, (uint16_t*)dx, dweight, dbias,
+                                                                n * h * w, c, workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"

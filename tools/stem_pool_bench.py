@@ -11,6 +11,8 @@ writes it), TB/s is bytes / min.
     python3 tools/stem_pool_bench.py --out profiles/r11_stem_pool_micro.txt [--lib label=/path/to/libmhaq_fq.so ...]
 
 --lib adds builds of the same library (cache policies, rows in flight) as further rows; the product library is always first.
+--dtype bf16 / fp16 times the 16-bit forms on the same tensor in that type: torch's 16-bit pool, mhaq_fq_maxpool3s2_fwd_x16,
+mhaq_fq_bn_bwd_x16 on torch's 16-bit dy and mhaq_fq_bn_pool_bwd_x16 (profiles/r15_stem_pool16_micro.txt).
 """
 import argparse
 import ctypes
@@ -37,28 +39,34 @@ def main():
     ap.add_argument("--shape", type=int, nargs=4, default=[250, 64, 112, 112], metavar=("N", "C", "H", "W"))
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--lib", action="append", default=[], metavar="LABEL=PATH")
+    ap.add_argument("--dtype", choices=["fp32", "bf16", "fp16"], default="fp32")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    dtype = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype]
+    x16 = args.dtype != "fp32"
+    dt = {"bf16": _lib.DT_BF16, "fp16": _lib.DT_F16}.get(args.dtype)
+    es = 2 if x16 else 4                               # bytes per element of x, t, g, p, dy and dx
+    bits = (lambda a: a.view(torch.int16)) if x16 else (lambda a: a.view(torch.int32))
     dev = "cuda:0"
     n, c, h, w = args.shape
     oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
     libs = [("product", _lib.lib())] + [(s.split("=", 1)[0], load(s.split("=", 1)[1])) for s in args.lib]
     gen = torch.Generator(device=dev).manual_seed(1)
     cl = torch.channels_last
-    x = torch.randn((n, c, h, w), device=dev, generator=gen).contiguous(memory_format=cl)
+    x = torch.randn((n, c, h, w), device=dev, generator=gen).to(dtype).contiguous(memory_format=cl)
     # the pool's input (which element wins is data, not a cost: every element is read either way)
-    t0 = (torch.randn((n, c, h, w), device=dev, generator=gen) * 2).contiguous(memory_format=cl)
+    t0 = (torch.randn((n, c, h, w), device=dev, generator=gen) * 2).to(dtype).contiguous(memory_format=cl)
     t = t0.clone(memory_format=torch.preserve_format)
-    g0 = torch.randn((n, c, oh, ow), device=dev, generator=gen).contiguous(memory_format=cl)
+    g0 = torch.randn((n, c, oh, ow), device=dev, generator=gen).to(dtype).contiguous(memory_format=cl)
     g = g0.clone(memory_format=torch.preserve_format)
-    mean = x.mean((0, 2, 3))
-    invstd = (x.var((0, 2, 3), unbiased=False) + 1e-5).rsqrt()
+    mean = x.mean((0, 2, 3), dtype=torch.float32)
+    invstd = (x.float().var((0, 2, 3), unbiased=False) + 1e-5).rsqrt()
     gamma = torch.randn(c, device=dev, generator=gen)
     p = torch.empty_like(g)
     code = torch.empty(g.shape, dtype=torch.uint8, device=dev).contiguous(memory_format=cl)
     dx = torch.empty_like(x)
     dw, db = torch.empty(c, device=dev), torch.empty(c, device=dev)
-    nb = libs[0][1].mhaq_fq_bn_bwd_workspace_bytes(n * h * w, c)
+    nb = (libs[0][1].mhaq_fq_bn_bwd_x16_workspace_bytes if x16 else libs[0][1].mhaq_fq_bn_bwd_workspace_bytes)(n * h * w, c)
     ws = torch.empty(nb, dtype=torch.uint8, device=dev)
     flush = torch.empty(1 << 28, dtype=torch.float32, device=dev)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -75,15 +83,26 @@ def main():
         state["dy"] = torch.ops.aten.max_pool2d_with_indices_backward(g, t, k3, s2, p1, d1, False, idx_t)
 
     def bn_bwd(L):
-        assert L.mhaq_fq_bn_bwd(P(x), P(state["dy"]), P(mean), P(invstd), P(gamma), P(dx), P(dw), P(db), n * h * w, c,
-                                P(ws), nb, st) == 0
+        if x16:
+            assert L.mhaq_fq_bn_bwd_x16(P(x), P(state["dy"]), P(mean), P(invstd), P(gamma), P(dx), P(dw), P(db), n * h * w, c,
+                                        dt, P(ws), nb, st) == 0
+        else:
+            assert L.mhaq_fq_bn_bwd(P(x), P(state["dy"]), P(mean), P(invstd), P(gamma), P(dx), P(dw), P(db), n * h * w, c,
+                                    P(ws), nb, st) == 0
 
     def hip_fwd(L):
-        assert L.mhaq_fq_maxpool3s2_fwd(P(t), P(p), P(code), n, h, w, c, st) == 0
+        if x16:
+            assert L.mhaq_fq_maxpool3s2_fwd_x16(P(t), P(p), P(code), n, h, w, c, dt, st) == 0
+        else:
+            assert L.mhaq_fq_maxpool3s2_fwd(P(t), P(p), P(code), n, h, w, c, st) == 0
 
     def hip_bwd(L):
-        assert L.mhaq_fq_bn_pool_bwd(P(x), P(g), P(code), P(mean), P(invstd), P(gamma), P(dx), P(dw), P(db), n, h, w, c,
-                                     P(ws), nb, st) == 0
+        if x16:
+            assert L.mhaq_fq_bn_pool_bwd_x16(P(x), P(g), P(code), P(mean), P(invstd), P(gamma), P(dx), P(dw), P(db), n, h, w,
+                                             c, dt, P(ws), nb, st) == 0
+        else:
+            assert L.mhaq_fq_bn_pool_bwd(P(x), P(g), P(code), P(mean), P(invstd), P(gamma), P(dx), P(dw), P(db), n, h, w, c,
+                                         P(ws), nb, st) == 0
 
     def timed(fn, rewrite):
         out = []
@@ -106,34 +125,36 @@ def main():
     rows = []
 
     def row(what, variant, mm, nbytes):
-        rows.append(f"{what:>34s} {variant:>8s} {mm[0]:8.1f} {mm[1]:8.1f} {nbytes / 1e6:8.0f} {nbytes / mm[0] / 1e6:6.2f}")
+        rows.append(f"{what:>38s} {variant:>8s} {mm[0]:8.1f} {mm[1]:8.1f} {nbytes / 1e6:8.0f} {nbytes / mm[0] / 1e6:6.2f}")
         print(rows[-1], flush=True)
 
     # exactness first: the two forms give the same bits
     hip_fwd(libs[0][1])
-    assert torch.equal(p, p_t), "pool forward differs from torch"
+    assert torch.equal(bits(p), bits(p_t)), "pool forward differs from torch"
     torch_pool_bwd()
     bn_bwd(libs[0][1])
     ref = (dx.clone(), dw.clone(), db.clone())
     hip_bwd(libs[0][1])
-    assert all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(ref, (dx, dw, db))), "backward differs"
+    assert torch.equal(bits(ref[0]), bits(dx)), "backward differs (dx)"
+    assert all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(ref[1:], (dw, db))), "backward differs"
     del ref
-    row("pool fwd", "torch", timed(torch_fwd, rew_t), 4 * elems + 4 * pel + 8 * pel)
+    sfx = "_x16" if x16 else ""
+    row("pool fwd", "torch", timed(torch_fwd, rew_t), es * elems + es * pel + 8 * pel)
     for label, L in libs:
-        row("pool fwd", label, timed(lambda: hip_fwd(L), rew_t), 4 * elems + 4 * pel + pel)
+        row("pool fwd", label, timed(lambda: hip_fwd(L), rew_t), es * elems + es * pel + pel)
     hip_fwd(libs[0][1])
-    row("pool bwd (torch)", "torch", timed(torch_pool_bwd, rew_g), 8 * pel + 4 * pel + 4 * elems)
-    row("mhaq_fq_bn_bwd on that dy", "product", timed(lambda: bn_bwd(libs[0][1]), lambda: None), 20 * elems)
-    row("pool bwd (torch) + mhaq_fq_bn_bwd", "product", timed(lambda: (torch_pool_bwd(), bn_bwd(libs[0][1])), rew_g),
-        8 * pel + 4 * pel + 4 * elems + 20 * elems)
+    row("pool bwd (torch)", "torch", timed(torch_pool_bwd, rew_g), 8 * pel + es * pel + es * elems)
+    row(f"mhaq_fq_bn_bwd{sfx} on that dy", "product", timed(lambda: bn_bwd(libs[0][1]), lambda: None), 5 * es * elems)
+    row(f"pool bwd (torch) + mhaq_fq_bn_bwd{sfx}", "product", timed(lambda: (torch_pool_bwd(), bn_bwd(libs[0][1])), rew_g),
+        8 * pel + es * pel + es * elems + 5 * es * elems)
     for label, L in libs:
-        row("mhaq_fq_bn_pool_bwd", label, timed(lambda: hip_bwd(L), rew_g), 2 * (4 * elems + 4 * pel + pel) + 4 * elems)
-    head = (f"Stem pool and BatchNorm backward stand-alone, {tuple(args.shape)} fp32 channels_last ({elems / 1e6:.1f} M elements), one "
+        row(f"mhaq_fq_bn_pool_bwd{sfx}", label, timed(lambda: hip_bwd(L), rew_g), 2 * (es * elems + es * pel + pel) + es * elems)
+    head = (f"Stem pool and BatchNorm backward stand-alone, {tuple(args.shape)} {args.dtype} channels_last ({elems / 1e6:.1f} M elements), one "
             f"{torch.cuda.get_device_name(0)}.\nBefore every timed call a 1 GiB buffer is written and the producer's tensor (t for the "
             f"forward, the pooled gradient for the backward;\nnothing for the line that times mhaq_fq_bn_bwd alone: its dy stays as the "
             f"flush left it) is rewritten; {args.reps} timed calls after one warm-up,\nHIP events around the whole call.  MB = algorithmic "
             f"bytes, TB/s = MB / min.  Both forms were checked to give the same bits first.\n\n"
-            f"{'what':>34s} {'variant':>8s} {'min us':>8s} {'med us':>8s} {'MB':>8s} {'TB/s':>6s}\n")
+            f"{'what':>38s} {'variant':>8s} {'min us':>8s} {'med us':>8s} {'MB':>8s} {'TB/s':>6s}\n")
     text = head + "\n".join(rows) + "\n"
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
