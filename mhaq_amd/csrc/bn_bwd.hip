@@ -22,6 +22,11 @@
 // (io16::down2: a plain cast, NaN stays NaN, fp16 overflow gives +-inf).  Statistics, weight, dweight, dbias and the
 // workspace stay fp32 / fp64.  The pool's gather on 16-bit tensors (DyPool16, mhaq_fq_bn_pool_bwd_x16) rounds its dy to
 // 16 bits in registers where the framework's pool backward rounds the tensor it would have written.
+//
+// The host side is written once ("the host path of the entry points" below): bn_bwd_status is the argument check of all four
+// backward entry points and pool_fwd_status that of the two pool forwards, bn_workspace_bytes stands behind the four workspace
+// queries, and io16::with_dtype (fq_io16.hpp) turns the dtype of an *_x16 call into the template argument, so that every
+// bn_bwd_launch<Dy, RU> is named in one place.
 #include "fq_io16.hpp"
 
 // The two tunables of the 16-bit pool gather (DyPool16), overridable at build time: tools/stem_pool_bench.py --dtype bf16 times
@@ -85,51 +90,33 @@ struct Io16 {
 // A source hands out, per 16-byte vector of x, a bundle of loads (issued with x's, before anything waits) and later the IO::kW dy
 // values out of it.  `Walk` follows a lane's rows through the reduction: (n, ih, iw) of a row, advanced by a fixed row
 // step without a division.
-struct DyMem {
-  using IO = IoF32;
-  const float* __restrict__ dy;
-  static constexpr int kDxWaves = 8;               // the occupancy the dx kernel is held to below kBnBigElems
+// dy as a tensor in memory, of the element type IOT
+template <class IOT>
+struct DyMemT {
+  using IO = IOT;
+  const typename IO::T* __restrict__ dy;
+  // fp32: the occupancy the dx kernel is held to below kBnBigElems
+  // 16-bit: 70 VGPRs (40 of them the constants of 8 channels): 8 waves would spill
+  static constexpr int kDxWaves = IO::kW == 8 ? 6 : 8;
   static constexpr bool kGather = false;           // (the dx kernel hands a gathering source the pixel of each vector)
   struct Walk {
-    __device__ __forceinline__ Walk(const DyMem&, uint32_t, uint32_t) {}
+    __device__ __forceinline__ Walk(const DyMemT&, uint32_t, uint32_t) {}
     __device__ __forceinline__ void next() {}
   };
-  struct Loads { vf4 v; };
+  struct Loads { typename IO::Vec v; };
   template <bool NT>
   __device__ __forceinline__ Loads load(int64_t vidx, const Walk&, bool, uint32_t, uint32_t) const {
-    return Loads{bn_ld4<NT>(dy, vidx)};
+    return Loads{IO::template ld<NT>(dy, vidx)};
   }
   template <bool NT>
   __device__ __forceinline__ Loads load_at_pixel(int64_t vidx, uint32_t, bool, uint32_t, uint32_t) const {
-    return Loads{bn_ld4<NT>(dy, vidx)};
+    return Loads{IO::template ld<NT>(dy, vidx)};
   }
-  __device__ __forceinline__ void value(const Loads& l, float (&o)[4]) const {
-    o[0] = l.v.x; o[1] = l.v.y; o[2] = l.v.z; o[3] = l.v.w;
-  }
+  __device__ __forceinline__ void value(const Loads& l, float (&o)[IO::kW]) const { IO::unpack(l.v, o); }
 };
-
-// dy as a 16-bit tensor in memory
+using DyMem = DyMemT<IoF32>;                        // dy as an fp32 tensor in memory
 template <int DT>
-struct DyMem16 {
-  using IO = Io16<DT>;
-  const uint16_t* __restrict__ dy;
-  static constexpr int kDxWaves = 6;               // 70 VGPRs (40 of them the constants of 8 channels): 8 waves would spill
-  static constexpr bool kGather = false;
-  struct Walk {
-    __device__ __forceinline__ Walk(const DyMem16&, uint32_t, uint32_t) {}
-    __device__ __forceinline__ void next() {}
-  };
-  struct Loads { io16::vu4 v; };
-  template <bool NT>
-  __device__ __forceinline__ Loads load(int64_t vidx, const Walk&, bool, uint32_t, uint32_t) const {
-    return Loads{io16::ld8<NT>(dy, vidx)};
-  }
-  template <bool NT>
-  __device__ __forceinline__ Loads load_at_pixel(int64_t vidx, uint32_t, bool, uint32_t, uint32_t) const {
-    return Loads{io16::ld8<NT>(dy, vidx)};
-  }
-  __device__ __forceinline__ void value(const Loads& l, float (&o)[8]) const { IO::unpack(l.v, o); }
-};
+using DyMem16 = DyMemT<Io16<DT>>;                   // ... as a 16-bit one
 
 // dy[n, ih, iw, .] of max_pool2d(kernel 3, stride 2, padding 1) from the pooled gradient g[n, oh, ow, .] and the argmax
 // code (kh * 3 + kw of the chosen element, one byte per output element).  The windows that cover row ih are
@@ -573,38 +560,47 @@ __launch_bounds__(kBlock) void bn_bwd_dx_kernel(
 
 static inline bool bn_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
-// The three launches behind both entry points (arguments checked by the caller); RU = rows in flight in the reduction.
+// What the four backward entry points have in common, with the element type of x, the gradient source and dx erased.
+struct BnCall {
+  const void *x, *src;                              // src: dy, or the pooled gradient g
+  const float *mean, *invstd, *weight;
+  void* dx;
+  float *dweight, *dbias;
+  void* workspace;
+  size_t workspace_bytes;
+  void* stream;
+};
+
+// The three launches behind every entry point (arguments checked by bn_bwd_status); RU = rows in flight in the reduction.
 template <class Dy, int RU>
-static int bn_bwd_launch(const typename Dy::IO::T* x, const Dy dy, const float* mean, const float* invstd,
-                         const float* weight, typename Dy::IO::T* dx, float* dweight, float* dbias, int64_t m, int64_t c,
-                         void* workspace, hipStream_t st) {
+static int bn_bwd_launch(const BnCall& a, const Dy dy, int64_t m, int64_t c) {
   using IO = typename Dy::IO;
   constexpr bool x16 = IO::kW == 8;
+  const typename IO::T* x = (const typename IO::T*)a.x;
+  typename IO::T* dx = (typename IO::T*)a.dx;
+  hipStream_t st = (hipStream_t)a.stream;
   const BnGeom g = bn_geom_io<IO>(m, c);
   const int64_t nvec = m * (c / IO::kW);
   const int64_t dx_grid = (nvec + kBlock * kBnDxU - 1) / (kBlock * kBnDxU);
   if (g.nchunks > 0x7fffffff || dx_grid > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
-  if (!dx && !dweight && !dbias) return 0;
-  float* consts = (float*)workspace;
+  if (!dx && !a.dweight && !a.dbias) return 0;
+  float* consts = (float*)a.workspace;
   double* parts = (double*)(consts + kBnNConst * c);      // 20 * c bytes in: 16-byte aligned (c % 4 == 0)
   const int cv = (int)(c / IO::kW);
   const bool nt_r = m * c >= (x16 ? kBn16ReduceNtElems : kBnReduceNtElems);
   const bool nt_d = m * c >= (x16 ? kBn16DxNtElems : kBnDxNtElems), big = m * c >= (x16 ? kBn16BigElems : kBnBigElems);
   const dim3 rgrid((unsigned)g.nchunks, (unsigned)g.ncol);
-  if (nt_r) MHAQ_LAUNCH((bn_bwd_reduce_kernel<true, Dy, RU>), rgrid, dim3(kBlock), 0, st, x, dy, mean, parts, m, cv, g.rows);
-  else MHAQ_LAUNCH((bn_bwd_reduce_kernel<false, Dy, RU>), rgrid, dim3(kBlock), 0, st, x, dy, mean, parts, m, cv, g.rows);
+  MHAQ_LAUNCH((nt_r ? bn_bwd_reduce_kernel<true, Dy, RU> : bn_bwd_reduce_kernel<false, Dy, RU>), rgrid, dim3(kBlock), 0, st, x,
+              dy, a.mean, parts, m, cv, g.rows);
   int rc = launch_status();
   if (rc) return rc;
   MHAQ_LAUNCH(bn_bwd_finalize_kernel, dim3((unsigned)(c >> 2)), dim3(kBlock), 0, st, (const double*)parts, (int)g.nchunks,
-              (int)c, mean, invstd, weight, 1.0 / (double)m, consts, dweight, dbias);
+              (int)c, a.mean, a.invstd, a.weight, 1.0 / (double)m, consts, a.dweight, a.dbias);
   rc = launch_status();
   if (rc || !dx) return rc;
-  const dim3 dgrid((unsigned)dx_grid);
-#define MHAQ_LAUNCH_BN_DX(NT, BG) \
-  MHAQ_LAUNCH((bn_bwd_dx_kernel<NT, BG, Dy>), dgrid, dim3(kBlock), 0, st, x, dy, dx, nvec, cv, (const float*)consts)
-  if (big) { if (nt_d) MHAQ_LAUNCH_BN_DX(true, true); else MHAQ_LAUNCH_BN_DX(false, true); }
-  else { if (nt_d) MHAQ_LAUNCH_BN_DX(true, false); else MHAQ_LAUNCH_BN_DX(false, false); }
-#undef MHAQ_LAUNCH_BN_DX
+  MHAQ_LAUNCH((big ? (nt_d ? bn_bwd_dx_kernel<true, true, Dy> : bn_bwd_dx_kernel<false, true, Dy>)
+                   : (nt_d ? bn_bwd_dx_kernel<true, false, Dy> : bn_bwd_dx_kernel<false, false, Dy>)),
+              dim3((unsigned)dx_grid), dim3(kBlock), 0, st, x, dy, dx, nvec, cv, (const float*)consts);
   return launch_status();
 }
 
@@ -721,14 +717,65 @@ __global__ __launch_bounds__(kBlock) void maxpool3s2_fwd16_kernel(
 
 // pooled extent of kernel 3, stride 2, padding 1, dilation 1, ceil_mode = false
 static inline int64_t pool_out(int64_t in) { return (in - 1) / 2 + 1; }
-// n, h, w, c of a pool entry point (cmask: 3 for fp32, a lane owns 4 channels; 7 for 16-bit elements): 0, or the error code
-static inline int pool_dims_status(int64_t n, int64_t h, int64_t w, int64_t c, int64_t cmask = 3) {
+// n, h, w, c of a pool entry point (kw channels per lane): 0, or the error code
+static inline int pool_dims_status(int64_t n, int64_t h, int64_t w, int64_t c, int kw) {
   if (n <= 0 || h <= 0 || w <= 0 || c <= 0) return MHAQ_FQ_EINVAL;
   // the pixel arithmetic of the kernels is 32-bit: n * h * w < 2^31
-  if ((c & cmask) || c > kBnMaxChannels || h >= (1ll << 31) || w >= (1ll << 31) || n >= (1ll << 31) ||
+  if ((c & (kw - 1)) || c > kBnMaxChannels || h >= (1ll << 31) || w >= (1ll << 31) || n >= (1ll << 31) ||
       n * h >= (1ll << 31) || n * h * w >= (1ll << 31))
     return MHAQ_FQ_EUNSUPPORTED;
   return 0;
+}
+
+// ---------------------------------------------------------------- the host path of the entry points
+// Written once for fp32 and 16-bit elements, told apart by kw, the channels of a lane's 16 bytes (4 or 8): C % kw == 0, and the
+// argmax codes, one byte per channel, are kw-byte aligned.
+// workspace of a backward over [m][c]: 5 fp32 constant rows and 2 fp64 partial rows per row chunk; 0 for an unsupported shape
+static size_t bn_workspace_bytes(int64_t m, int64_t c, int kw) {
+  if (m <= 0 || c <= 0 || (c & (kw - 1)) || c > kBnMaxChannels) return 0;
+  const BnGeom g = kw == 8 ? bn_geom16(m, c) : bn_geom(m, c);
+  return ((size_t)kBnNConst * sizeof(float) + 2 * (size_t)g.nchunks * sizeof(double)) * (size_t)c;
+}
+
+// Status of a backward call before anything is launched, in the order include/mhaq_fq.h promises: required pointers and
+// positive sizes, the dtype (kw == 8), width and range, the workspace, the alignment.  `code` and (h, w) belong to the pool
+// forms (pool); the plain forms pass their m as n.
+static int bn_bwd_status(const BnCall& a, int kw, int dtype, bool pool, const uint8_t* code, int64_t n, int64_t h, int64_t w,
+                         int64_t c) {
+  if (!a.x || !a.src || !a.mean || !a.invstd || !a.workspace || (pool ? !code : n <= 0 || c <= 0)) return MHAQ_FQ_EINVAL;
+  if (kw == 8 && !io16::known_dtype(dtype)) return MHAQ_FQ_EINVAL;
+  if (pool) {
+    if (const int rc = pool_dims_status(n, h, w, c, kw)) return rc;
+  } else if ((c & (kw - 1)) || c > kBnMaxChannels || n > (INT64_MAX >> 3) / c) {
+    return MHAQ_FQ_EUNSUPPORTED;      // a lane owns kw channels; the width bound keeps the dx kernel's column arithmetic in 32 bits
+  }
+  if (a.workspace_bytes < bn_workspace_bytes(n * h * w, c, kw)) return MHAQ_FQ_EWORKSPACE;
+  if (!bn_aligned(a.x, 16) || !bn_aligned(a.src, 16) || !bn_aligned(code, kw) || !bn_aligned(a.dx, 16) ||
+      !bn_aligned(a.workspace, 16) || !bn_aligned(a.mean, 4) || !bn_aligned(a.invstd, 4) || !bn_aligned(a.weight, 4) ||
+      !bn_aligned(a.dweight, 4) || !bn_aligned(a.dbias, 4))
+    return MHAQ_FQ_EALIGN;
+  return 0;
+}
+
+// A pool forward: its status in the same order, then its one launch (T: float or a 16-bit element, 16 / sizeof(T) per lane).
+static int pool_fwd_status(const void* t, const void* p, const uint8_t* code, int kw, int dtype, int64_t n, int64_t h,
+                           int64_t w, int64_t c) {
+  if (!t || !p || !code) return MHAQ_FQ_EINVAL;
+  if (kw == 8 && !io16::known_dtype(dtype)) return MHAQ_FQ_EINVAL;
+  if (const int rc = pool_dims_status(n, h, w, c, kw)) return rc;
+  if (!bn_aligned(t, 16) || !bn_aligned(p, 16) || !bn_aligned(code, kw)) return MHAQ_FQ_EALIGN;
+  return 0;
+}
+template <class T>
+static int pool_fwd_launch(void (*kernel)(const T*, T*, uint8_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int64_t),
+                           const void* t, void* p, uint8_t* code, int64_t n, int64_t h, int64_t w, int64_t c, void* stream) {
+  constexpr int64_t kw = 16 / sizeof(T);
+  const int64_t oh = pool_out(h), ow = pool_out(w), nvec = n * oh * ow * (c / kw);
+  const int64_t grid = (nvec + kBlock - 1) / kBlock;
+  if (grid > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
+  MHAQ_LAUNCH(kernel, dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream, (const T*)t, (T*)p, code, (uint32_t)h,
+              (uint32_t)w, (uint32_t)oh, (uint32_t)ow, (uint32_t)(c / kw), nvec);
+  return launch_status();
 }
 
 }  // namespace mhaq
@@ -737,134 +784,68 @@ using namespace mhaq;
 
 extern "C" {
 
-size_t mhaq_fq_bn_bwd_workspace_bytes(int64_t m, int64_t c) {
-  if (m <= 0 || c <= 0 || (c & 3) || c > kBnMaxChannels) return 0;
-  return ((size_t)kBnNConst * sizeof(float) + 2 * (size_t)bn_geom(m, c).nchunks * sizeof(double)) * (size_t)c;
+size_t mhaq_fq_bn_bwd_workspace_bytes(int64_t m, int64_t c) { return bn_workspace_bytes(m, c, 4); }
+size_t mhaq_fq_bn_bwd_x16_workspace_bytes(int64_t m, int64_t c) { return bn_workspace_bytes(m, c, 8); }
+size_t mhaq_fq_bn_pool_bwd_workspace_bytes(int64_t n, int64_t h, int64_t w, int64_t c) {
+  return pool_dims_status(n, h, w, c, 4) ? 0 : bn_workspace_bytes(n * h * w, c, 4);
+}
+size_t mhaq_fq_bn_pool_bwd_x16_workspace_bytes(int64_t n, int64_t h, int64_t w, int64_t c) {
+  return pool_dims_status(n, h, w, c, 8) ? 0 : bn_workspace_bytes(n * h * w, c, 8);
 }
 
 int mhaq_fq_bn_bwd(const float* x, const float* dy, const float* mean, const float* invstd, const float* weight,
                    float* dx, float* dweight, float* dbias, int64_t m, int64_t c, void* workspace,
                    size_t workspace_bytes, void* stream) {
-  if (m <= 0 || c <= 0 || !x || !dy || !mean || !invstd || !workspace) return MHAQ_FQ_EINVAL;
-  // C % 4: a lane owns 4 channels; the width bound keeps the column arithmetic of the dx kernel in 32 bits
-  if ((c & 3) || c > kBnMaxChannels || m > (INT64_MAX >> 3) / c) return MHAQ_FQ_EUNSUPPORTED;
-  if (workspace_bytes < mhaq_fq_bn_bwd_workspace_bytes(m, c)) return MHAQ_FQ_EWORKSPACE;
-  if (!bn_aligned(x, 16) || !bn_aligned(dy, 16) || !bn_aligned(dx, 16) || !bn_aligned(workspace, 16) ||
-      !bn_aligned(mean, 4) || !bn_aligned(invstd, 4) || !bn_aligned(weight, 4) || !bn_aligned(dweight, 4) ||
-      !bn_aligned(dbias, 4))
-    return MHAQ_FQ_EALIGN;
-  return bn_bwd_launch<DyMem, kBnRedU>(x, DyMem{dy}, mean, invstd, weight, dx, dweight, dbias, m, c, workspace,
-                                       (hipStream_t)stream);
-}
-
-size_t mhaq_fq_bn_bwd_x16_workspace_bytes(int64_t m, int64_t c) {
-  if (m <= 0 || c <= 0 || (c & 7) || c > kBnMaxChannels) return 0;
-  return ((size_t)kBnNConst * sizeof(float) + 2 * (size_t)bn_geom16(m, c).nchunks * sizeof(double)) * (size_t)c;
+  const BnCall a{x, dy, mean, invstd, weight, dx, dweight, dbias, workspace, workspace_bytes, stream};
+  if (const int rc = bn_bwd_status(a, 4, 0, false, nullptr, m, 1, 1, c)) return rc;
+  return bn_bwd_launch<DyMem, kBnRedU>(a, DyMem{dy}, m, c);
 }
 
 int mhaq_fq_bn_bwd_x16(const void* x, const void* dy, const float* mean, const float* invstd, const float* weight, void* dx,
                        float* dweight, float* dbias, int64_t m, int64_t c, int dtype, void* workspace,
                        size_t workspace_bytes, void* stream) {
-  if (m <= 0 || c <= 0 || !x || !dy || !mean || !invstd || !workspace) return MHAQ_FQ_EINVAL;
-  if (dtype != MHAQ_FQ_DT_BF16 && dtype != MHAQ_FQ_DT_F16) return MHAQ_FQ_EINVAL;
-  // C % 8: a lane owns 8 channels
-  if ((c & 7) || c > kBnMaxChannels || m > (INT64_MAX >> 3) / c) return MHAQ_FQ_EUNSUPPORTED;
-  if (workspace_bytes < mhaq_fq_bn_bwd_x16_workspace_bytes(m, c)) return MHAQ_FQ_EWORKSPACE;
-  if (!bn_aligned(x, 16) || !bn_aligned(dy, 16) || !bn_aligned(dx, 16) || !bn_aligned(workspace, 16) ||
-      !bn_aligned(mean, 4) || !bn_aligned(invstd, 4) || !bn_aligned(weight, 4) || !bn_aligned(dweight, 4) ||
-      !bn_aligned(dbias, 4))
-    return MHAQ_FQ_EALIGN;
-  const uint16_t* x16 = (const uint16_t*)x;
-  const uint16_t* dy16 = (const uint16_t*)dy;
-  if (dtype == MHAQ_FQ_DT_BF16)
-    return bn_bwd_launch<DyMem16<MHAQ_FQ_DT_BF16>, kBnRedU>(x16, DyMem16<MHAQ_FQ_DT_BF16>{dy16}, mean, invstd, weight,
-                                                            (uint16_t*)dx, dweight, dbias, m, c, workspace,
-                                                            (hipStream_t)stream);
-  return bn_bwd_launch<DyMem16<MHAQ_FQ_DT_F16>, kBnRedU>(x16, DyMem16<MHAQ_FQ_DT_F16>{dy16}, mean, invstd, weight,
-                                                         (uint16_t*)dx, dweight, dbias, m, c, workspace,
-                                                         (hipStream_t)stream);
+  const BnCall a{x, dy, mean, invstd, weight, dx, dweight, dbias, workspace, workspace_bytes, stream};
+  if (const int rc = bn_bwd_status(a, 8, dtype, false, nullptr, m, 1, 1, c)) return rc;
+  return io16::with_dtype(dtype, [&](auto dt) {
+    using Dy = DyMem16<decltype(dt)::value>;
+    return bn_bwd_launch<Dy, kBnRedU>(a, Dy{(const uint16_t*)dy}, m, c);
+  });
 }
 
 int mhaq_fq_maxpool3s2_fwd(const float* t, float* p, uint8_t* code, int64_t n, int64_t h, int64_t w, int64_t c,
                            void* stream) {
-  if (!t || !p || !code) return MHAQ_FQ_EINVAL;
-  if (const int rc = pool_dims_status(n, h, w, c)) return rc;
-  if (!bn_aligned(t, 16) || !bn_aligned(p, 16) || !bn_aligned(code, 4)) return MHAQ_FQ_EALIGN;
-  const int64_t oh = pool_out(h), ow = pool_out(w), nvec = n * oh * ow * (c >> 2);
-  const int64_t grid = (nvec + kBlock - 1) / kBlock;
-  if (grid > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
-  MHAQ_LAUNCH(maxpool3s2_fwd_kernel, dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream, t, p, code, (uint32_t)h,
-              (uint32_t)w, (uint32_t)oh, (uint32_t)ow, (uint32_t)(c >> 2), nvec);
-  return launch_status();
+  if (const int rc = pool_fwd_status(t, p, code, 4, 0, n, h, w, c)) return rc;
+  return pool_fwd_launch<float>(maxpool3s2_fwd_kernel, t, p, code, n, h, w, c, stream);
 }
 
-size_t mhaq_fq_bn_pool_bwd_workspace_bytes(int64_t n, int64_t h, int64_t w, int64_t c) {
-  if (pool_dims_status(n, h, w, c)) return 0;
-  return mhaq_fq_bn_bwd_workspace_bytes(n * h * w, c);
+int mhaq_fq_maxpool3s2_fwd_x16(const void* t, void* p, uint8_t* code, int64_t n, int64_t h, int64_t w, int64_t c, int dtype,
+                               void* stream) {
+  if (const int rc = pool_fwd_status(t, p, code, 8, dtype, n, h, w, c)) return rc;
+  return io16::with_dtype(dtype, [&](auto dt) {
+    return pool_fwd_launch<uint16_t>(maxpool3s2_fwd16_kernel<decltype(dt)::value>, t, p, code, n, h, w, c, stream);
+  });
 }
 
 int mhaq_fq_bn_pool_bwd(const float* x, const float* g, const uint8_t* code, const float* mean, const float* invstd,
                         const float* weight, float* dx, float* dweight, float* dbias, int64_t n, int64_t h, int64_t w,
                         int64_t c, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!x || !g || !code || !mean || !invstd || !workspace) return MHAQ_FQ_EINVAL;
-  if (const int rc = pool_dims_status(n, h, w, c)) return rc;
-  if (workspace_bytes < mhaq_fq_bn_pool_bwd_workspace_bytes(n, h, w, c)) return MHAQ_FQ_EWORKSPACE;
-  if (!bn_aligned(x, 16) || !bn_aligned(g, 16) || !bn_aligned(code, 4) || !bn_aligned(dx, 16) ||
-      !bn_aligned(workspace, 16) || !bn_aligned(mean, 4) || !bn_aligned(invstd, 4) || !bn_aligned(weight, 4) ||
-      !bn_aligned(dweight, 4) || !bn_aligned(dbias, 4))
-    return MHAQ_FQ_EALIGN;
+  const BnCall a{x, g, mean, invstd, weight, dx, dweight, dbias, workspace, workspace_bytes, stream};
+  if (const int rc = bn_bwd_status(a, 4, 0, true, code, n, h, w, c)) return rc;
   const DyPool src{g, code, (uint32_t)h, (uint32_t)w, (uint32_t)pool_out(h), (uint32_t)pool_out(w)};
-  return bn_bwd_launch<DyPool, kBnPoolRedU>(x, src, mean, invstd, weight, dx, dweight, dbias, n * h * w, c, workspace,
-                                            (hipStream_t)stream);
-}
-
-int mhaq_fq_maxpool3s2_fwd_x16(const void* t, void* p, uint8_t* code, int64_t n, int64_t h, int64_t w, int64_t c, int dtype,
-                               void* stream) {
-  if (!t || !p || !code) return MHAQ_FQ_EINVAL;
-  if (dtype != MHAQ_FQ_DT_BF16 && dtype != MHAQ_FQ_DT_F16) return MHAQ_FQ_EINVAL;
-  if (const int rc = pool_dims_status(n, h, w, c, 7)) return rc;
-  if (!bn_aligned(t, 16) || !bn_aligned(p, 16) || !bn_aligned(code, 8)) return MHAQ_FQ_EALIGN;
-  const int64_t oh = pool_out(h), ow = pool_out(w), nvec = n * oh * ow * (c >> 3);
-  const int64_t grid = (nvec + kBlock - 1) / kBlock;
-  if (grid > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
-  const uint16_t* t16 = (const uint16_t*)t;
-  if (dtype == MHAQ_FQ_DT_BF16)
-    MHAQ_LAUNCH(maxpool3s2_fwd16_kernel<MHAQ_FQ_DT_BF16>, dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream, t16,
-                (uint16_t*)p, code, (uint32_t)h, (uint32_t)w, (uint32_t)oh, (uint32_t)ow, (uint32_t)(c >> 3), nvec);
-  else
-    MHAQ_LAUNCH(maxpool3s2_fwd16_kernel<MHAQ_FQ_DT_F16>, dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream, t16,
-                (uint16_t*)p, code, (uint32_t)h, (uint32_t)w, (uint32_t)oh, (uint32_t)ow, (uint32_t)(c >> 3), nvec);
-  return launch_status();
-}
-
-size_t mhaq_fq_bn_pool_bwd_x16_workspace_bytes(int64_t n, int64_t h, int64_t w, int64_t c) {
-  if (pool_dims_status(n, h, w, c, 7)) return 0;
-  return mhaq_fq_bn_bwd_x16_workspace_bytes(n * h * w, c);
+  return bn_bwd_launch<DyPool, kBnPoolRedU>(a, src, n * h * w, c);
 }
 
 int mhaq_fq_bn_pool_bwd_x16(const void* x, const void* g, const uint8_t* code, const float* mean, const float* invstd,
                             const float* weight, void* dx, float* dweight, float* dbias, int64_t n, int64_t h, int64_t w,
                             int64_t c, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!x || !g || !code || !mean || !invstd || !workspace) return MHAQ_FQ_EINVAL;
-  if (dtype != MHAQ_FQ_DT_BF16 && dtype != MHAQ_FQ_DT_F16) return MHAQ_FQ_EINVAL;
-  if (const int rc = pool_dims_status(n, h, w, c, 7)) return rc;
-  if (workspace_bytes < mhaq_fq_bn_pool_bwd_x16_workspace_bytes(n, h, w, c)) return MHAQ_FQ_EWORKSPACE;
-  if (!bn_aligned(x, 16) || !bn_aligned(g, 16) || !bn_aligned(code, 8) || !bn_aligned(dx, 16) ||
-      !bn_aligned(workspace, 16) || !bn_aligned(mean, 4) || !bn_aligned(invstd, 4) || !bn_aligned(weight, 4) ||
-      !bn_aligned(dweight, 4) || !bn_aligned(dbias, 4))
-    return MHAQ_FQ_EALIGN;
-  const uint16_t* x16 = (const uint16_t*)x;
-  const uint16_t* g16 = (const uint16_t*)g;
-  const uint32_t uh = (uint32_t)h, uw = (uint32_t)w, oh = (uint32_t)pool_out(h), ow = (uint32_t)pool_out(w);
-  const bool plane1 = h == 1 && w == 1;
-  if (dtype == MHAQ_FQ_DT_BF16) {
-    const DyPool16<MHAQ_FQ_DT_BF16> src{g16, code, uh, uw, oh, ow, plane1};
-    return bn_bwd_launch<DyPool16<MHAQ_FQ_DT_BF16>, kBnPool16RedU>(x16, src, mean, invstd, weight, (uint16_t*)dx, dweight, dbias,
-                                                                   n * h * w, c, workspace, (hipStream_t)stream);
-  }
-  const DyPool16<MHAQ_FQ_DT_F16> src{g16, code, uh, uw, oh, ow, plane1};
-  return bn_bwd_launch<DyPool16<MHAQ_FQ_DT_F16>, kBnPool16RedU>(x16, src, mean, invstd, weight, (uint16_t*)dx, dweight, dbias,
-                                                                n * h * w, c, workspace, (hipStream_t)stream);
+  const BnCall a{x, g, mean, invstd, weight, dx, dweight, dbias, workspace, workspace_bytes, stream};
+  if (const int rc = bn_bwd_status(a, 8, dtype, true, code, n, h, w, c)) return rc;
+  return io16::with_dtype(dtype, [&](auto dt) {
+    using Dy = DyPool16<decltype(dt)::value>;
+    const Dy src{(const uint16_t*)g, code, (uint32_t)h, (uint32_t)w, (uint32_t)pool_out(h), (uint32_t)pool_out(w),
+                 h == 1 && w == 1};
+    return bn_bwd_launch<Dy, kBnPool16RedU>(a, src, n * h * w, c);
+  });
 }
 
 }  // extern "C"

@@ -26,9 +26,8 @@
 // kernels above): z + addend is rounded to 16 bits before the ReLU, and the gradient gq is rounded to 16 bits BEFORE g_a is
 // added and the sum is rounded again -- two roundings, as the quantizer's 16-bit gx and autograd's 16-bit add give them.
 // Partial rows, geometry, sign tile and workspace rule are those of x16_act_bwd_kernel on (relu(z), g_y).
-#include <type_traits>
 
-#include "fq_io16.hpp"   // up2 / down2 / ld8 / st8: shared with bn_bwd.hip
+#include "fq_io16.hpp"   // up2 / down2 / ld8 / st8, known_dtype / with_dtype: shared with bn_bwd.hip
 
 namespace mhaq {
 namespace io16 {
@@ -593,7 +592,6 @@ __global__ __launch_bounds__(kFinalThreads) void x16_act_finalize_kernel(const f
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 inline bool aligned2(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 1u) == 0; }
-inline bool known_dtype(int dt) { return dt == MHAQ_FQ_DT_BF16 || dt == MHAQ_FQ_DT_F16; }
 inline int64_t blocks8(int64_t n, int u) {          // blocks of 256 * u lanes x 8 elements
   const int64_t per = (int64_t)kBlock * u;
   const int64_t b = ((n >> 3) + per - 1) / per;
@@ -606,13 +604,8 @@ inline int64_t simple_grid(int64_t n) {            // fq_pt.hip simple_grid
   return b;
 }
 
-// A runtime value as a template argument: f receives it as a std::integral_constant.  The entry points have checked
-// dtype and method before they get here.
-template <class F>
-void with_dtype(int dtype, F f) {
-  if (dtype == MHAQ_FQ_DT_BF16) f(std::integral_constant<int, MHAQ_FQ_DT_BF16>{});
-  else f(std::integral_constant<int, MHAQ_FQ_DT_F16>{});
-}
+// A runtime value as a template argument, as with_dtype (fq_io16.hpp): the entry points have checked the method before
+// they get here.
 template <class F>
 void with_method(int method, F f) {
   switch (method) {

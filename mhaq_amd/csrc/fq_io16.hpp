@@ -2,6 +2,8 @@
 // 16 B per lane = 8 elements per access, exact conversion up, one round-to-nearest-even down.
 #pragma once
 
+#include <type_traits>
+
 #include "fq_common.hpp"
 
 namespace mhaq {
@@ -51,6 +53,15 @@ template <bool NT>
 __device__ __forceinline__ void st8(uint16_t* p, int64_t vidx, vu4 v) {
   vu4* q = reinterpret_cast<vu4*>(p) + vidx;
   if (NT) __builtin_nontemporal_store(v, q); else *q = v;
+}
+
+// ---- host side: the dtype of an *_x16 entry point, checked, and then as a template argument (f receives it as a
+// std::integral_constant and its result is handed back; the entry points have checked the dtype before they get here)
+inline bool known_dtype(int dt) { return dt == MHAQ_FQ_DT_BF16 || dt == MHAQ_FQ_DT_F16; }
+template <class F>
+auto with_dtype(int dtype, F f) {
+  if (dtype == MHAQ_FQ_DT_BF16) return f(std::integral_constant<int, MHAQ_FQ_DT_BF16>{});
+  return f(std::integral_constant<int, MHAQ_FQ_DT_F16>{});
 }
 
 }  // namespace io16

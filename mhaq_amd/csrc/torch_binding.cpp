@@ -689,29 +689,64 @@ std::tuple<Tensor, std::optional<Tensor>, Tensor, Tensor, Tensor> act_relu_layer
 // the call (`x16`): C % 8 == 0, fp32 weight and statistics, and a dy of x's dtype; its dx is the fp32 arithmetic rounded once.
 inline bool aligned16(const Tensor& t) { return (reinterpret_cast<uintptr_t>(t.const_data_ptr()) & 15) == 0; }
 
-inline bool bn_bwd_eligible(const Tensor& x, const Tensor& w, const Tensor& mean, const Tensor& invstd) {
-  if (!x.is_cuda() || x.scalar_type() != at::kFloat || x.dim() != 4 || x.numel() == 0) return false;
-  if (!x.is_contiguous(at::MemoryFormat::ChannelsLast) || (x.size(1) & 3) || !aligned16(x)) return false;
+// What every HIP route asks: x a non-empty dense channels_last device tensor of fp32, bf16 or fp16, 16-byte aligned, C a multiple
+// of the channels in a lane's 16 bytes (4, 8 for 16-bit elements); the statistics (absent before the forward has produced them)
+// and the optional weight fp32, contiguous and of length C.  The 16-bit route adds "dy has x's dtype and sizes", the pooled
+// node "fp32, n * h * w < 2^31 and a weight", at their call sites.
+inline bool bn_hip_eligible(const Tensor& x, const Tensor& w, const Tensor* mean = nullptr, const Tensor* invstd = nullptr) {
+  if (!x.is_cuda() || (x.scalar_type() != at::kFloat && act_dtype(x) == 0) || x.dim() != 4 || x.numel() == 0) return false;
+  if (!x.is_contiguous(at::MemoryFormat::ChannelsLast) || (x.size(1) & (act_dtype(x) ? 7 : 3)) || !aligned16(x)) return false;
   auto stat_ok = [&](const Tensor& t) {
     return t.defined() && t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == x.size(1);
   };
-  return stat_ok(mean) && stat_ok(invstd) && (!w.defined() || stat_ok(w));
-}
-
-// the 16-bit route: as above with 8 channels per 16-byte access; dy (in x's layout) must have x's dtype
-inline bool bn_bwd_x16_eligible(const Tensor& x, const Tensor& dy, const Tensor& w, const Tensor& mean,
-                                const Tensor& invstd) {
-  if (!x.is_cuda() || act_dtype(x) == 0 || x.dim() != 4 || x.numel() == 0) return false;
-  if (!x.is_contiguous(at::MemoryFormat::ChannelsLast) || (x.size(1) & 7) || !aligned16(x)) return false;
-  if (dy.scalar_type() != x.scalar_type() || !dy.is_cuda() || dy.sizes() != x.sizes()) return false;
-  auto stat_ok = [&](const Tensor& t) {
-    return t.defined() && t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == x.size(1);
-  };
-  return stat_ok(mean) && stat_ok(invstd) && (!w.defined() || stat_ok(w));
+  return (!mean || stat_ok(*mean)) && (!invstd || stat_ok(*invstd)) && (!w.defined() || stat_ok(w));
 }
 
 std::atomic<int64_t> g_bn_hip_backwards{0};   // backwards that took mhaq_fq_bn_bwd (tests: the fallback is never silent)
 std::atomic<int64_t> g_bn_hip_backwards_x16{0};   // ... that took mhaq_fq_bn_bwd_x16
+std::atomic<int64_t> g_bn_pool_hip_backwards{0};   // ... that took mhaq_fq_bn_pool_bwd
+
+// One HIP BatchNorm backward of an eligible x: {dx, dweight, dbias} in the first three of `slots` outputs, undefined where the
+// mask says so.  The gradient comes as dy in x's layout or, with `code`, as the pooled gradient in the layout of its argmax
+// codes; the entry point follows from that and from x's dtype.  (The 16-bit pooled form, which the binding does not load,
+// would be one more case.)
+variable_list bn_hip_backward(size_t slots, const Tensor& x, const Tensor& grad, const Tensor& code, const Tensor& w,
+                              const Tensor& mean, const Tensor& invstd, const std::array<bool, 3>& mask) {
+  need_lib();
+  const int64_t n = x.size(0), c = x.size(1), h = x.size(2), wd = x.size(3), m = x.numel() / c;
+  const int dt = act_dtype(x);
+  TORCH_CHECK(!(code.defined() && dt), "bn_hip_backward: there is no 16-bit pooled route");
+  Tensor dx = mask[0] ? at::empty_like(x) : Tensor();
+  Tensor dw = mask[1] ? at::empty_like(w) : Tensor();
+  Tensor db = mask[2] ? at::empty({c}, mean.options()) : Tensor();
+  const size_t nb = code.defined() ? A.mhaq_fq_bn_pool_bwd_workspace_bytes(n, h, wd, c)
+                                   : dt ? A.mhaq_fq_bn_bwd_x16_workspace_bytes(m, c) : A.mhaq_fq_bn_bwd_workspace_bytes(m, c);
+  Tensor ws = at::empty({(int64_t)nb}, x.options().dtype(at::kByte));
+  void* dxp = mask[0] ? dx.mutable_data_ptr() : nullptr;
+  float *dwp = mask[1] ? fptr_mut(dw) : nullptr, *dbp = mask[2] ? fptr_mut(db) : nullptr;
+  if (code.defined()) {
+    check(A.mhaq_fq_bn_pool_bwd(fptr(x), fptr(grad), static_cast<const uint8_t*>(code.const_data_ptr()), fptr(mean),
+                                fptr(invstd), fptr_or_null(w), static_cast<float*>(dxp), dwp, dbp, n, h, wd, c,
+                                ws.mutable_data_ptr(), nb, cur_stream(x)),
+          "mhaq_fq_bn_pool_bwd");
+    g_bn_pool_hip_backwards.fetch_add(1, std::memory_order_relaxed);
+  } else if (dt) {
+    check(A.mhaq_fq_bn_bwd_x16(x.const_data_ptr(), grad.const_data_ptr(), fptr(mean), fptr(invstd), fptr_or_null(w), dxp, dwp,
+                               dbp, m, c, dt, ws.mutable_data_ptr(), nb, cur_stream(x)),
+          "mhaq_fq_bn_bwd_x16");
+    g_bn_hip_backwards_x16.fetch_add(1, std::memory_order_relaxed);
+  } else {
+    check(A.mhaq_fq_bn_bwd(fptr(x), fptr(grad), fptr(mean), fptr(invstd), fptr_or_null(w), static_cast<float*>(dxp), dwp, dbp,
+                           m, c, ws.mutable_data_ptr(), nb, cur_stream(x)),
+          "mhaq_fq_bn_bwd");
+    g_bn_hip_backwards.fetch_add(1, std::memory_order_relaxed);
+  }
+  variable_list out(slots);
+  out[0] = dx;
+  out[1] = dw;
+  out[2] = db;
+  return out;
+}
 
 class BatchNormTrainFn : public torch::autograd::Function<BatchNormTrainFn> {
  public:
@@ -743,58 +778,27 @@ class BatchNormTrainFn : public torch::autograd::Function<BatchNormTrainFn> {
     const Tensor &x = saved[0], &w = saved[1], &mean = saved[2], &invstd = saved[3], &reserve = saved[4];
     const std::array<bool, 3> mask = {ctx->needs_input_grad(0), w.defined() && ctx->needs_input_grad(1),
                                       ctx->needs_input_grad(2)};
-    if (ctx->saved_data["x16"].toBool() && x.is_cuda() && act_dtype(x) != 0 && grads[0].scalar_type() == x.scalar_type() &&
+    // the route: 16-bit where the caller enabled it and dy has x's dtype and sizes, else fp32, else the framework's own backward
+    const bool hip = bn_hip_eligible(x, w, &mean, &invstd);
+    if (hip && act_dtype(x) != 0 && ctx->saved_data["x16"].toBool() && grads[0].scalar_type() == x.scalar_type() &&
         grads[0].sizes() == x.sizes()) {
       const Tensor dy = like_layout(grads[0], x);
-      if (bn_bwd_x16_eligible(x, dy, w, mean, invstd)) {
-        need_lib();
-        const int64_t c = x.size(1), m = x.numel() / c;
-        Tensor dx = mask[0] ? at::empty_like(x) : Tensor();
-        Tensor dw = mask[1] ? at::empty_like(w) : Tensor();
-        Tensor db = mask[2] ? at::empty({c}, mean.options()) : Tensor();
-        const size_t nb = A.mhaq_fq_bn_bwd_x16_workspace_bytes(m, c);
-        Tensor ws = at::empty({(int64_t)nb}, x.options().dtype(at::kByte));
-        check(A.mhaq_fq_bn_bwd_x16(x.const_data_ptr(), dy.const_data_ptr(), fptr(mean), fptr(invstd), fptr_or_null(w),
-                                   mask[0] ? dx.mutable_data_ptr() : nullptr, mask[1] ? fptr_mut(dw) : nullptr,
-                                   mask[2] ? fptr_mut(db) : nullptr, m, c, act_dtype(x), ws.mutable_data_ptr(), nb,
-                                   cur_stream(x)),
-              "mhaq_fq_bn_bwd_x16");
-        g_bn_hip_backwards_x16.fetch_add(1, std::memory_order_relaxed);
-        out[0] = dx;
-        out[1] = dw;
-        out[2] = db;
-        return out;
-      }
+      if (dy.is_cuda()) return bn_hip_backward(9, x, dy, Tensor(), w, mean, invstd, mask);
     }
-    if (!bn_bwd_eligible(x, w, mean, invstd)) {
-      auto opt = [](const Tensor& t) { return t.defined() ? std::optional<Tensor>(t) : std::nullopt; };
-      auto get = [&](const char* k) {
-        return ctx->saved_data.count(k) ? std::optional<Tensor>(ctx->saved_data[k].toTensor()) : std::nullopt;
-      };
-      auto g = at::_batch_norm_impl_index_backward(ctx->saved_data["impl"].toInt(), x, grads[0], opt(w), get("rm"),
-                                                   get("rv"), opt(mean), opt(invstd), /*train=*/true,
-                                                   ctx->saved_data["eps"].toDouble(), mask, reserve);
-      if (mask[0]) out[0] = std::get<0>(g);
-      if (mask[1]) out[1] = std::get<1>(g);
-      if (mask[2]) out[2] = std::get<2>(g);
-      return out;
+    if (hip && x.scalar_type() == at::kFloat) {
+      const Tensor dy = like_layout(grads[0].scalar_type() == at::kFloat ? grads[0] : grads[0].to(at::kFloat), x);
+      return bn_hip_backward(9, x, dy, Tensor(), w, mean, invstd, mask);
     }
-    need_lib();
-    const int64_t c = x.size(1), m = x.numel() / c;
-    const Tensor dy = like_layout(grads[0].scalar_type() == at::kFloat ? grads[0] : grads[0].to(at::kFloat), x);
-    Tensor dx = mask[0] ? at::empty_like(x) : Tensor();
-    Tensor dw = mask[1] ? at::empty_like(w) : Tensor();
-    Tensor db = mask[2] ? at::empty({c}, mean.options()) : Tensor();
-    const size_t nb = A.mhaq_fq_bn_bwd_workspace_bytes(m, c);
-    Tensor ws = at::empty({(int64_t)nb}, x.options().dtype(at::kByte));
-    check(A.mhaq_fq_bn_bwd(fptr(x), fptr(dy), fptr(mean), fptr(invstd), fptr_or_null(w), mask[0] ? fptr_mut(dx) : nullptr,
-                           mask[1] ? fptr_mut(dw) : nullptr, mask[2] ? fptr_mut(db) : nullptr, m, c, ws.mutable_data_ptr(),
-                           nb, cur_stream(x)),
-          "mhaq_fq_bn_bwd");
-    g_bn_hip_backwards.fetch_add(1, std::memory_order_relaxed);
-    out[0] = dx;
-    out[1] = dw;
-    out[2] = db;
+    auto opt = [](const Tensor& t) { return t.defined() ? std::optional<Tensor>(t) : std::nullopt; };
+    auto get = [&](const char* k) {
+      return ctx->saved_data.count(k) ? std::optional<Tensor>(ctx->saved_data[k].toTensor()) : std::nullopt;
+    };
+    auto g = at::_batch_norm_impl_index_backward(ctx->saved_data["impl"].toInt(), x, grads[0], opt(w), get("rm"), get("rv"),
+                                                 opt(mean), opt(invstd), /*train=*/true, ctx->saved_data["eps"].toDouble(),
+                                                 mask, reserve);
+    if (mask[0]) out[0] = std::get<0>(g);
+    if (mask[1]) out[1] = std::get<1>(g);
+    if (mask[2]) out[2] = std::get<2>(g);
     return out;
   }
 };
@@ -816,17 +820,6 @@ Tensor bn_train(const Tensor& x, const std::optional<Tensor>& w, const std::opti
 // of reading a materialized one.  Output, running statistics and the three gradients are the bits of the two nodes run one
 // after the other.  Taken under BatchNormTrainFn's own conditions (and n * h * w < 2^31); outside them bn_pool_train IS
 // that composition.
-inline bool bn_pool_eligible(const Tensor& x, const Tensor& w) {
-  auto stat_ok = [&](const Tensor& t) {
-    return t.defined() && t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == x.size(1);
-  };
-  if (!x.is_cuda() || x.scalar_type() != at::kFloat || x.dim() != 4 || x.numel() == 0) return false;
-  if (!x.is_contiguous(at::MemoryFormat::ChannelsLast) || (x.size(1) & 3) || !aligned16(x)) return false;
-  return x.numel() / x.size(1) < (1ll << 31) && stat_ok(w);
-}
-
-std::atomic<int64_t> g_bn_pool_hip_backwards{0};   // backwards that took mhaq_fq_bn_pool_bwd
-
 class BatchNormPoolTrainFn : public torch::autograd::Function<BatchNormPoolTrainFn> {
  public:
   static Tensor forward(AutogradContext* ctx, const Tensor& x, const Tensor& w, const Tensor& b,
@@ -835,7 +828,7 @@ class BatchNormPoolTrainFn : public torch::autograd::Function<BatchNormPoolTrain
     auto out = at::_batch_norm_impl_index(x, w, b, running_mean, running_var, /*training=*/true, momentum, eps,
                                           cudnn_enabled);
     const Tensor &mean = std::get<1>(out), &invstd = std::get<2>(out);
-    TORCH_CHECK(bn_bwd_eligible(x, w, mean, invstd), "bn_pool_train: the BatchNorm forward left statistics the HIP "
+    TORCH_CHECK(bn_hip_eligible(x, w, &mean, &invstd), "bn_pool_train: the BatchNorm forward left statistics the HIP "
                 "backward cannot read (there is no fallback behind this point)");
     const Tensor t = std::get<0>(out).contiguous(at::MemoryFormat::ChannelsLast);
     const int64_t n = x.size(0), c = x.size(1), h = x.size(2), wd = x.size(3);
@@ -858,8 +851,6 @@ class BatchNormPoolTrainFn : public torch::autograd::Function<BatchNormPoolTrain
     auto saved = ctx->get_saved_variables();
     const Tensor &x = saved[0], &w = saved[1], &mean = saved[2], &invstd = saved[3], &code = saved[4];
     const std::array<bool, 3> mask = {ctx->needs_input_grad(0), ctx->needs_input_grad(1), ctx->needs_input_grad(2)};
-    need_lib();
-    const int64_t n = x.size(0), c = x.size(1), h = x.size(2), wd = x.size(3);
     // the pooled gradient in the memory order of the pooled tensor (= the codes')
     Tensor g = grads[0].scalar_type() == at::kFloat ? grads[0] : grads[0].to(at::kFloat);
     if (g.sizes() != code.sizes() || g.strides() != code.strides()) {
@@ -867,20 +858,7 @@ class BatchNormPoolTrainFn : public torch::autograd::Function<BatchNormPoolTrain
       dense.copy_(g);
       g = dense;
     }
-    Tensor dx = mask[0] ? at::empty_like(x) : Tensor();
-    Tensor dw = mask[1] ? at::empty_like(w) : Tensor();
-    Tensor db = mask[2] ? at::empty({c}, mean.options()) : Tensor();
-    const size_t nb = A.mhaq_fq_bn_pool_bwd_workspace_bytes(n, h, wd, c);
-    Tensor ws = at::empty({(int64_t)nb}, x.options().dtype(at::kByte));
-    check(A.mhaq_fq_bn_pool_bwd(fptr(x), fptr(g), static_cast<const uint8_t*>(code.const_data_ptr()), fptr(mean),
-                                fptr(invstd), fptr(w), mask[0] ? fptr_mut(dx) : nullptr, mask[1] ? fptr_mut(dw) : nullptr,
-                                mask[2] ? fptr_mut(db) : nullptr, n, h, wd, c, ws.mutable_data_ptr(), nb, cur_stream(x)),
-          "mhaq_fq_bn_pool_bwd");
-    g_bn_pool_hip_backwards.fetch_add(1, std::memory_order_relaxed);
-    out[0] = dx;
-    out[1] = dw;
-    out[2] = db;
-    return out;
+    return bn_hip_backward(8, x, g, code, w, mean, invstd, mask);
   }
 };
 
@@ -890,7 +868,8 @@ Tensor bn_pool_train(const Tensor& x, const std::optional<Tensor>& w, const std:
   TORCH_CHECK(w.has_value() && w->defined() && b.has_value() && b->defined(),
               "bn_pool_train: an affine BatchNorm (weight and bias) is required");
   MHAQ_ON_DEVICE_OF(x);
-  if (!bn_pool_eligible(x, *w))
+  // the fused node: fp32, with the 32-bit pixel arithmetic of its kernels (n * h * w < 2^31)
+  if (!(bn_hip_eligible(x, *w) && x.scalar_type() == at::kFloat && x.numel() / x.size(1) < (1ll << 31)))
     return at::max_pool2d(BatchNormTrainFn::apply(x, w, b, running_mean, running_var, momentum, eps, cudnn_enabled,
                                                   /*x16=*/false),
                           {3, 3}, {2, 2}, {1, 1});

@@ -63,6 +63,23 @@ def test_argument_errors_are_returned_before_any_launch(L):
     assert call(fake, fake, fake, fake, None, None, None, None, 64, 8, fake, nb, None) == 0
 
 
+def test_argument_errors_come_in_a_fixed_order(L):
+    """Several things wrong at once: NULL / size first, then the width, then the workspace, then the alignment."""
+    fake, odd = ctypes.c_void_p(0x1000), ctypes.c_void_p(0x1004)
+    nb = L.mhaq_fq_bn_bwd_workspace_bytes(64, 8)
+    call = L.mhaq_fq_bn_bwd
+
+    def with_(x=fake, dy=odd, m=64, c=6, ws=fake, nbytes=0):
+        return call(x, dy, fake, fake, fake, fake, fake, fake, m, c, ws, nbytes, None)
+    assert with_(x=None) == -1 and with_(m=0) == -1 and with_(ws=None) == -1
+    assert with_(c=0) == -1 and with_(c=-4) == -1
+    assert with_() == -4                                          # C % 4 before the workspace and the alignment
+    assert with_(m=4, c=1 << 23) == -4 and with_(m=1 << 60, c=8) == -4
+    assert with_(c=8) == -2                                       # the workspace before the alignment
+    assert with_(c=8, nbytes=nb - 1) == -2
+    assert with_(c=8, nbytes=nb) == -3
+
+
 def _net():
     torch.manual_seed(0)
     return nn.Sequential(nn.Conv2d(3, 8, 3, padding=1), nn.BatchNorm2d(8), nn.ReLU(),

@@ -92,6 +92,31 @@ def test_argument_errors_are_returned_before_any_launch(L):
     assert fwd(fake, fake, fake, 1 << 11, 1 << 10, 1 << 10, 8, None) == -4
 
 
+def test_argument_errors_come_in_a_fixed_order(L):
+    """Several things wrong at once: NULL first, then the dimensions, then the workspace, then the alignment."""
+    fake, odd = ctypes.c_void_p(0x1000), ctypes.c_void_p(0x1004)
+    n, h, w = 2, 5, 4
+    nb = L.mhaq_fq_bn_pool_bwd_workspace_bytes(n, h, w, 8)
+
+    def bwd(x=fake, g=odd, n=n, c=6, nbytes=0):
+        return L.mhaq_fq_bn_pool_bwd(x, g, fake, fake, fake, fake, fake, fake, fake, n, h, w, c, fake, nbytes, None)
+    assert bwd(x=None) == -1
+    assert bwd(n=0) == -1 and bwd(c=0) == -1                      # a size that is not positive before one that is unsupported
+    assert bwd() == -4                                            # C % 4 before the workspace and the alignment
+    assert bwd(n=1 << 31, c=8) == -4
+    assert bwd(c=8) == -2                                         # the workspace before the alignment
+    assert bwd(c=8, nbytes=nb - 1) == -2
+    assert bwd(c=8, nbytes=nb) == -3
+
+    def fwd(t=fake, p=odd, n=n, c=6):
+        return L.mhaq_fq_maxpool3s2_fwd(t, p, fake, n, h, w, c, None)
+    assert fwd(t=None) == -1
+    assert fwd(n=0) == -1 and fwd(c=0) == -1
+    assert fwd() == -4                                            # C % 4 before the alignment
+    assert fwd(n=1 << 31, c=8) == -4
+    assert fwd(c=8) == -3
+
+
 def test_switches(monkeypatch):
     from mhaq_amd.qat import QATConfig
     assert QATConfig().fuse_stem_pool is True
