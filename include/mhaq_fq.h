@@ -314,6 +314,34 @@ int mhaq_fq_bn_bwd(const float* x, const float* dy, const float* mean, const flo
                    void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Forward of training-mode BatchNorm on the same tensors (fp32).  Additive to ABI v4 -- MHAQ_FQ_ABI_VERSION stays 4; a
+ * caller discovers these entry points by symbol.
+ *   x, y            dense fp32 NHWC seen as [m][c]; m >= 2 (the unbiased variance), c % 4 == 0 and c <= 2^22 (else
+ *                   MHAQ_FQ_EUNSUPPORTED); x, y and `workspace` 16-byte aligned (else MHAQ_FQ_EALIGN).  y == NULL skips the
+ *                   third launch (statistics only).
+ *   weight, bias    [c]; NULL = 1 and NULL = 0
+ *   save_mean, save_invstd      [c], required: what mhaq_fq_bn_bwd reads
+ *   running_mean, running_var   [c], both given or both NULL (one of them alone: MHAQ_FQ_EINVAL); NULL skips the update
+ * Argument errors are returned before any launch, with mhaq_fq_bn_bwd's codes in its order: required pointers and positive
+ * sizes (MHAQ_FQ_EINVAL), width and range (MHAQ_FQ_EUNSUPPORTED), the workspace (MHAQ_FQ_EWORKSPACE), the alignment.
+ * Arithmetic: with k = x[row 0][.] as a per-channel shift, S1 = sum (x - k) and S2 = sum (x - k)^2 are fixed-order fp64 sums
+ * of exact fp64 terms (x read once); in fp64, each result rounded to fp32 ONCE:
+ *   mean = k + S1 / m        var = max(S2 / m - (S1 / m)^2, 0)  (biased)        invstd = (var + eps)^-1/2
+ *   running_mean = (1 - factor) * running_mean + factor * mean
+ *   running_var  = (1 - factor) * running_var  + factor * var * m / (m - 1)
+ * and, in fp32, in this order, without contraction, with a = weight * save_invstd (an fp32 product):
+ *   y = (x - save_mean) * a + bias
+ * A constant channel gives mean = the constant, var = 0 and y = bias exactly; a channel that holds a NaN or an infinity is NaN
+ * in every element of y and in its statistics.  Three launches, deterministic (y, the statistics and every byte of the
+ * workspace), no float atomics.  Stream-ordered, capture-safe, stateless.
+ * ---------------------------------------------------------------------- */
+size_t mhaq_fq_bn_fwd_workspace_bytes(int64_t m, int64_t c);
+int mhaq_fq_bn_fwd(const float* x, const float* weight, const float* bias, float* y,
+                   float* save_mean, float* save_invstd, float* running_mean, float* running_var,
+                   double factor, double eps, int64_t m, int64_t c,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * The same on 16-bit tensors (the BatchNorm behind a convolution under torch.autocast).  Additive to ABI v4 --
  * MHAQ_FQ_ABI_VERSION stays 4; a caller discovers these entry points by symbol.
  *   x, dy, dx       dense NHWC seen as [m][c], of the type named by `dtype` (MHAQ_FQ_DT_BF16 or MHAQ_FQ_DT_F16, anything else:

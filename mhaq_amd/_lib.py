@@ -57,6 +57,9 @@ SIGNATURES = {
     # training BatchNorm backward from the saved statistics (additive, ABI v4 kept)
     "mhaq_fq_bn_bwd_workspace_bytes": (_sz, [_i64, _i64]),
     "mhaq_fq_bn_bwd": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _sz, _p]),
+    # training BatchNorm forward, fp32: statistics, running statistics and y (additive, ABI v4 kept)
+    "mhaq_fq_bn_fwd_workspace_bytes": (_sz, [_i64, _i64]),
+    "mhaq_fq_bn_fwd": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_double, _i64, _i64, _p, _sz, _p]),
     # ... and on 16-bit tensors: `dtype` after c, its own workspace query (additive, ABI v4 kept)
     "mhaq_fq_bn_bwd_x16_workspace_bytes": (_sz, [_i64, _i64]),
     "mhaq_fq_bn_bwd_x16": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _int, _p, _sz, _p]),

@@ -25,6 +25,13 @@ forward_pooled() is the same module with the ResNet stem's max pool behind it in
 it; csrc/torch_binding.cpp, BatchNormPoolTrainFn): same forward bits, and a backward that never materializes the pool's
 gradient.  float32 only (takes_pooled_node): a 16-bit stem stays maxpool(bn(c)), with the 16-bit backward above where enabled.
 
+HIP forward.  install(model, hip_forward=True) also runs the FORWARD of a float32 input on the kernels of csrc/bn_bwd.hip
+(mhaq_fq_bn_fwd: shifted fp64 sums, statistics rounded once, y = (x - mean) * (gamma * invstd) + beta); the node falls back to
+the framework's forward, bit for bit, where that does not apply (NCHW, C % 4 != 0).  16-bit inputs keep the framework's
+forward.  OFF by default -- it changes the bits of y and of the saved and running statistics --:
+QATConfig.hip_bn_forward=True switches it on per trainer, MHAQ_BN_FORWARD=1 in the environment for an unchanged benchmark,
+with the semantics of MHAQ_BN_BACKWARD_X16.
+
 MHAQ_BN_BACKWARD=0 in the environment keeps QATTrainer from installing (A/B runs of an unchanged benchmark);
 QATConfig.hip_bn_backward=False does the same per trainer.
 """
@@ -37,7 +44,9 @@ from torch import nn
 
 ENV_SWITCH = "MHAQ_BN_BACKWARD"
 ENV_SWITCH_X16 = "MHAQ_BN_BACKWARD_X16"
+ENV_SWITCH_FORWARD = "MHAQ_BN_FORWARD"
 _X16 = "_mhaq_bn_x16"          # per-module flag in the instance __dict__ (not a parameter, buffer or state_dict entry)
+_HIP_FWD = "_mhaq_bn_hip_forward"      # likewise
 
 
 def enabled_by_env() -> bool:
@@ -48,7 +57,17 @@ def enabled_by_env() -> bool:
 def x16_enabled(configured: bool = False) -> bool:
     """The 16-bit route's switch: `configured` (QATConfig.hip_bn_backward_16bit) unless MHAQ_BN_BACKWARD_X16 is set, which
     then decides: "1" / "true" / "on" / "yes" enable it, anything else disables it."""
-    v = os.environ.get(ENV_SWITCH_X16)
+    return _env_or(ENV_SWITCH_X16, configured)
+
+
+def hip_forward_enabled(configured: bool = False) -> bool:
+    """The HIP forward's switch: `configured` (QATConfig.hip_bn_forward) unless MHAQ_BN_FORWARD is set, which then decides,
+    as in x16_enabled()."""
+    return _env_or(ENV_SWITCH_FORWARD, configured)
+
+
+def _env_or(name: str, configured: bool) -> bool:
+    v = os.environ.get(name)
     if v is None or not v.strip():
         return bool(configured)
     return v.strip().lower() in ("1", "true", "on", "yes")
@@ -67,6 +86,10 @@ class HipBackwardBatchNorm2d(nn.BatchNorm2d):
     def takes_x16(self) -> bool:
         """True when install(..., x16=True) enabled the 16-bit backward for this module."""
         return bool(self.__dict__.get(_X16, False))
+
+    def takes_hip_forward(self) -> bool:
+        """True when install(..., hip_forward=True) enabled the HIP forward (of float32 inputs) for this module."""
+        return bool(self.__dict__.get(_HIP_FWD, False))
 
     def takes_pooled_node(self, input) -> bool:
         """True when forward_pooled() applies: the pooled node's kernels are float32."""
@@ -93,24 +116,27 @@ class HipBackwardBatchNorm2d(nn.BatchNorm2d):
         if not self.takes_node(input):
             return super().forward(input)
         from . import _ext
-        return self._node(_ext.ext().bn_train, input, input.dtype != torch.float32)
+        x16 = input.dtype != torch.float32
+        return self._node(_ext.ext().bn_train, input, x16, not x16 and self.takes_hip_forward())
 
     def forward_pooled(self, input):
         """max_pool2d(self(input), 3, 2, 1) as one node (bn_pool_train: the BatchNorm output is not kept, the backward
         gathers its dy from the pooled gradient).  Call only when takes_pooled_node(input) holds."""
         from . import _ext
-        return self._node(_ext.ext().bn_pool_train, input)
+        return self._node(_ext.ext().bn_pool_train, input, input.dtype == torch.float32 and self.takes_hip_forward())
 
 
-def install(model: nn.Module, x16: bool = False) -> int:
+def install(model: nn.Module, x16: bool = False, hip_forward: bool = False) -> int:
     """Give every nn.BatchNorm2d of `model` (the exact type) the forward above; x16=True also enables the 16-bit backward
-    on them.  Returns the number of modules switched."""
+    on them, hip_forward=True the HIP forward of float32 inputs.  Returns the number of modules switched."""
     switched = 0
     for m in model.modules():
         if type(m) is nn.BatchNorm2d:
             m.__class__ = HipBackwardBatchNorm2d
             if x16:
                 m.__dict__[_X16] = True
+            if hip_forward:
+                m.__dict__[_HIP_FWD] = True
             switched += 1
     return switched
 
@@ -120,3 +146,4 @@ def uninstall(model: nn.Module) -> None:
         if type(m) is HipBackwardBatchNorm2d:
             m.__class__ = nn.BatchNorm2d
             m.__dict__.pop(_X16, None)
+            m.__dict__.pop(_HIP_FWD, None)

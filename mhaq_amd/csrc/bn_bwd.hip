@@ -1,8 +1,8 @@
 // Backward of training-mode BatchNorm for gfx950, dense NHWC seen as [M = N*H*W][C]: fp32 with C % 4 == 0, or bf16 / fp16
 // with C % 8 == 0 (a lane owns 16 bytes of a row either way).
 //
-// The forward stays with the framework (it saves the batch mean and invstd); this file replaces the three launches of
-// its backward with three bandwidth-bound ones:
+// By default the forward stays with the framework (it saves the batch mean and invstd; the opt-in mhaq_fq_bn_fwd, fp32, is
+// further down: "the training forward"); this file replaces the three launches of its backward with three bandwidth-bound ones:
 //   bn_bwd_reduce_kernel     one read of x and dy   -> per-block fp64 partial rows of  sum dy  and  sum dy * (x - mean)
 //   bn_bwd_finalize_kernel   fixed-order fp64 sum of the partial rows -> dbias, dweight, per-channel constants
 //   bn_bwd_dx_kernel         a 2R1W stream in the shape of pt_bwd_kernel (fq_pt.hip):
@@ -604,6 +604,250 @@ static int bn_bwd_launch(const BnCall& a, const Dy dy, int64_t m, int64_t c) {
   return launch_status();
 }
 
+// ---------------------------------------------------------------- the training forward (mhaq_fq_bn_fwd)
+// The sibling of the three launches above, over the same partition:
+//   bn_fwd_reduce_kernel     one read of x -> per-block fp64 partial rows of  sum (x - k)  and  sum (x - k)^2
+//   bn_fwd_finalize_kernel   fixed-order fp64 sum of the partial rows -> mean, invstd, the running statistics, the constants
+//   bn_fwd_norm_kernel       a 1R1W stream in the shape of bn_bwd_dx_kernel:  y = (x - mean) * (gamma * invstd) + beta
+// k is a per-channel shift, the same for every block: x[row 0][c].  x - k is exact in fp64, and with the shift the
+// cancellation in E[(x - k)^2] - (E[x - k])^2 is bounded whatever the mean: k is one of the M samples, so
+// (mean - k)^2 <= (M - 1) var.  (Unshifted, a channel at 1e4 +- 1 loses eight digits of its variance.)  A constant channel
+// sums exact zeros: mean = k, var = 0, y = beta.  As in the backward the mean is not folded into an additive constant.
+// Workspace: consts[3][C] = {mean, gamma * invstd, beta} and shift[C] (fp32), then partials[chunk][2][C] (fp64).
+// The cache policy of the two reads of x, each overridable at build time (tools/bn_fwd_bench.py times builds with a forced
+// policy next to the product's): the byte-equivalent of the backward's rule -- one fp32 stream instead of two fits the
+// Infinity Cache up to twice the element count.
+#ifndef MHAQ_BN_FWD_REDUCE_NT_ELEMS
+#define MHAQ_BN_FWD_REDUCE_NT_ELEMS (56ll << 20)
+#endif
+#ifndef MHAQ_BN_FWD_NORM_NT_ELEMS
+#define MHAQ_BN_FWD_NORM_NT_ELEMS (56ll << 20)
+#endif
+constexpr int64_t kBnFwdReduceNtElems = MHAQ_BN_FWD_REDUCE_NT_ELEMS;
+constexpr int64_t kBnFwdNormNtElems = MHAQ_BN_FWD_NORM_NT_ELEMS;
+constexpr int kBnFwdNConst = 3;       // per-channel constants of the norm kernel: mean, gamma * invstd, beta
+constexpr int kBnFwdRows32 = kBnFwdNConst + 1;      // fp32 rows at the head of the workspace: the constants and the shift
+
+// partials[chunk][2][C] (fp64): row 0 = sum (x - k), row 1 = sum (x - k)^2 over the chunk's rows; the blocks of the first
+// row chunk leave k in shift[C].  Partition, clamped loads and the block sum are bn_bwd_reduce_kernel's.
+template <bool NT, class IO, int U>
+__global__ __launch_bounds__(kBlock) void bn_fwd_reduce_kernel(
+    const typename IO::T* __restrict__ x, float* __restrict__ shift, double* __restrict__ partials, int64_t m, int cv,
+    int64_t rows) {
+  constexpr int K = IO::kW;
+  const int c0 = (int)blockIdx.y * kBnCols;
+  const int cols = (cv - c0) < kBnCols ? (cv - c0) : kBnCols;
+  const int rpp = kBlock / cols;
+  const int ty = (int)(threadIdx.x / (uint32_t)cols), tx = (int)threadIdx.x - ty * cols;
+  const bool live = ty < rpp;
+  const int64_t row0 = (int64_t)blockIdx.x * rows;
+  const int64_t rend = (row0 + rows < m) ? row0 + rows : m;
+  const int64_t colv = c0 + tx;
+  float kf[K];
+  IO::unpack(IO::template ld<false>(x, colv), kf);             // row 0 of the tensor: every block reads the same shift
+  if (blockIdx.x == 0 && ty == 0) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) shift[colv * K + j] = kf[j];
+  }
+  double s1[K] = {}, s2[K] = {};
+  for (int64_t rb = row0 + ty; rb - ty < rend; rb += (int64_t)rpp * U) {
+    typename IO::Vec a[U];
+    bool ok[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t r = rb + (int64_t)u * rpp;
+      ok[u] = live && r < rend;
+      a[u] = IO::template ld<NT>(x, (ok[u] ? r : rend - 1) * cv + colv);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      float av[K];
+      IO::unpack(a[u], av);
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        const double d = ok[u] ? (double)av[j] - (double)kf[j] : 0.0;      // a select: a dropped NaN stays dropped
+        s1[j] += d;
+        s2[j] = fma(d, d, s2[j]);
+      }
+    }
+  }
+  __shared__ __align__(16) double sm[kBlock * 2 * K];
+  const int w = K * cols;
+  if (live) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      sm[(ty * 2 + 0) * w + tx * K + j] = s1[j];
+      sm[(ty * 2 + 1) * w + tx * K + j] = s2[j];
+    }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < 2 * w) {
+    const int k = (int)threadIdx.x >= w ? 1 : 0, c = (int)threadIdx.x - k * w;
+    double tot = 0.0;
+    for (int r = 0; r < rpp; ++r) tot += sm[(r * 2 + k) * w + c];
+    partials[((int64_t)blockIdx.x * 2 + k) * ((int64_t)cv * K) + (int64_t)c0 * K + c] = tot;
+  }
+}
+
+// One block per group of 4 channels, the sums as in bn_bwd_finalize_kernel.  Everything is fp64 and every result is rounded
+// to fp32 ONCE:  mean = k + S1 / M,  var = max(S2 / M - (S1 / M)^2, 0) (biased; a NaN stays a NaN),  invstd = (var + eps)^-1/2;
+// running_mean = R32((1 - f) running_mean + f mean),  running_var = R32((1 - f) running_var + f var M / (M - 1)).
+__global__ __launch_bounds__(kBlock) void bn_fwd_finalize_kernel(
+    const double* __restrict__ partials, int nchunks, int c, const float* __restrict__ shift,
+    const float* __restrict__ weight, const float* __restrict__ bias, double m, double factor, double eps,
+    float* __restrict__ consts, float* __restrict__ save_mean, float* __restrict__ save_invstd,
+    float* __restrict__ running_mean, float* __restrict__ running_var) {
+  const int ch = (int)blockIdx.x * 4;
+  double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int i = threadIdx.x; i < nchunks; i += kBlock) {
+    const double* p0 = partials + ((int64_t)i * 2 + 0) * c + ch;
+    const double* p1 = partials + ((int64_t)i * 2 + 1) * c + ch;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      v[j] += p0[j];
+      v[4 + j] += p1[j];
+    }
+  }
+  __shared__ double sm[8 * (kBlock / 64)];
+  block_sum<8>(v, sm);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const double e1 = v[j] / m, e2 = v[4 + j] / m;
+      const double d = e2 - e1 * e1;
+      const double var = d < 0.0 ? 0.0 : d;                     // (not fmax: a NaN stays)
+      const double mean = (double)shift[ch + j] + e1;
+      const float mean32 = (float)mean, is32 = (float)(1.0 / sqrt(var + eps));
+      save_mean[ch + j] = mean32;
+      save_invstd[ch + j] = is32;
+      consts[0 * c + ch + j] = mean32;
+      consts[1 * c + ch + j] = (weight ? weight[ch + j] : 1.0f) * is32;
+      consts[2 * c + ch + j] = bias ? bias[ch + j] : 0.0f;
+      if (running_mean) {
+        running_mean[ch + j] = (float)((1.0 - factor) * (double)running_mean[ch + j] + factor * mean);
+        running_var[ch + j] = (float)((1.0 - factor) * (double)running_var[ch + j] + factor * (var * m / (m - 1.0)));
+      }
+    }
+  }
+}
+
+// y = (x - mean) * a + beta in fp32, in this order (the build contracts nothing).  Block, loads and the column arithmetic of
+// the constants are bn_bwd_dx_kernel's; occupancy by size likewise.
+template <class IO>
+constexpr int kBnFwdWaves = IO::kW == 8 ? 6 : 8;
+template <bool NT, bool BIG, class IO>
+__global__ __attribute__((amdgpu_waves_per_eu(
+    (BIG ? 1 : kBnFwdWaves<IO>), (BIG && kBnBigMaxWaves < kBnFwdWaves<IO> ? kBnBigMaxWaves : kBnFwdWaves<IO>))))
+__launch_bounds__(kBlock) void bn_fwd_norm_kernel(
+    const typename IO::T* __restrict__ x, typename IO::T* __restrict__ y, int64_t nvec, int cv,
+    const float* __restrict__ consts) {
+  constexpr int K = IO::kW;
+  const int64_t blk0 = (int64_t)blockIdx.x * (kBlock * kBnDxU);
+  const int64_t base = blk0 + threadIdx.x;
+  const bool full = blk0 + kBlock * kBnDxU <= nvec;
+  typename IO::Vec a[kBnDxU];
+#pragma unroll
+  for (int u = 0; u < kBnDxU; ++u) {
+    const int64_t idx = base + u * kBlock;
+    a[u] = IO::template ld<NT>(x, (full || idx < nvec) ? idx : nvec - 1);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  const uint32_t ucv = (uint32_t)cv;
+  const uint32_t cb = ((blockIdx.x % ucv) * ((uint32_t)(kBlock * kBnDxU) % ucv)) % ucv;      // wave-uniform
+  const uint32_t step = (uint32_t)kBlock % ucv;                                               // wave-uniform
+  uint32_t col = (cb + threadIdx.x) % ucv;
+  const int64_t c = (int64_t)cv * K;
+  float k[kBnFwdNConst][K / 4][4];
+#pragma unroll
+  for (int u = 0; u < kBnDxU; ++u) {
+    const int64_t idx = base + u * kBlock;
+    if (u > 0) {
+      col += step;
+      if (col >= ucv) col -= ucv;
+    }
+    if (u == 0 || step != 0) {
+#pragma unroll
+      for (int q = 0; q < kBnFwdNConst; ++q)
+#pragma unroll
+        for (int h = 0; h < K / 4; ++h) ldv<4>(consts + q * c + (int64_t)col * K + 4 * h, k[q][h]);
+    }
+    if (full || idx < nvec) {
+      float xv[K], o[K];
+      IO::unpack(a[u], xv);
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        const int h = j >> 2, i = j & 3;
+        o[j] = (xv[j] - k[0][h][i]) * k[1][h][i] + k[2][h][i];
+      }
+      IO::st(y, idx, o);
+    }
+  }
+}
+
+struct BnFwdCall {
+  const void* x;
+  const float *weight, *bias;
+  void* y;
+  float *save_mean, *save_invstd, *running_mean, *running_var;
+  double factor, eps;
+  void* workspace;
+  size_t workspace_bytes;
+  void* stream;
+};
+
+// workspace of a forward over [m][c]: 4 fp32 rows and 2 fp64 partial rows per row chunk; 0 for an unsupported shape
+static size_t bn_fwd_workspace_bytes(int64_t m, int64_t c, int kw) {
+  if (m < 2 || c <= 0 || (c & (kw - 1)) || c > kBnMaxChannels) return 0;
+  const BnGeom g = kw == 8 ? bn_geom16(m, c) : bn_geom(m, c);
+  return ((size_t)kBnFwdRows32 * sizeof(float) + 2 * (size_t)g.nchunks * sizeof(double)) * (size_t)c;
+}
+
+// Status of a forward call before anything is launched, in bn_bwd_status's order: required pointers and positive sizes, width
+// and range (m == 1 has no unbiased variance), the workspace, the alignment.
+static int bn_fwd_status(const BnFwdCall& a, int kw, int64_t m, int64_t c) {
+  if (!a.x || !a.save_mean || !a.save_invstd || !a.workspace || m <= 0 || c <= 0 || !a.running_mean != !a.running_var)
+    return MHAQ_FQ_EINVAL;
+  if ((c & (kw - 1)) || c > kBnMaxChannels || m > (INT64_MAX >> 3) / c || m < 2) return MHAQ_FQ_EUNSUPPORTED;
+  if (a.workspace_bytes < bn_fwd_workspace_bytes(m, c, kw)) return MHAQ_FQ_EWORKSPACE;
+  if (!bn_aligned(a.x, 16) || !bn_aligned(a.y, 16) || !bn_aligned(a.workspace, 16) || !bn_aligned(a.weight, 4) ||
+      !bn_aligned(a.bias, 4) || !bn_aligned(a.save_mean, 4) || !bn_aligned(a.save_invstd, 4) ||
+      !bn_aligned(a.running_mean, 4) || !bn_aligned(a.running_var, 4))
+    return MHAQ_FQ_EALIGN;
+  return 0;
+}
+
+// The three launches (arguments checked by bn_fwd_status).
+template <class IO>
+static int bn_fwd_launch(const BnFwdCall& a, int64_t m, int64_t c) {
+  const typename IO::T* x = (const typename IO::T*)a.x;
+  typename IO::T* y = (typename IO::T*)a.y;
+  hipStream_t st = (hipStream_t)a.stream;
+  const BnGeom g = bn_geom_io<IO>(m, c);
+  const int64_t nvec = m * (c / IO::kW);
+  const int64_t grid = (nvec + kBlock * kBnDxU - 1) / (kBlock * kBnDxU);
+  if (g.nchunks > 0x7fffffff || grid > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
+  float* consts = (float*)a.workspace;
+  float* shift = consts + kBnFwdNConst * c;
+  double* parts = (double*)(consts + kBnFwdRows32 * c);     // 16 * c bytes in: 16-byte aligned
+  const int cv = (int)(c / IO::kW);
+  const bool nt_r = m * c >= kBnFwdReduceNtElems, nt_n = m * c >= kBnFwdNormNtElems, big = m * c >= kBnBigElems;
+  const dim3 rgrid((unsigned)g.nchunks, (unsigned)g.ncol);
+  MHAQ_LAUNCH((nt_r ? bn_fwd_reduce_kernel<true, IO, kBnRedU> : bn_fwd_reduce_kernel<false, IO, kBnRedU>), rgrid,
+              dim3(kBlock), 0, st, x, shift, parts, m, cv, g.rows);
+  int rc = launch_status();
+  if (rc) return rc;
+  MHAQ_LAUNCH(bn_fwd_finalize_kernel, dim3((unsigned)(c >> 2)), dim3(kBlock), 0, st, (const double*)parts, (int)g.nchunks,
+              (int)c, (const float*)shift, a.weight, a.bias, (double)m, a.factor, a.eps, consts, a.save_mean, a.save_invstd,
+              a.running_mean, a.running_var);
+  rc = launch_status();
+  if (rc || !y) return rc;
+  MHAQ_LAUNCH((big ? (nt_n ? bn_fwd_norm_kernel<true, true, IO> : bn_fwd_norm_kernel<false, true, IO>)
+                   : (nt_n ? bn_fwd_norm_kernel<true, false, IO> : bn_fwd_norm_kernel<false, false, IO>)),
+              dim3((unsigned)grid), dim3(kBlock), 0, st, x, y, nvec, cv, (const float*)consts);
+  return launch_status();
+}
+
 // ---------------------------------------------------------------- the pool's forward: values and argmax codes
 // max_pool2d(kernel 3, stride 2, padding 1) of a dense fp32 NHWC tensor: one lane per float4 of the output.  The selection
 // is the framework's channels_last kernel's: the window's in-range positions in kh, then kw order, starting at -inf and
@@ -799,6 +1043,17 @@ int mhaq_fq_bn_bwd(const float* x, const float* dy, const float* mean, const flo
   const BnCall a{x, dy, mean, invstd, weight, dx, dweight, dbias, workspace, workspace_bytes, stream};
   if (const int rc = bn_bwd_status(a, 4, 0, false, nullptr, m, 1, 1, c)) return rc;
   return bn_bwd_launch<DyMem, kBnRedU>(a, DyMem{dy}, m, c);
+}
+
+size_t mhaq_fq_bn_fwd_workspace_bytes(int64_t m, int64_t c) { return bn_fwd_workspace_bytes(m, c, 4); }
+
+int mhaq_fq_bn_fwd(const float* x, const float* weight, const float* bias, float* y, float* save_mean, float* save_invstd,
+                   float* running_mean, float* running_var, double factor, double eps, int64_t m, int64_t c,
+                   void* workspace, size_t workspace_bytes, void* stream) {
+  const BnFwdCall a{x, weight, bias, y, save_mean, save_invstd, running_mean, running_var, factor, eps, workspace,
+                    workspace_bytes, stream};
+  if (const int rc = bn_fwd_status(a, 4, m, c)) return rc;
+  return bn_fwd_launch<IoF32>(a, m, c);
 }
 
 int mhaq_fq_bn_bwd_x16(const void* x, const void* dy, const float* mean, const float* invstd, const float* weight, void* dx,

@@ -57,7 +57,7 @@ namespace {
   X(mhaq_fq_act_relu_fwd_x16) X(mhaq_fq_act_relu_bwd_x16) X(mhaq_fq_act_relu_bwd_partials_x16)                        \
   X(mhaq_fq_bn_bwd_workspace_bytes) X(mhaq_fq_bn_bwd) X(mhaq_fq_maxpool3s2_fwd)                                       \
   X(mhaq_fq_bn_pool_bwd_workspace_bytes) X(mhaq_fq_bn_pool_bwd) X(mhaq_fq_bn_bwd_x16_workspace_bytes)                 \
-  X(mhaq_fq_bn_bwd_x16)
+  X(mhaq_fq_bn_bwd_x16) X(mhaq_fq_bn_fwd_workspace_bytes) X(mhaq_fq_bn_fwd)
 
 struct Api {
 #define X(n) decltype(&::n) n = nullptr;
@@ -706,6 +706,41 @@ std::atomic<int64_t> g_bn_hip_backwards{0};   // backwards that took mhaq_fq_bn_
 std::atomic<int64_t> g_bn_hip_backwards_x16{0};   // ... that took mhaq_fq_bn_bwd_x16
 std::atomic<int64_t> g_bn_pool_hip_backwards{0};   // ... that took mhaq_fq_bn_pool_bwd
 
+// ... and the opt-in HIP FORWARD (mhaq_fq_bn_fwd; `hip_forward` of bn_train / bn_pool_train): taken where bn_hip_eligible
+// holds for an fp32 x with N * H * W >= 2, the bias is eligible like the weight, and the running statistics are both absent or
+// both fp32 contiguous device tensors of length C.  Anything else is the framework's forward, as without the flag.
+std::atomic<int64_t> g_bn_hip_forwards{0};   // forwards of both nodes that took mhaq_fq_bn_fwd
+
+inline Tensor opt_tensor(const std::optional<Tensor>& t) { return t.has_value() ? *t : Tensor(); }
+
+inline bool bn_hip_forward_eligible(const Tensor& x, const Tensor& w, const Tensor& b, const Tensor& rm, const Tensor& rv) {
+  if (rm.defined() != rv.defined()) return false;
+  return bn_hip_eligible(x, w) && x.scalar_type() == at::kFloat && x.numel() / x.size(1) >= 2 &&
+         bn_hip_eligible(x, b, rm.defined() ? &rm : nullptr, rv.defined() ? &rv : nullptr);
+}
+
+// One HIP BatchNorm forward of an eligible x: {y, mean, invstd}; the running statistics are updated in place, with their
+// version counters bumped as the framework's in-place update bumps them.
+std::array<Tensor, 3> bn_hip_forward(const Tensor& x, const Tensor& w, const Tensor& b, const Tensor& rm, const Tensor& rv,
+                                     double momentum, double eps) {
+  need_lib();
+  const int64_t c = x.size(1), m = x.numel() / c;
+  Tensor y = at::empty_like(x);
+  Tensor mean = at::empty({c}, x.options()), invstd = at::empty({c}, x.options());
+  const size_t nb = A.mhaq_fq_bn_fwd_workspace_bytes(m, c);
+  Tensor ws = at::empty({(int64_t)nb}, x.options().dtype(at::kByte));
+  check(A.mhaq_fq_bn_fwd(fptr(x), fptr_or_null(w), fptr_or_null(b), fptr_mut(y), fptr_mut(mean), fptr_mut(invstd),
+                         rm.defined() ? fptr_mut(rm) : nullptr, rv.defined() ? fptr_mut(rv) : nullptr, momentum, eps, m, c,
+                         ws.mutable_data_ptr(), nb, cur_stream(x)),
+        "mhaq_fq_bn_fwd");
+  if (rm.defined()) {
+    torch::autograd::impl::bump_version(rm);
+    torch::autograd::impl::bump_version(rv);
+  }
+  g_bn_hip_forwards.fetch_add(1, std::memory_order_relaxed);
+  return {y, mean, invstd};
+}
+
 // One HIP BatchNorm backward of an eligible x: {dx, dweight, dbias} in the first three of `slots` outputs, undefined where the
 // mask says so.  The gradient comes as dy in x's layout or, with `code`, as the pooled gradient in the layout of its argmax
 // codes; the entry point follows from that and from x's dtype.  (The 16-bit pooled form, which the binding does not load,
@@ -753,10 +788,22 @@ class BatchNormTrainFn : public torch::autograd::Function<BatchNormTrainFn> {
   static Tensor forward(AutogradContext* ctx, const Tensor& x, const std::optional<Tensor>& w,
                         const std::optional<Tensor>& b, const std::optional<Tensor>& running_mean,
                         const std::optional<Tensor>& running_var, double momentum, double eps, bool cudnn_enabled,
-                        bool x16) {
+                        bool x16, bool hip_forward) {
+    const bool has_w = w.has_value() && w->defined();
+    ctx->saved_data["hip_fwd"] = false;
+    if (hip_forward && bn_hip_forward_eligible(x, opt_tensor(w), opt_tensor(b), opt_tensor(running_mean),
+                                               opt_tensor(running_var))) {
+      // the HIP forward: no reserve, no implementation index; such a node is eligible for the HIP backward by construction
+      auto out = bn_hip_forward(x, opt_tensor(w), opt_tensor(b), opt_tensor(running_mean), opt_tensor(running_var), momentum,
+                                eps);
+      ctx->save_for_backward({x, has_w ? *w : Tensor(), out[1], out[2], Tensor()});
+      ctx->saved_data["hip_fwd"] = true;
+      ctx->saved_data["x16"] = false;
+      ctx->set_materialize_grads(false);
+      return out[0];
+    }
     auto out = at::_batch_norm_impl_index(x, w, b, running_mean, running_var, /*training=*/true, momentum, eps,
                                           cudnn_enabled);
-    const bool has_w = w.has_value() && w->defined();
     ctx->save_for_backward({x, has_w ? *w : Tensor(), std::get<1>(out), std::get<2>(out), std::get<3>(out)});
     ctx->saved_data["impl"] = std::get<4>(out);
     ctx->saved_data["eps"] = eps;
@@ -769,7 +816,7 @@ class BatchNormTrainFn : public torch::autograd::Function<BatchNormTrainFn> {
   }
 
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    variable_list out(9);
+    variable_list out(10);
     if (!grads[0].defined()) return out;
     TORCH_CHECK(!(at::GradMode::is_enabled() && grads[0].requires_grad()),
                 "bn_train: the node is once-differentiable (no double backward)");
@@ -783,12 +830,14 @@ class BatchNormTrainFn : public torch::autograd::Function<BatchNormTrainFn> {
     if (hip && act_dtype(x) != 0 && ctx->saved_data["x16"].toBool() && grads[0].scalar_type() == x.scalar_type() &&
         grads[0].sizes() == x.sizes()) {
       const Tensor dy = like_layout(grads[0], x);
-      if (dy.is_cuda()) return bn_hip_backward(9, x, dy, Tensor(), w, mean, invstd, mask);
+      if (dy.is_cuda()) return bn_hip_backward(10, x, dy, Tensor(), w, mean, invstd, mask);
     }
     if (hip && x.scalar_type() == at::kFloat) {
       const Tensor dy = like_layout(grads[0].scalar_type() == at::kFloat ? grads[0] : grads[0].to(at::kFloat), x);
-      return bn_hip_backward(9, x, dy, Tensor(), w, mean, invstd, mask);
+      return bn_hip_backward(10, x, dy, Tensor(), w, mean, invstd, mask);
     }
+    TORCH_CHECK(!ctx->saved_data["hip_fwd"].toBool(), "bn_train: a node whose forward was mhaq_fq_bn_fwd has no framework "
+                "backward to fall back to");
     auto opt = [](const Tensor& t) { return t.defined() ? std::optional<Tensor>(t) : std::nullopt; };
     auto get = [&](const char* k) {
       return ctx->saved_data.count(k) ? std::optional<Tensor>(ctx->saved_data[k].toTensor()) : std::nullopt;
@@ -805,17 +854,17 @@ class BatchNormTrainFn : public torch::autograd::Function<BatchNormTrainFn> {
 
 Tensor bn_train(const Tensor& x, const std::optional<Tensor>& w, const std::optional<Tensor>& b,
                 const std::optional<Tensor>& running_mean, const std::optional<Tensor>& running_var, double momentum,
-                double eps, bool cudnn_enabled, bool x16) {
+                double eps, bool cudnn_enabled, bool x16, bool hip_forward) {
   TORCH_CHECK(w.has_value() && w->defined() && b.has_value() && b->defined(),
               "bn_train: an affine BatchNorm (weight and bias) is required");
   MHAQ_ON_DEVICE_OF(x);
-  return BatchNormTrainFn::apply(x, w, b, running_mean, running_var, momentum, eps, cudnn_enabled, x16);
+  return BatchNormTrainFn::apply(x, w, b, running_mean, running_var, momentum, eps, cudnn_enabled, x16, hip_forward);
 }
 
 // ------------------------------------------------------------------------------------------------ BatchNorm + stem pool
 // max_pool2d(bn_train(x, ..), 3, 2, 1) as ONE node (the ResNet stem, mhaq_amd/fused_blocks.py).  Forward: the framework's
-// BatchNorm forward as above, then mhaq_fq_maxpool3s2_fwd, which leaves the pooled tensor and a 1-byte argmax code per
-// output; the BatchNorm output dies with the forward, and neither it nor int64 indices are kept for the backward.
+// BatchNorm forward as above (mhaq_fq_bn_fwd with `hip_forward`, where eligible), then mhaq_fq_maxpool3s2_fwd, which leaves
+// the pooled tensor and a 1-byte argmax code per output; the BatchNorm output dies with the forward, and neither it nor int64 indices are kept for the backward.
 // Backward: mhaq_fq_bn_pool_bwd, the BatchNorm backward that gathers its dy from the pooled gradient and the codes instead
 // of reading a materialized one.  Output, running statistics and the three gradients are the bits of the two nodes run one
 // after the other.  Taken under BatchNormTrainFn's own conditions (and n * h * w < 2^31); outside them bn_pool_train IS
@@ -824,13 +873,20 @@ class BatchNormPoolTrainFn : public torch::autograd::Function<BatchNormPoolTrain
  public:
   static Tensor forward(AutogradContext* ctx, const Tensor& x, const Tensor& w, const Tensor& b,
                         const std::optional<Tensor>& running_mean, const std::optional<Tensor>& running_var,
-                        double momentum, double eps, bool cudnn_enabled) {
-    auto out = at::_batch_norm_impl_index(x, w, b, running_mean, running_var, /*training=*/true, momentum, eps,
-                                          cudnn_enabled);
-    const Tensor &mean = std::get<1>(out), &invstd = std::get<2>(out);
+                        double momentum, double eps, bool cudnn_enabled, bool hip_forward) {
+    // hip_forward: bn_pool_train has checked bn_hip_forward_eligible before this node was entered
+    Tensor t, mean, invstd;
+    if (hip_forward) {
+      auto out = bn_hip_forward(x, w, b, opt_tensor(running_mean), opt_tensor(running_var), momentum, eps);
+      t = out[0], mean = out[1], invstd = out[2];
+    } else {
+      auto out = at::_batch_norm_impl_index(x, w, b, running_mean, running_var, /*training=*/true, momentum, eps,
+                                            cudnn_enabled);
+      mean = std::get<1>(out), invstd = std::get<2>(out);
+      t = std::get<0>(out).contiguous(at::MemoryFormat::ChannelsLast);
+    }
     TORCH_CHECK(bn_hip_eligible(x, w, &mean, &invstd), "bn_pool_train: the BatchNorm forward left statistics the HIP "
                 "backward cannot read (there is no fallback behind this point)");
-    const Tensor t = std::get<0>(out).contiguous(at::MemoryFormat::ChannelsLast);
     const int64_t n = x.size(0), c = x.size(1), h = x.size(2), wd = x.size(3);
     Tensor p = at::empty({n, c, (h - 1) / 2 + 1, (wd - 1) / 2 + 1}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
     Tensor code = at::empty_like(p, p.options().dtype(at::kByte));
@@ -843,7 +899,7 @@ class BatchNormPoolTrainFn : public torch::autograd::Function<BatchNormPoolTrain
   }
 
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    variable_list out(8);
+    variable_list out(9);
     if (!grads[0].defined()) return out;
     TORCH_CHECK(!(at::GradMode::is_enabled() && grads[0].requires_grad()),
                 "bn_pool_train: the node is once-differentiable (no double backward)");
@@ -858,23 +914,25 @@ class BatchNormPoolTrainFn : public torch::autograd::Function<BatchNormPoolTrain
       dense.copy_(g);
       g = dense;
     }
-    return bn_hip_backward(8, x, g, code, w, mean, invstd, mask);
+    return bn_hip_backward(9, x, g, code, w, mean, invstd, mask);
   }
 };
 
 Tensor bn_pool_train(const Tensor& x, const std::optional<Tensor>& w, const std::optional<Tensor>& b,
                      const std::optional<Tensor>& running_mean, const std::optional<Tensor>& running_var, double momentum,
-                     double eps, bool cudnn_enabled) {
+                     double eps, bool cudnn_enabled, bool hip_forward) {
   TORCH_CHECK(w.has_value() && w->defined() && b.has_value() && b->defined(),
               "bn_pool_train: an affine BatchNorm (weight and bias) is required");
   MHAQ_ON_DEVICE_OF(x);
+  // the HIP forward's eligibility is settled here, before either node runs: nothing a fallback needs is dropped later
+  const bool hipf = hip_forward && bn_hip_forward_eligible(x, *w, *b, opt_tensor(running_mean), opt_tensor(running_var));
   // the fused node: fp32, with the 32-bit pixel arithmetic of its kernels (n * h * w < 2^31)
   if (!(bn_hip_eligible(x, *w) && x.scalar_type() == at::kFloat && x.numel() / x.size(1) < (1ll << 31)))
     return at::max_pool2d(BatchNormTrainFn::apply(x, w, b, running_mean, running_var, momentum, eps, cudnn_enabled,
-                                                  /*x16=*/false),
+                                                  /*x16=*/false, hipf),
                           {3, 3}, {2, 2}, {1, 1});
   need_lib();
-  return BatchNormPoolTrainFn::apply(x, *w, *b, running_mean, running_var, momentum, eps, cudnn_enabled);
+  return BatchNormPoolTrainFn::apply(x, *w, *b, running_mean, running_var, momentum, eps, cudnn_enabled, hipf);
 }
 
 // ------------------------------------------------------------------------------------------------ weight layer ops
@@ -1544,10 +1602,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("act_b"), py::arg("method"), py::arg("want_act"), py::arg("hub") = 0, py::arg("slot") = 0,
         py::arg("rank") = 0);
 
-  // training BatchNorm: the framework's forward, the HIP backward
+  // training BatchNorm: the framework's forward (mhaq_fq_bn_fwd with hip_forward, where eligible), the HIP backward
   m.def("bn_train", &bn_train, py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("running_mean"),
         py::arg("running_var"), py::arg("momentum"), py::arg("eps"), py::arg("cudnn_enabled") = true,
-        py::arg("x16") = false);
+        py::arg("x16") = false, py::arg("hip_forward") = false);
+  m.def("bn_hip_forwards", []() { return g_bn_hip_forwards.load(); },
+        "number of BatchNorm forwards so far (bn_train and bn_pool_train) that ran mhaq_fq_bn_fwd instead of the framework's");
 
   m.def("bn_hip_backwards", []() { return g_bn_hip_backwards.load(); },
         "number of BatchNorm backwards so far that ran the fp32 HIP kernels instead of the framework's backward");
@@ -1555,7 +1615,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "number of BatchNorm backwards so far that ran the 16-bit HIP kernels (mhaq_fq_bn_bwd_x16)");
   // ... with the stem's 3x3 / stride 2 max pool in the same node
   m.def("bn_pool_train", &bn_pool_train, py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("running_mean"),
-        py::arg("running_var"), py::arg("momentum"), py::arg("eps"), py::arg("cudnn_enabled") = true);
+        py::arg("running_var"), py::arg("momentum"), py::arg("eps"), py::arg("cudnn_enabled") = true,
+        py::arg("hip_forward") = false);
   m.def("bn_pool_hip_backwards", []() { return g_bn_pool_hip_backwards.load(); },
         "number of BatchNorm + pool backwards so far that ran mhaq_fq_bn_pool_bwd (the fallback is the two separate nodes)");
 

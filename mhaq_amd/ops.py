@@ -341,6 +341,34 @@ def row_minmax(w: torch.Tensor):
     return mn, mx
 
 
+@_on_device
+def bn_forward_train(x, weight=None, bias=None, running_mean=None, running_var=None, factor=0.1, eps=1e-5):
+    """Training-mode BatchNorm forward of a dense float32 channels_last [N, C, H, W] tensor on mhaq_fq_bn_fwd (no autograd:
+    the compiled node bn_train(hip_forward=True) is the differentiable form).  Returns (y, save_mean, save_invstd); the running
+    statistics, both given or both None, are updated in place with `factor`."""
+    x = _require_cuda_f32(x.detach(), "x", any_dense_layout=True)
+    if x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last):
+        raise ValueError("bn_forward_train: x must be a dense channels_last [N, C, H, W] tensor")
+    c = x.shape[1]
+    m = x.numel() // max(c, 1)
+    vecs = [None if t is None else _require_cuda_f32(t.detach(), "a per-channel vector")
+            for t in (weight, bias, running_mean, running_var)]
+    if any(t is not None and (t.numel() != c or t.device != x.device) for t in vecs):
+        raise ValueError("bn_forward_train: per-channel vectors must have C elements on x's device")
+    if any(t is not None and t.data_ptr() != o.data_ptr() for t, o in zip(vecs[2:], (running_mean, running_var))):
+        raise ValueError("bn_forward_train: the running statistics must be contiguous (they are updated in place)")
+    L = _lib.lib()
+    y = torch.empty_like(x)
+    mean, invstd = torch.empty(c, device=x.device), torch.empty(c, device=x.device)
+    nb = L.mhaq_fq_bn_fwd_workspace_bytes(m, c)
+    ws = _workspace(max(nb, 16), x.device)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    _lib.check(L.mhaq_fq_bn_fwd(x.data_ptr(), *map(ptr, vecs[:2]), y.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
+                                *map(ptr, vecs[2:]), float(factor), float(eps), m, c, ws.data_ptr(), nb, _stream()),
+               "mhaq_fq_bn_fwd")
+    return y, mean, invstd
+
+
 # ----------------------------------------------------------------------------- per-tensor op
 def _pt_forward(x, s, zp, lo, hi, want_q=False, want_stats=False):
     L = _lib.lib()

@@ -68,6 +68,9 @@ class QATConfig:
     # ... and on the 16-bit tensors of an autocast step (mhaq_fq_bn_bwd_x16: dx is the fp32 arithmetic rounded once, so the
     # gradient bits of a bf16 run change).  Off by default; MHAQ_BN_BACKWARD_X16=1 / 0 in the environment overrides it.
     hip_bn_backward_16bit: bool = False
+    # ... and the FORWARD of float32 inputs on mhaq_fq_bn_fwd, where hip_bn_backward installs (the bits of y and of the saved
+    # and running statistics change).  Off by default; MHAQ_BN_FORWARD=1 / 0 in the environment overrides it.
+    hip_bn_forward: bool = False
     criterion: nn.Module = field(default_factory=nn.CrossEntropyLoss)
     # mixed precision (the reference trainer's `precision = "bf16-mixed"`, training/trainer.py:126): torch.bfloat16 runs
     # the teacher and student forwards, the loss and validate_step's forward under torch.autocast; the activation
@@ -226,7 +229,8 @@ class QATTrainer:
         if cfg.hip_bn_backward and layers is None and self.device.type == "cuda":
             from . import bn_backward
             if bn_backward.enabled_by_env():
-                bn_backward.install(net, x16=bn_backward.x16_enabled(cfg.hip_bn_backward_16bit))
+                bn_backward.install(net, x16=bn_backward.x16_enabled(cfg.hip_bn_backward_16bit),
+                                    hip_forward=bn_backward.hip_forward_enabled(cfg.hip_bn_forward))
         self.net = net
         self.teacher_stream = None
         if cfg.distillation and cfg.overlap_teacher and self.device.type == "cuda":
