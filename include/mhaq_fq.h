@@ -422,6 +422,39 @@ int mhaq_fq_bn_pool_bwd_x16(const void* x, const void* g, const uint8_t* code, c
                             const float* weight, void* dx, float* dweight, float* dbias, int64_t n, int64_t h, int64_t w,
                             int64_t c, int dtype, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Eval-mode BatchNorm of a FROZEN network (a distillation teacher: parameters and running statistics fixed between calls)
+ * with what follows it in a ResNet block, one launch per place.  Additive to ABI v4 -- MHAQ_FQ_ABI_VERSION stays 4; a caller
+ * discovers these entry points by symbol.  Tensors are dense fp32 NHWC seen as [m][c]; m >= 1, c % 4 == 0 and c <= 2^22
+ * (else MHAQ_FQ_EUNSUPPORTED); tensors and constant slabs 16-byte aligned (else MHAQ_FQ_EALIGN).  Argument errors are
+ * returned before any launch, with mhaq_fq_bn_fwd's codes in its order: required pointers, positive sizes and a known mode
+ * (MHAQ_FQ_EINVAL), width and range (MHAQ_FQ_EUNSUPPORTED), the alignment (there is no workspace).
+ *
+ * mhaq_fq_bn_infer_consts: consts[3][c] = {running_mean, a, bias} with a = weight * (running_var + eps)^-1/2 evaluated in
+ * fp64 and rounded to fp32 ONCE; weight NULL = 1, bias NULL = 0.  The slab is the caller's; it is valid until a parameter,
+ * a statistic or eps changes.
+ *
+ * mhaq_fq_bn_infer_act: with t = (x - mean) * a + bias in fp32, in this order, without contraction (mhaq_fq_bn_fwd's
+ * expression), and relu(v) = v > 0 ? v : (isnan(v) ? v : 0):
+ *   MHAQ_FQ_BN_RELU        y = relu(t)                x2, consts2, residual NULL
+ *   MHAQ_FQ_BN_ADD_RELU    y = relu(t + residual)     residual [m][c] required; x2, consts2 NULL
+ *   MHAQ_FQ_BN2_ADD_RELU   y = relu(t + t2)           t2 = the same expression of x2 [m][c] with consts2; residual NULL
+ * (an operand the mode does not read, or a missing one: MHAQ_FQ_EINVAL).  The sum is rounded to fp32 before the ReLU: every
+ * y is the bits of torch's separate sub, mul, add, add and relu on the same constants.  y must not overlap an input.
+ *
+ * mhaq_fq_bn_relu_pool3s2: p[n, oh, ow, c] = max_pool2d(relu(t), kernel 3, stride 2, padding 1) of x[n, h, w, c], t never
+ * stored; geometry, limits (n * h * w < 2^31) and selection (start at -inf, replace on val > max || isnan(val)) are
+ * mhaq_fq_maxpool3s2_fwd's.
+ * Each is one launch: stream-ordered, no host synchronisation, capture-safe, stateless.
+ * ---------------------------------------------------------------------- */
+enum { MHAQ_FQ_BN_RELU = 0, MHAQ_FQ_BN_ADD_RELU = 1, MHAQ_FQ_BN2_ADD_RELU = 2 };
+int mhaq_fq_bn_infer_consts(const float* running_mean, const float* running_var, const float* weight, const float* bias,
+                            double eps, int64_t c, float* consts /* [3][c] */, void* stream);
+int mhaq_fq_bn_infer_act(const float* x, const float* consts, const float* x2, const float* consts2, const float* residual,
+                         float* y, int64_t m, int64_t c, int mode, void* stream);
+int mhaq_fq_bn_relu_pool3s2(const float* x, const float* consts, float* p, int64_t n, int64_t h, int64_t w, int64_t c,
+                            void* stream);
+
 /* Whole-tensor min / max (zero point of a PER_TENSOR weight quantizer,
  * gdnsq_conv2d.py:82-83; min/max observer, calib/minmaxobserver.py:19-36).
  * out[0] = min, out[1] = max. */

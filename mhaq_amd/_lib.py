@@ -71,6 +71,10 @@ SIGNATURES = {
     "mhaq_fq_maxpool3s2_fwd_x16": (_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _int, _p]),
     "mhaq_fq_bn_pool_bwd_x16_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "mhaq_fq_bn_pool_bwd_x16": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _int, _p, _sz, _p]),
+    # eval-mode BatchNorm of a frozen network with its ReLU, residual add and stem pool (additive, ABI v4 kept)
+    "mhaq_fq_bn_infer_consts": (_int, [_p, _p, _p, _p, C.c_double, _i64, _p, _p]),
+    "mhaq_fq_bn_infer_act": (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _int, _p]),
+    "mhaq_fq_bn_relu_pool3s2": (_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _p]),
     "mhaq_fq_minmax_workspace_bytes": (_sz, [_i64]),
     "mhaq_fq_minmax": (_int, [_p, _i64, _p, _p, _sz, _p]),
     "mhaq_fq_row_minmax": (_int, [_p, _i64, _i64, _p, _p, _p]),

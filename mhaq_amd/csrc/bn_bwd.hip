@@ -848,6 +848,145 @@ static int bn_fwd_launch(const BnFwdCall& a, int64_t m, int64_t c) {
   return launch_status();
 }
 
+// ---------------------------------------------------------------- the frozen forward (mhaq_fq_bn_infer_*)
+// Eval-mode BatchNorm from the running statistics with what follows it in a frozen ResNet block, one launch per place:
+//   bn_infer_consts_kernel     consts[3][C] = {running_mean, gamma * (running_var + eps)^-1/2, beta}: the three rows of the
+//                              training forward; the product in fp64, rounded to fp32 ONCE.  Launched when the parameters change.
+//   bn_infer_act_kernel        bn_fwd_norm_kernel with the ReLU, and the residual add in front of it, in the same pass:
+//                              BN_RELU        y = relu(t)                    1R1W
+//                              BN_ADD_RELU    y = relu(t + r)                2R1W  (r: the block's input)
+//                              BN2_ADD_RELU   y = relu(t + t2)               2R1W  (t2: the downsample branch, its own constants)
+//   bn_relu_pool3s2_kernel     max_pool2d(relu(t), 3, 2, 1) without a stored t (behind the pool's forward, further down)
+// t = (x - mean) * a + beta in fp32, in this order, uncontracted; the add and the ReLU round where torch's separate add and
+// clamp_min round, so every output is the bits of those ops on the same constants.  relu keeps a NaN.
+// Cache policy, overridable at build time (tools/teacher_fwd_bench.py times builds with forced policies next to the
+// product's): loads go by the byte rule of the training forward -- non-temporal once the INPUT streams together exceed
+// 56 Mi fp32 elements --; the output is read again by the next convolution, so stores take the default policy.
+#ifndef MHAQ_BN_INFER_NT_ELEMS
+#define MHAQ_BN_INFER_NT_ELEMS (56ll << 20)
+#endif
+#ifndef MHAQ_BN_INFER_ST_NT
+#define MHAQ_BN_INFER_ST_NT 0
+#endif
+constexpr int64_t kBnInferNtElems = MHAQ_BN_INFER_NT_ELEMS;
+constexpr bool kBnInferStNt = MHAQ_BN_INFER_ST_NT != 0;
+
+__device__ __forceinline__ float bn_relu(float v) { return v > 0.0f ? v : (v != v ? v : 0.0f); }
+__device__ __forceinline__ void bn_infer_st4(float* p, int64_t vidx, vf4 v) {
+  if constexpr (kBnInferStNt) bn_st4(p, vidx, v);
+  else reinterpret_cast<vf4*>(p)[vidx] = v;
+}
+
+__global__ __launch_bounds__(kBlock) void bn_infer_consts_kernel(
+    const float* __restrict__ mean, const float* __restrict__ var, const float* __restrict__ weight,
+    const float* __restrict__ bias, double eps, int c, float* __restrict__ consts) {
+  const int i = (int)(blockIdx.x * kBlock + threadIdx.x);
+  if (i >= c) return;
+  const double is = 1.0 / sqrt((double)var[i] + eps);
+  consts[i] = mean[i];
+  consts[c + i] = (float)((weight ? (double)weight[i] : 1.0) * is);
+  consts[2 * c + i] = bias ? bias[i] : 0.0f;
+}
+
+// Block, loads, column arithmetic and occupancy are bn_fwd_norm_kernel's (fp32).  x2 is the residual (BN_ADD_RELU) or the
+// second branch's input with its constants k2 (BN2_ADD_RELU).
+template <bool NT, bool BIG, int MODE>
+__global__ __attribute__((amdgpu_waves_per_eu(
+    (BIG ? 1 : kBnFwdWaves<IoF32>), (BIG && kBnBigMaxWaves < kBnFwdWaves<IoF32> ? kBnBigMaxWaves : kBnFwdWaves<IoF32>))))
+__launch_bounds__(kBlock) void bn_infer_act_kernel(
+    const float* __restrict__ x, const float* __restrict__ x2, float* __restrict__ y, int64_t nvec, int cv,
+    const float* __restrict__ k1, const float* __restrict__ k2) {
+  constexpr bool kTwo = MODE != MHAQ_FQ_BN_RELU, kBn2 = MODE == MHAQ_FQ_BN2_ADD_RELU;
+  const int64_t blk0 = (int64_t)blockIdx.x * (kBlock * kBnDxU);
+  const int64_t base = blk0 + threadIdx.x;
+  const bool full = blk0 + kBlock * kBnDxU <= nvec;
+  vf4 a[kBnDxU], b[kBnDxU];
+#pragma unroll
+  for (int u = 0; u < kBnDxU; ++u) {
+    const int64_t idx = base + u * kBlock;
+    const int64_t idc = (full || idx < nvec) ? idx : nvec - 1;
+    a[u] = bn_ld4<NT>(x, idc);
+    if constexpr (kTwo) b[u] = bn_ld4<NT>(x2, idc);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  const uint32_t ucv = (uint32_t)cv;
+  const uint32_t cb = ((blockIdx.x % ucv) * ((uint32_t)(kBlock * kBnDxU) % ucv)) % ucv;      // wave-uniform
+  const uint32_t step = (uint32_t)kBlock % ucv;                                               // wave-uniform
+  uint32_t col = (cb + threadIdx.x) % ucv;
+  const int64_t c = (int64_t)cv * 4;
+  float k[kBnFwdNConst][4], kk[kBnFwdNConst][4];
+#pragma unroll
+  for (int u = 0; u < kBnDxU; ++u) {
+    const int64_t idx = base + u * kBlock;
+    if (u > 0) {
+      col += step;
+      if (col >= ucv) col -= ucv;
+    }
+    if (u == 0 || step != 0) {
+#pragma unroll
+      for (int q = 0; q < kBnFwdNConst; ++q) {
+        ldv<4>(k1 + q * c + (int64_t)col * 4, k[q]);
+        if constexpr (kBn2) ldv<4>(k2 + q * c + (int64_t)col * 4, kk[q]);
+      }
+    }
+    if (full || idx < nvec) {
+      const float xv[4] = {a[u].x, a[u].y, a[u].z, a[u].w};
+      float o[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float t = (xv[j] - k[0][j]) * k[1][j] + k[2][j];
+        if constexpr (kTwo) {
+          const float bv = b[u][j];
+          t = t + (kBn2 ? (bv - kk[0][j]) * kk[1][j] + kk[2][j] : bv);
+        }
+        o[j] = bn_relu(t);
+      }
+      bn_infer_st4(y, idx, vf4{o[0], o[1], o[2], o[3]});
+    }
+  }
+}
+
+// Status of the two elementwise entry points before anything is launched, in bn_fwd_status's order: required pointers,
+// positive sizes and a known mode; width and range; (no workspace;) the alignment -- the constant rows are read 16 bytes at a time.
+static int bn_infer_consts_status(const float* mean, const float* var, const float* weight, const float* bias, int64_t c,
+                                  const float* consts) {
+  if (!mean || !var || !consts || c <= 0) return MHAQ_FQ_EINVAL;
+  if ((c & 3) || c > kBnMaxChannels) return MHAQ_FQ_EUNSUPPORTED;
+  if (!bn_aligned(mean, 4) || !bn_aligned(var, 4) || !bn_aligned(weight, 4) || !bn_aligned(bias, 4) ||
+      !bn_aligned(consts, 16))
+    return MHAQ_FQ_EALIGN;
+  return 0;
+}
+// A mode's own operands are required and the other mode's refused: a residual with BN_ADD_RELU only, x2 and consts2 with
+// BN2_ADD_RELU only.
+static int bn_infer_act_status(const float* x, const float* consts, const float* x2, const float* consts2,
+                               const float* residual, const float* y, int64_t m, int64_t c, int mode) {
+  if (!x || !consts || !y || m <= 0 || c <= 0) return MHAQ_FQ_EINVAL;
+  if (mode != MHAQ_FQ_BN_RELU && mode != MHAQ_FQ_BN_ADD_RELU && mode != MHAQ_FQ_BN2_ADD_RELU) return MHAQ_FQ_EINVAL;
+  if (!residual != (mode != MHAQ_FQ_BN_ADD_RELU) || !x2 != (mode != MHAQ_FQ_BN2_ADD_RELU) || !x2 != !consts2)
+    return MHAQ_FQ_EINVAL;
+  if ((c & 3) || c > kBnMaxChannels || m > (INT64_MAX >> 3) / c ||
+      (m * (c >> 2) + kBlock * kBnDxU - 1) / (kBlock * kBnDxU) > 0x7fffffff)
+    return MHAQ_FQ_EUNSUPPORTED;
+  if (!bn_aligned(x, 16) || !bn_aligned(consts, 16) || !bn_aligned(x2, 16) || !bn_aligned(consts2, 16) ||
+      !bn_aligned(residual, 16) || !bn_aligned(y, 16))
+    return MHAQ_FQ_EALIGN;
+  return 0;
+}
+
+// The one launch (arguments checked by bn_infer_act_status); x2: the mode's second stream.
+template <int MODE>
+static int bn_infer_act_launch(const float* x, const float* k1, const float* x2, const float* k2, float* y, int64_t m,
+                               int64_t c, hipStream_t st) {
+  const int64_t nvec = m * (c >> 2);
+  const int64_t grid = (nvec + kBlock * kBnDxU - 1) / (kBlock * kBnDxU);
+  const bool nt = m * c * (MODE == MHAQ_FQ_BN_RELU ? 1 : 2) >= kBnInferNtElems, big = m * c >= kBnBigElems;
+  MHAQ_LAUNCH((big ? (nt ? bn_infer_act_kernel<true, true, MODE> : bn_infer_act_kernel<false, true, MODE>)
+                   : (nt ? bn_infer_act_kernel<true, false, MODE> : bn_infer_act_kernel<false, false, MODE>)),
+              dim3((unsigned)grid), dim3(kBlock), 0, st, x, x2, y, nvec, (int)(c >> 2), k1, k2);
+  return launch_status();
+}
+
 // ---------------------------------------------------------------- the pool's forward: values and argmax codes
 // max_pool2d(kernel 3, stride 2, padding 1) of a dense fp32 NHWC tensor: one lane per float4 of the output.  The selection
 // is the framework's channels_last kernel's: the window's in-range positions in kh, then kw order, starting at -inf and
@@ -901,6 +1040,49 @@ __global__ __launch_bounds__(kBlock) void maxpool3s2_fwd_kernel(
   }
   reinterpret_cast<vf4*>(p)[idx] = vf4{mx[0], mx[1], mx[2], mx[3]};
   reinterpret_cast<uint32_t*>(code)[idx] = cd[0] | (cd[1] << 8) | (cd[2] << 16) | (cd[3] << 24);
+}
+
+// The frozen stem: p = max_pool2d(relu((x - mean) * a + beta), 3, 2, 1) of a dense fp32 NHWC x, the BatchNorm output never
+// stored.  Geometry, the nine clamped loads, their cache policy and the selection are the kernel's above, without the codes
+// (nothing is differentiated); the constants of the lane's four channels arrive under the data loads, and each in-range value
+// takes bn_infer_act_kernel's arithmetic before it is compared.
+__global__ __launch_bounds__(kBlock) void bn_relu_pool3s2_kernel(
+    const float* __restrict__ x, float* __restrict__ p, uint32_t h, uint32_t w, uint32_t oh, uint32_t ow, uint32_t cv,
+    int64_t nvec, const float* __restrict__ consts) {
+  const uint32_t bq = blockIdx.x / cv, br = (blockIdx.x - bq * cv) * (uint32_t)kBlock, brq = br / cv;
+  const uint32_t tt = br - brq * cv + threadIdx.x, tq = tt / cv;
+  const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool ok = idx < nvec;
+  const uint32_t pixel = ok ? bq * (uint32_t)kBlock + brq + tq : 0u, col = tt - tq * cv;
+  const uint32_t q = pixel / ow, n = q / oh, po = q - n * oh, pw = pixel - q * ow;
+  const int ih0 = (int)(po * 2u) - 1, iw0 = (int)(pw * 2u) - 1;
+  vf4 v[9];
+  bool in[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const int ih = ih0 + k / 3, iw = iw0 + k % 3;
+    in[k] = ih >= 0 && ih < (int)h && iw >= 0 && iw < (int)w;
+    const uint32_t ihc = (uint32_t)(ih < 0 ? 0 : (ih < (int)h ? ih : (int)h - 1));
+    const uint32_t iwc = (uint32_t)(iw < 0 ? 0 : (iw < (int)w ? iw : (int)w - 1));
+    v[k] = bn_ld4<false>(x, (int64_t)((n * h + ihc) * w + iwc) * cv + col);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  float kc[kBnFwdNConst][4];
+#pragma unroll
+  for (int r = 0; r < kBnFwdNConst; ++r) ldv<4>(consts + ((int64_t)r * cv + col) * 4, kc[r]);
+  if (!ok) return;
+  float mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const float e[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float r = bn_relu((e[j] - kc[0][j]) * kc[1][j] + kc[2][j]);
+      const bool take = in[k] && (r > mx[j] || r != r);
+      mx[j] = take ? r : mx[j];
+    }
+  }
+  reinterpret_cast<vf4*>(p)[idx] = vf4{mx[0], mx[1], mx[2], mx[3]};
 }
 
 // The same pool on a dense 16-bit NHWC tensor of the element type DT: one lane per 8 output channels, nine 16-byte loads, a
@@ -1054,6 +1236,36 @@ int mhaq_fq_bn_fwd(const float* x, const float* weight, const float* bias, float
                     workspace_bytes, stream};
   if (const int rc = bn_fwd_status(a, 4, m, c)) return rc;
   return bn_fwd_launch<IoF32>(a, m, c);
+}
+
+int mhaq_fq_bn_infer_consts(const float* running_mean, const float* running_var, const float* weight, const float* bias,
+                            double eps, int64_t c, float* consts, void* stream) {
+  if (const int rc = bn_infer_consts_status(running_mean, running_var, weight, bias, c, consts)) return rc;
+  MHAQ_LAUNCH(bn_infer_consts_kernel, dim3((unsigned)((c + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream,
+              running_mean, running_var, weight, bias, eps, (int)c, consts);
+  return launch_status();
+}
+
+int mhaq_fq_bn_infer_act(const float* x, const float* consts, const float* x2, const float* consts2, const float* residual,
+                         float* y, int64_t m, int64_t c, int mode, void* stream) {
+  if (const int rc = bn_infer_act_status(x, consts, x2, consts2, residual, y, m, c, mode)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (mode == MHAQ_FQ_BN_RELU) return bn_infer_act_launch<MHAQ_FQ_BN_RELU>(x, consts, nullptr, nullptr, y, m, c, st);
+  if (mode == MHAQ_FQ_BN_ADD_RELU) return bn_infer_act_launch<MHAQ_FQ_BN_ADD_RELU>(x, consts, residual, nullptr, y, m, c, st);
+  return bn_infer_act_launch<MHAQ_FQ_BN2_ADD_RELU>(x, consts, x2, consts2, y, m, c, st);
+}
+
+int mhaq_fq_bn_relu_pool3s2(const float* x, const float* consts, float* p, int64_t n, int64_t h, int64_t w, int64_t c,
+                            void* stream) {
+  if (!x || !consts || !p) return MHAQ_FQ_EINVAL;
+  if (const int rc = pool_dims_status(n, h, w, c, 4)) return rc;
+  const int64_t oh = pool_out(h), ow = pool_out(w), nvec = n * oh * ow * (c >> 2);
+  const int64_t grid = (nvec + kBlock - 1) / kBlock;
+  if (grid > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
+  if (!bn_aligned(x, 16) || !bn_aligned(consts, 16) || !bn_aligned(p, 16)) return MHAQ_FQ_EALIGN;
+  MHAQ_LAUNCH(bn_relu_pool3s2_kernel, dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream, x, p, (uint32_t)h,
+              (uint32_t)w, (uint32_t)oh, (uint32_t)ow, (uint32_t)(c >> 2), nvec, consts);
+  return launch_status();
 }
 
 int mhaq_fq_bn_bwd_x16(const void* x, const void* dy, const float* mean, const float* invstd, const float* weight, void* dx,

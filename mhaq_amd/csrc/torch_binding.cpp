@@ -57,7 +57,8 @@ namespace {
   X(mhaq_fq_act_relu_fwd_x16) X(mhaq_fq_act_relu_bwd_x16) X(mhaq_fq_act_relu_bwd_partials_x16)                        \
   X(mhaq_fq_bn_bwd_workspace_bytes) X(mhaq_fq_bn_bwd) X(mhaq_fq_maxpool3s2_fwd)                                       \
   X(mhaq_fq_bn_pool_bwd_workspace_bytes) X(mhaq_fq_bn_pool_bwd) X(mhaq_fq_bn_bwd_x16_workspace_bytes)                 \
-  X(mhaq_fq_bn_bwd_x16) X(mhaq_fq_bn_fwd_workspace_bytes) X(mhaq_fq_bn_fwd)
+  X(mhaq_fq_bn_bwd_x16) X(mhaq_fq_bn_fwd_workspace_bytes) X(mhaq_fq_bn_fwd)                                         \
+  X(mhaq_fq_bn_infer_consts) X(mhaq_fq_bn_infer_act) X(mhaq_fq_bn_relu_pool3s2)
 
 struct Api {
 #define X(n) decltype(&::n) n = nullptr;
@@ -935,6 +936,70 @@ Tensor bn_pool_train(const Tensor& x, const std::optional<Tensor>& w, const std:
   return BatchNormPoolTrainFn::apply(x, *w, *b, running_mean, running_var, momentum, eps, cudnn_enabled, hipf);
 }
 
+// ------------------------------------------------------------------------------------------------ the frozen teacher
+// Eval-mode BatchNorm with its ReLU, residual add and stem pool in one launch per place (mhaq_amd/frozen_blocks.py;
+// mhaq_fq_bn_infer_*).  Plain functions, not nodes: the teacher runs without grad.  The caller has settled that the place may
+// be fused; what arrives here and does not fit the kernels is an error, never a quiet framework path.  Outputs come from the
+// caching allocator, the launch goes to the current stream of the input's device: no host synchronisation, capture-safe.
+std::atomic<int64_t> g_teacher_fused_calls{0};   // launches of mhaq_fq_bn_infer_act and mhaq_fq_bn_relu_pool3s2 so far
+
+inline void check_frozen_input(const Tensor& x, const Tensor& consts, const char* what) {
+  TORCH_CHECK(bn_hip_eligible(x, Tensor()) && x.scalar_type() == at::kFloat, what,
+              ": x must be a non-empty dense channels_last float32 device tensor with C % 4 == 0");
+  TORCH_CHECK(consts.defined() && consts.is_cuda() && consts.device() == x.device() && consts.scalar_type() == at::kFloat &&
+                  consts.is_contiguous() && consts.numel() == 3 * x.size(1) && aligned16(consts),
+              what, ": the constants must be a contiguous float32 [3, C] slab on x's device");
+}
+
+void bn_infer_consts(const Tensor& running_mean, const Tensor& running_var, const std::optional<Tensor>& weight,
+                     const std::optional<Tensor>& bias, double eps, const Tensor& consts) {
+  need_lib();
+  const int64_t c = running_mean.numel();
+  const Tensor w = opt_tensor(weight), b = opt_tensor(bias);
+  auto vec_ok = [&](const Tensor& t) {
+    return t.is_cuda() && t.device() == consts.device() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == c;
+  };
+  TORCH_CHECK(consts.defined() && consts.is_cuda() && consts.scalar_type() == at::kFloat && consts.is_contiguous() &&
+                  consts.numel() == 3 * c && vec_ok(running_mean) && vec_ok(running_var) && (!w.defined() || vec_ok(w)) &&
+                  (!b.defined() || vec_ok(b)),
+              "bn_infer_consts: contiguous float32 vectors of one length C on the device of a [3, C] slab are required");
+  MHAQ_ON_DEVICE_OF(consts);
+  check(A.mhaq_fq_bn_infer_consts(fptr(running_mean), fptr(running_var), fptr_or_null(w), fptr_or_null(b), eps, c,
+                                  fptr_mut(consts), cur_stream(consts)),
+        "mhaq_fq_bn_infer_consts");
+}
+
+Tensor bn_infer_act(const Tensor& x, const Tensor& consts, int64_t mode, const std::optional<Tensor>& x2,
+                    const std::optional<Tensor>& consts2, const std::optional<Tensor>& residual) {
+  need_lib();
+  check_frozen_input(x, consts, "bn_infer_act");
+  const Tensor b = opt_tensor(x2), k2 = opt_tensor(consts2), r = opt_tensor(residual);
+  for (const Tensor* t : {&b, &r})
+    TORCH_CHECK(!t->defined() || (t->is_cuda() && t->device() == x.device() && t->scalar_type() == at::kFloat &&
+                                  t->sizes() == x.sizes() && t->strides() == x.strides() && aligned16(*t)),
+                "bn_infer_act: the second input and the residual must have x's dtype, device, sizes and strides");
+  if (b.defined()) check_frozen_input(b, k2, "bn_infer_act (second input)");
+  MHAQ_ON_DEVICE_OF(x);
+  const int64_t c = x.size(1), m = x.numel() / c;
+  Tensor y = at::empty_like(x);
+  check(A.mhaq_fq_bn_infer_act(fptr(x), fptr(consts), fptr_or_null(b), fptr_or_null(k2), fptr_or_null(r), fptr_mut(y), m, c,
+                               (int)mode, cur_stream(x)),
+        "mhaq_fq_bn_infer_act");
+  g_teacher_fused_calls.fetch_add(1, std::memory_order_relaxed);
+  return y;
+}
+
+Tensor bn_relu_pool(const Tensor& x, const Tensor& consts) {
+  need_lib();
+  check_frozen_input(x, consts, "bn_relu_pool");
+  MHAQ_ON_DEVICE_OF(x);
+  const int64_t n = x.size(0), c = x.size(1), h = x.size(2), wd = x.size(3);
+  Tensor p = at::empty({n, c, (h - 1) / 2 + 1, (wd - 1) / 2 + 1}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
+  check(A.mhaq_fq_bn_relu_pool3s2(fptr(x), fptr(consts), fptr_mut(p), n, h, wd, c, cur_stream(x)), "mhaq_fq_bn_relu_pool3s2");
+  g_teacher_fused_calls.fetch_add(1, std::memory_order_relaxed);
+  return p;
+}
+
 // ------------------------------------------------------------------------------------------------ weight layer ops
 struct Pre {   // this step's forward of the layer out of the model-wide launch (multi.py, forward-only mode)
   bool has = false;
@@ -1619,6 +1684,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("hip_forward") = false);
   m.def("bn_pool_hip_backwards", []() { return g_bn_pool_hip_backwards.load(); },
         "number of BatchNorm + pool backwards so far that ran mhaq_fq_bn_pool_bwd (the fallback is the two separate nodes)");
+
+  // the frozen teacher's eval-mode BatchNorm with its ReLU, residual add and stem pool (no autograd)
+  m.def("bn_infer_consts", &bn_infer_consts, py::arg("running_mean"), py::arg("running_var"), py::arg("weight"),
+        py::arg("bias"), py::arg("eps"), py::arg("consts"));
+  m.def("bn_infer_act", &bn_infer_act, py::arg("x"), py::arg("consts"), py::arg("mode"), py::arg("x2") = py::none(),
+        py::arg("consts2") = py::none(), py::arg("residual") = py::none());
+  m.def("bn_relu_pool", &bn_relu_pool, py::arg("x"), py::arg("consts"));
+  m.def("teacher_fused_calls", []() { return g_teacher_fused_calls.load(); },
+        "number of fused launches so far on a frozen network's elementwise chain (bn_infer_act and bn_relu_pool)");
 
   // weight layers
   m.def("weight_layer", &weight_layer, py::arg("w"), py::arg("log_wght_s"), py::arg("method"),

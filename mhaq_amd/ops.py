@@ -369,6 +369,71 @@ def bn_forward_train(x, weight=None, bias=None, running_mean=None, running_var=N
     return y, mean, invstd
 
 
+# modes of bn_infer_act (include/mhaq_fq.h)
+BN_RELU, BN_ADD_RELU, BN2_ADD_RELU = 0, 1, 2
+
+
+def _nhwc_f32(t, name):
+    t = _require_cuda_f32(t.detach(), name, any_dense_layout=True)
+    if t.dim() != 4 or not t.is_contiguous(memory_format=torch.channels_last):
+        raise ValueError(f"{name} must be a dense channels_last [N, C, H, W] tensor")
+    return t
+
+
+@_on_device
+def bn_infer_consts(running_mean, running_var, weight=None, bias=None, eps=1e-5, out=None):
+    """The [3, C] constant slab {running_mean, weight * (running_var + eps)^-1/2, bias} of an eval-mode BatchNorm
+    (mhaq_fq_bn_infer_consts: the product in fp64, rounded once), into `out` when given."""
+    vecs = [None if t is None else _require_cuda_f32(t.detach(), "a per-channel vector")
+            for t in (running_mean, running_var, weight, bias)]
+    c = vecs[0].numel()
+    if any(t is not None and (t.numel() != c or t.device != vecs[0].device) for t in vecs):
+        raise ValueError("bn_infer_consts: per-channel vectors must have one length and one device")
+    if out is None:
+        out = torch.empty(3, c, dtype=torch.float32, device=vecs[0].device)
+    elif out.dtype != torch.float32 or out.numel() != 3 * c or not out.is_contiguous() or out.device != vecs[0].device:
+        raise ValueError("bn_infer_consts: out must be a contiguous float32 [3, C] tensor on the vectors' device")
+    _lib.check(_lib.lib().mhaq_fq_bn_infer_consts(*(None if t is None else t.data_ptr() for t in vecs), float(eps), c,
+                                                  out.data_ptr(), _stream()), "mhaq_fq_bn_infer_consts")
+    return out
+
+
+@_on_device
+def bn_infer_act(x, consts, mode=BN_RELU, x2=None, consts2=None, residual=None):
+    """relu(bn(x)), relu(bn(x) + residual) or relu(bn(x) + bn2(x2)) of dense float32 channels_last tensors in one launch
+    (mhaq_fq_bn_infer_act; no autograd), with the slabs of bn_infer_consts."""
+    x = _nhwc_f32(x, "x")
+    c = x.shape[1]
+    others = [None if t is None else _nhwc_f32(t, name) for t, name in ((x2, "x2"), (residual, "residual"))]
+    if any(t is not None and (t.shape != x.shape or t.device != x.device) for t in others):
+        raise ValueError("bn_infer_act: x2 and residual must have x's shape and device")
+    slabs = [None if k is None else _require_cuda_f32(k.detach(), "a constant slab") for k in (consts, consts2)]
+    if any(k is not None and (k.numel() != 3 * c or k.device != x.device) for k in slabs):
+        raise ValueError("bn_infer_act: a constant slab must be [3, C] on x's device")
+    y = torch.empty_like(x)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    _lib.check(_lib.lib().mhaq_fq_bn_infer_act(x.data_ptr(), ptr(slabs[0]), ptr(others[0]), ptr(slabs[1]), ptr(others[1]),
+                                               y.data_ptr(), x.numel() // max(c, 1), c, int(mode), _stream()),
+               "mhaq_fq_bn_infer_act")
+    return y
+
+
+@_on_device
+def bn_relu_pool(x, consts):
+    """max_pool2d(relu(bn(x)), 3, 2, 1) of a dense float32 channels_last tensor in one launch (mhaq_fq_bn_relu_pool3s2; no
+    autograd), the BatchNorm output never stored."""
+    x = _nhwc_f32(x, "x")
+    n, c, h, w = x.shape
+    k = _require_cuda_f32(consts.detach(), "the constant slab")
+    if k.numel() != 3 * c or k.device != x.device:
+        raise ValueError("bn_relu_pool: the constant slab must be [3, C] on x's device")
+    p = torch.empty((n, c, (h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=x.dtype, device=x.device,
+                    memory_format=torch.channels_last)
+    _lib.check(_lib.lib().mhaq_fq_bn_relu_pool3s2(x.data_ptr(), k.data_ptr(), p.data_ptr(), n, h, w, c, _stream()),
+               "mhaq_fq_bn_relu_pool3s2")
+    return p
+
+
 # ----------------------------------------------------------------------------- per-tensor op
 def _pt_forward(x, s, zp, lo, hi, want_q=False, want_stats=False):
     L = _lib.lib()

@@ -71,6 +71,9 @@ class QATConfig:
     # ... and the FORWARD of float32 inputs on mhaq_fq_bn_fwd, where hip_bn_backward installs (the bits of y and of the saved
     # and running statistics change).  Off by default; MHAQ_BN_FORWARD=1 / 0 in the environment overrides it.
     hip_bn_forward: bool = False
+    # the frozen teacher's BatchNorm, ReLU, residual add and stem pool in one HIP launch per place (frozen_blocks.py; fp32,
+    # agrees with the stock eval modules to rounding, not bit for bit).  MHAQ_TEACHER_FUSED=0 in the environment switches it off.
+    fuse_teacher: bool = True
     criterion: nn.Module = field(default_factory=nn.CrossEntropyLoss)
     # mixed precision (the reference trainer's `precision = "bf16-mixed"`, training/trainer.py:126): torch.bfloat16 runs
     # the teacher and student forwards, the loss and validate_step's forward under torch.autocast; the activation
@@ -231,6 +234,10 @@ class QATTrainer:
             if bn_backward.enabled_by_env():
                 bn_backward.install(net, x16=bn_backward.x16_enabled(cfg.hip_bn_backward_16bit),
                                     hip_forward=bn_backward.hip_forward_enabled(cfg.hip_bn_forward))
+        if cfg.fuse_teacher and cfg.distillation and layers is None and self.device.type == "cuda":
+            from . import frozen_blocks
+            if frozen_blocks.enabled_by_env():
+                frozen_blocks.install(self.teacher)
         self.net = net
         self.teacher_stream = None
         if cfg.distillation and cfg.overlap_teacher and self.device.type == "cuda":
