@@ -455,6 +455,54 @@ int mhaq_fq_bn_infer_act(const float* x, const float* consts, const float* x2, c
 int mhaq_fq_bn_relu_pool3s2(const float* x, const float* consts, float* p, int64_t n, int64_t h, int64_t w, int64_t c,
                             void* stream);
 
+/* ------------------------------------------------------------------------
+ * One-pass RAdam: the optimizer step of every parameter tensor of a model in ONE launch, with the bits of
+ * torch.optim.RAdam(foreach=True) on the same device (weight_decay = 0, maximize off, not capturable).  Additive to ABI v4 --
+ * MHAQ_FQ_ABI_VERSION stays 4; a caller discovers these entry points by symbol.
+ *
+ * A descriptor names one tensor's four streams -- p, g = p.grad, m = exp_avg, v = exp_avg_sq: fp32, n elements each, dense,
+ * all four in the SAME memory order, at least 4-byte aligned, p / m / v overlapping nothing -- and its two scalars, which the
+ * host computes in double precision as _multi_tensor_radam's non-capturable branch does and rounds to fp32 once:
+ *   c1 = float(unrect_step_size)   = -lr / bias_correction1 while rho_t <= 5, then 0
+ *   c2 = float(bias_correction2)   = -0.0 while rho_t <= 5, then -sqrt(1 - beta2^t) * lr * rect / bias_correction1
+ * Per element, in fp32, each line rounded once (sqrt and both divisions correctly rounded):
+ *   m = lerp(m, g, w1)                  w1 = float(1 - beta1);  |w1| < 0.5 ? m + w1 * (g - m) : g - (g - m) * (1 - w1)
+ *   v = v * beta2                       beta2 = float(beta2)
+ *   v = v + w2 * (g * g)                w2 = float(1 - beta2)
+ *   b = sqrt(v);  b = b + eps;  b = b / c2;  b = 1 / b;  b = b + c1
+ *   p = p + m * b
+ * "Rounded once" includes the framework's contractions, measured on the device against its foreach kernels (DESIGN
+ * section 14): the multiply-adds of the lerp and of the second moment are FUSED -- m = fmaf(w1, g - m, m),
+ * v = fmaf(w2, g * g, v) --, and the last line is fmaf(1, m * b, p) with the 1 a run-time operand, as the framework's
+ * addcmul multiplies by its `value`: that rounds like p + m * b, and where p and m * b are both NaN it keeps the bits
+ * (the sign) the framework keeps.  While c2 is -0.0 the chain runs through -inf and -0.0 to b = c1: plain IEEE
+ * operations, nothing special-cased.  NaN and infinities propagate as in the framework's chain, bit for bit.
+ *
+ * Geometry: `work_device` lists the launch's blocks: block i updates chunk `chunk` -- elements [chunk * C, min(n, chunk * C +
+ * C)), C = mhaq_fq_radam_chunk_elements() -- of tensor `tensor` of the table.  The host lists every chunk of every tensor
+ * exactly once, in any order.  A chunk whose four addresses are 16-byte aligned moves 16 bytes per access, any other one
+ * dwords.  An entry outside the table or the tensor is skipped.  No atomics, no workspace: 7 passes over the data.
+ * Argument errors are returned before the launch: negative counts, NULL tables with work to do (MHAQ_FQ_EINVAL), more
+ * than 2^31 - 1 blocks (MHAQ_FQ_EUNSUPPORTED), tables not 8-byte aligned (MHAQ_FQ_EALIGN); nwork == 0 is a valid empty step.
+ * The tables are read by the kernel: they stay untouched until the launch has run.  Stream-ordered, no host
+ * synchronisation, stateless.  (A CAPTURED launch would freeze c1 / c2, which change every step: step eagerly.)
+ * ---------------------------------------------------------------------- */
+typedef struct {
+  float* p;        /* the parameter, updated in place */
+  const float* g;  /* its gradient */
+  float* m;        /* exp_avg, updated in place */
+  float* v;        /* exp_avg_sq, updated in place */
+  int64_t n;       /* elements */
+  float c1, c2;    /* this tensor's scalars at its own step count */
+} mhaq_radam_desc;
+typedef struct {
+  int32_t tensor;  /* index into the descriptor table */
+  int32_t chunk;   /* chunk of that tensor */
+} mhaq_radam_work;
+int64_t mhaq_fq_radam_chunk_elements(void);
+int mhaq_fq_radam_step(const mhaq_radam_desc* descs_device, int ntensors, const mhaq_radam_work* work_device,
+                       int64_t nwork, float w1, float beta2, float w2, float eps, void* stream);
+
 /* Whole-tensor min / max (zero point of a PER_TENSOR weight quantizer,
  * gdnsq_conv2d.py:82-83; min/max observer, calib/minmaxobserver.py:19-36).
  * out[0] = min, out[1] = max. */

@@ -58,7 +58,8 @@ namespace {
   X(mhaq_fq_bn_bwd_workspace_bytes) X(mhaq_fq_bn_bwd) X(mhaq_fq_maxpool3s2_fwd)                                       \
   X(mhaq_fq_bn_pool_bwd_workspace_bytes) X(mhaq_fq_bn_pool_bwd) X(mhaq_fq_bn_bwd_x16_workspace_bytes)                 \
   X(mhaq_fq_bn_bwd_x16) X(mhaq_fq_bn_fwd_workspace_bytes) X(mhaq_fq_bn_fwd)                                         \
-  X(mhaq_fq_bn_infer_consts) X(mhaq_fq_bn_infer_act) X(mhaq_fq_bn_relu_pool3s2)
+  X(mhaq_fq_bn_infer_consts) X(mhaq_fq_bn_infer_act) X(mhaq_fq_bn_relu_pool3s2)                                     \
+  X(mhaq_fq_radam_chunk_elements) X(mhaq_fq_radam_step)
 
 struct Api {
 #define X(n) decltype(&::n) n = nullptr;
@@ -1585,6 +1586,99 @@ std::pair<Tensor, Tensor> potential_loss(const Tensor& base, const Tensor& las, 
   return {out[0], out[1]};
 }
 
+// ------------------------------------------------------------------------------------------------ one-pass RAdam
+// The optimizer step of mhaq_amd/optim.py (FusedRAdam) as ONE launch of mhaq_fq_radam_step.  The descriptor table changes
+// every step -- c1 / c2 follow the step count, and the gradients are new tensors after zero_grad(set_to_none=True) --, so it
+// comes from a TablePool: pinned staging, hipMemcpyAsync on the current stream, a ring of entries behind events.  The work
+// list depends on the tensors' sizes alone: a TableCache uploads it once.  No host synchronisation (an entry of the ring is
+// waited for only when the stream is 8 steps behind the host).
+struct RadamTables {
+  std::mutex mu;
+  std::map<std::pair<int, int64_t>, std::unique_ptr<TablePool>> descs;   // (device, capacity in descriptors)
+  std::map<int, TableCache> work;                                        // per device
+  static constexpr size_t kWorkLists = 4;
+  static constexpr int64_t kDescGrain = 64;
+};
+RadamTables& g_radam = *new RadamTables();     // never destroyed: it holds device tensors and HIP events
+std::atomic<int64_t> g_fused_radam_steps{0};   // launches of mhaq_fq_radam_step so far
+
+// equal strides once the dimensions of size 1 are dropped: the same element order in memory
+bool same_memory_order(const Tensor& a, const Tensor& b) {
+  if (a.sizes() != b.sizes()) return false;
+  for (int64_t d = 0; d < a.dim(); ++d)
+    if (a.size(d) != 1 && a.stride(d) != b.stride(d)) return false;
+  return true;
+}
+
+void radam_step(const std::vector<Tensor>& params, const std::vector<Tensor>& grads, const std::vector<Tensor>& exp_avgs,
+                const std::vector<Tensor>& exp_avg_sqs, const std::vector<double>& c1s, const std::vector<double>& c2s,
+                double beta1, double beta2, double eps) {
+  need_lib();
+  const size_t n = params.size();
+  TORCH_CHECK(grads.size() == n && exp_avgs.size() == n && exp_avg_sqs.size() == n && c1s.size() == n && c2s.size() == n,
+              "radam_step: the six lists must have one length");
+  if (n == 0) return;
+  TORCH_CHECK(!capturing(), "radam_step: a captured launch would freeze the step-dependent scalars; step eagerly");
+  const Tensor& like = params[0];
+  TORCH_CHECK(like.is_cuda(), "radam_step: device tensors are required (there is no CPU path)");
+  for (size_t i = 0; i < n; ++i) {
+    const Tensor& p = params[i];
+    for (const Tensor* t : {&p, &grads[i], &exp_avgs[i], &exp_avg_sqs[i]})
+      TORCH_CHECK(t->defined() && t->device() == like.device() && t->scalar_type() == at::kFloat &&
+                      t->is_non_overlapping_and_dense() && same_memory_order(*t, p),
+                  "radam_step: tensor ", i, ": p, grad, exp_avg and exp_avg_sq must be dense float32 tensors on one device "
+                  "in the same memory order");
+  }
+  MHAQ_ON_DEVICE_OF(like);
+  void* st = cur_stream(like);
+  const int dev = (int)like.device().index();
+  const int64_t chunk = A.mhaq_fq_radam_chunk_elements();
+  std::vector<mhaq_radam_desc> descs(n);
+  std::vector<int64_t> key, sizes;
+  key.reserve(6 * n);
+  sizes.reserve(n);
+  int64_t nwork = 0;
+  for (size_t i = 0; i < n; ++i) {
+    mhaq_radam_desc& d = descs[i];
+    d.p = fptr_mut(params[i]);
+    d.g = fptr(grads[i]);
+    d.m = fptr_mut(exp_avgs[i]);
+    d.v = fptr_mut(exp_avg_sqs[i]);
+    d.n = params[i].numel();
+    d.c1 = (float)c1s[i];
+    d.c2 = (float)c2s[i];
+    int64_t scalars;
+    static_assert(sizeof(scalars) == 2 * sizeof(float), "two floats per key word");
+    std::memcpy(&scalars, &d.c1, sizeof(scalars));
+    for (int64_t w : {(int64_t)(uintptr_t)d.p, (int64_t)(uintptr_t)d.g, (int64_t)(uintptr_t)d.m, (int64_t)(uintptr_t)d.v,
+                      d.n, scalars})
+      key.push_back(w);
+    sizes.push_back(d.n);
+    nwork += (d.n + chunk - 1) / chunk;
+  }
+  if (nwork == 0) return;
+  std::lock_guard<std::mutex> guard(g_radam.mu);
+  const int64_t cap = ((int64_t)n + RadamTables::kDescGrain - 1) / RadamTables::kDescGrain * RadamTables::kDescGrain;
+  auto& pool = g_radam.descs[{dev, cap}];
+  if (!pool) pool = std::make_unique<TablePool>(sizeof(mhaq_radam_desc) * (size_t)cap, like);
+  const Tensor& dtab = pool->get(key, [&](void* host) {
+    std::memset(host, 0, sizeof(mhaq_radam_desc) * (size_t)cap);
+    std::memcpy(host, descs.data(), sizeof(mhaq_radam_desc) * n);
+  }, st);
+  const Tensor wtab = g_radam.work[dev].get(sizes, RadamTables::kWorkLists, like, [&]() {
+    std::vector<mhaq_radam_work> w;
+    w.reserve((size_t)nwork);
+    for (size_t i = 0; i < n; ++i)
+      for (int64_t c = 0; c * chunk < sizes[i]; ++c) w.push_back({(int32_t)i, (int32_t)c});
+    return w;
+  });
+  check(A.mhaq_fq_radam_step(static_cast<const mhaq_radam_desc*>(dtab.const_data_ptr()), (int)n,
+                             static_cast<const mhaq_radam_work*>(wtab.const_data_ptr()), nwork, (float)(1.0 - beta1),
+                             (float)beta2, (float)(1.0 - beta2), (float)eps, st),
+        "mhaq_fq_radam_step");
+  g_fused_radam_steps.fetch_add(1, std::memory_order_relaxed);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1734,4 +1828,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   });
 
   m.def("potential_loss", &potential_loss);
+  m.def("radam_step", &radam_step, py::arg("params"), py::arg("grads"), py::arg("exp_avgs"), py::arg("exp_avg_sqs"),
+        py::arg("c1s"), py::arg("c2s"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
+        "one launch of mhaq_fq_radam_step over the listed tensors (mhaq_amd/optim.py)");
+  m.def("fused_radam_steps", []() { return g_fused_radam_steps.load(); },
+        "launches of mhaq_fq_radam_step so far (tests: the optimizer step took the HIP kernel)");
 }

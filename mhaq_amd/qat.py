@@ -74,6 +74,10 @@ class QATConfig:
     # the frozen teacher's BatchNorm, ReLU, residual add and stem pool in one HIP launch per place (frozen_blocks.py; fp32,
     # agrees with the stock eval modules to rounding, not bit for bit).  MHAQ_TEACHER_FUSED=0 in the environment switches it off.
     fuse_teacher: bool = True
+    # the optimizer step as one HIP launch (optim.py: FusedRAdam, the bits of torch.optim.RAdam's foreach form) where the
+    # trainer builds the optimizer itself, on a GPU; an optimizer_factory is never replaced.  MHAQ_FUSED_RADAM=1 / 0 in the
+    # environment overrides it.
+    fused_optimizer: bool = True
     criterion: nn.Module = field(default_factory=nn.CrossEntropyLoss)
     # mixed precision (the reference trainer's `precision = "bf16-mixed"`, training/trainer.py:126): torch.bfloat16 runs
     # the teacher and student forwards, the loss and validate_step's forward under torch.autocast; the activation
@@ -317,7 +321,8 @@ class QATTrainer:
             self.loss = loss_classes[1](cfg.criterion, p=1, a=cfg.act_bit, w=cfg.weight_bit)
         # hipGraph option (single GPU): after three eager steps the device work of a step up to the gradients --
         # teacher and student forward, loss, backward, ~500 launches -- is captured once and replayed; the optimizer
-        # then steps eagerly on the static gradient tensors (its ordinary foreach form: torch's graph-capturable
+        # then steps eagerly on the static gradient tensors (optim.FusedRAdam's one launch, or torch's ordinary foreach
+        # form; neither is captured: torch's graph-capturable
         # RAdam costs +5 ms per ResNet-18 step, measured in tools/graph_probe.py, which more than ate the gain).  It
         # pays where the host is the limit (ResNet-20 at batch 128: 11 ms/step of Python).  Everything a replay must
         # see fresh lives on the device: the loss state {loss_sum, cnt, t} and the offset of the random sign
@@ -353,7 +358,12 @@ class QATTrainer:
             # the default stream cannot take part in a capture
             self._gstream = torch.cuda.Stream(device=self.device)
         # RAdam as in every shipped config (vision_cls_module.py:54-55); a factory may override it
-        self.optimizer = (optimizer_factory or torch.optim.RAdam)(self.net.parameters(), cfg.learning_rate)
+        make_optimizer = optimizer_factory or torch.optim.RAdam
+        if optimizer_factory is None and self.device.type == "cuda":
+            from . import optim
+            if optim.enabled(cfg.fused_optimizer):
+                make_optimizer = optim.FusedRAdam
+        self.optimizer = make_optimizer(self.net.parameters(), cfg.learning_rate)
         self.schedule = TemperatureSchedule(cfg.learning_rate, cfg.warmup, cfg.scale_lr, cfg.scale_t)
         self.schedule.start(self.optimizer)
 
