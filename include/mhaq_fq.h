@@ -456,6 +456,28 @@ int mhaq_fq_bn_relu_pool3s2(const float* x, const float* consts, float* p, int64
                             void* stream);
 
 /* ------------------------------------------------------------------------
+ * The same two launches on 16-bit tensors (the frozen network under torch.autocast).  Additive to ABI v4 --
+ * MHAQ_FQ_ABI_VERSION stays 4; a caller discovers these entry points by symbol.  x, x2, residual, y and p are dense NHWC tensors
+ * of the type named by `dtype` (MHAQ_FQ_DT_BF16 or MHAQ_FQ_DT_F16, anything else: MHAQ_FQ_EINVAL); c % 8 == 0 and c <= 2^22
+ * (else MHAQ_FQ_EUNSUPPORTED; the pool keeps n * h * w < 2^31); tensors and slabs 16-byte aligned (else MHAQ_FQ_EALIGN).  The
+ * constant slabs are mhaq_fq_bn_infer_consts's fp32 [3][c], unchanged.  A mode's operands are required or refused as above.
+ * Argument errors are returned before any launch, in the fp32 entry points' order with the dtype behind the NULL, size and
+ * mode checks: required pointers, positive sizes, a known mode and its operands, the dtype (MHAQ_FQ_EINVAL); width and
+ * range; the alignment.
+ *
+ * The arithmetic is the fp32 contract on the exactly upcast inputs, rounded ONCE to nearest-even at the end:
+ *   y = R16(relu(fl32((up(x) - mean) * a + bias  [+ up(residual)]  [+ t2])))
+ * uncontracted, in the fp32 order, the sum rounded to fp32 before the ReLU; relu keeps a NaN and a NaN stays a NaN in 16 bits
+ * (its payload is not specified); an fp16 result beyond the fp16 range is +-inf, as a cast gives.
+ *   p = R16(max_pool2d(relu(t), 3, 2, 1))  with mhaq_fq_maxpool3s2_fwd's selection on the fp32 values.
+ * Each is one launch: stream-ordered, no host synchronisation, capture-safe, stateless.  y must not overlap an input.
+ * ---------------------------------------------------------------------- */
+int mhaq_fq_bn_infer_act_x16(const void* x, const float* consts, const void* x2, const float* consts2, const void* residual,
+                             void* y, int64_t m, int64_t c, int mode, int dtype, void* stream);
+int mhaq_fq_bn_relu_pool3s2_x16(const void* x, const float* consts, void* p, int64_t n, int64_t h, int64_t w, int64_t c,
+                                int dtype, void* stream);
+
+/* ------------------------------------------------------------------------
  * One-pass RAdam: the optimizer step of every parameter tensor of a model in ONE launch, with the bits of
  * torch.optim.RAdam(foreach=True) on the same device (weight_decay = 0, maximize off, not capturable).  Additive to ABI v4 --
  * MHAQ_FQ_ABI_VERSION stays 4; a caller discovers these entry points by symbol.

@@ -75,6 +75,9 @@ SIGNATURES = {
     "mhaq_fq_bn_infer_consts": (_int, [_p, _p, _p, _p, C.c_double, _i64, _p, _p]),
     "mhaq_fq_bn_infer_act": (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _int, _p]),
     "mhaq_fq_bn_relu_pool3s2": (_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _p]),
+    # ... and on 16-bit tensors: `dtype` before the stream (additive, ABI v4 kept)
+    "mhaq_fq_bn_infer_act_x16": (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _int, _int, _p]),
+    "mhaq_fq_bn_relu_pool3s2_x16": (_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _int, _p]),
     # one-pass RAdam over a descriptor table and a (tensor, chunk) work list (additive, ABI v4 kept)
     "mhaq_fq_radam_chunk_elements": (_i64, []),
     "mhaq_fq_radam_step": (_int, [_p, _int, _p, _i64, C.c_float, C.c_float, C.c_float, C.c_float, _p]),

@@ -946,7 +946,90 @@ __launch_bounds__(kBlock) void bn_infer_act_kernel(
   }
 }
 
-// Status of the two elementwise entry points before anything is launched, in bn_fwd_status's order: required pointers,
+// The same launch on 16-bit tensors of the element type DT (mhaq_fq_bn_infer_act_x16: the teacher under autocast): one 16-byte
+// access per lane and stream is 8 channels, so 24 constants per slab, and cv = C / 8 in the column arithmetic.  A 16-bit element
+// is converted UP exactly and takes the expression above unchanged -- the sum is rounded to fp32 before the ReLU --; the result is
+// rounded to nearest-even ONCE on the way out (io16::down2: a plain cast, a NaN stays a NaN, fp16 overflow gives +-inf).  The
+// store is NOT Io16::st, which is non-temporal: the next convolution reads y.
+// Cache policy of the loads: the fp32 byte rule (the input streams together above 224 MiB = 112 Mi 16-bit elements); occupancy
+// by elements, as in fq_io16.hip.  Each can be overridden at build time (tools/teacher_fwd_bench.py --dtype bf16 times builds
+// with forced policies next to the product's).
+#ifndef MHAQ_BN_INFER16_NT_ELEMS
+#define MHAQ_BN_INFER16_NT_ELEMS (112ll << 20)
+#endif
+#ifndef MHAQ_BN_INFER16_BIG_ELEMS
+#define MHAQ_BN_INFER16_BIG_ELEMS (20ll << 20)
+#endif
+#ifndef MHAQ_BN_INFER16_ST_NT
+#define MHAQ_BN_INFER16_ST_NT 0
+#endif
+constexpr int64_t kBnInfer16NtElems = MHAQ_BN_INFER16_NT_ELEMS;
+constexpr int64_t kBnInfer16BigElems = MHAQ_BN_INFER16_BIG_ELEMS;
+constexpr bool kBnInfer16StNt = MHAQ_BN_INFER16_ST_NT != 0;
+
+template <bool NT, bool BIG, int MODE, int DT>
+__global__ __attribute__((amdgpu_waves_per_eu(
+    (BIG ? 1 : kBnFwdWaves<Io16<DT>>),
+    (BIG && kBnBigMaxWaves < kBnFwdWaves<Io16<DT>> ? kBnBigMaxWaves : kBnFwdWaves<Io16<DT>>))))
+__launch_bounds__(kBlock) void bn_infer_act16_kernel(
+    const uint16_t* __restrict__ x, const uint16_t* __restrict__ x2, uint16_t* __restrict__ y, int64_t nvec, int cv,
+    const float* __restrict__ k1, const float* __restrict__ k2) {
+  using IO = Io16<DT>;
+  constexpr bool kTwo = MODE != MHAQ_FQ_BN_RELU, kBn2 = MODE == MHAQ_FQ_BN2_ADD_RELU;
+  const int64_t blk0 = (int64_t)blockIdx.x * (kBlock * kBnDxU);
+  const int64_t base = blk0 + threadIdx.x;
+  const bool full = blk0 + kBlock * kBnDxU <= nvec;
+  io16::vu4 a[kBnDxU], b[kBnDxU];
+#pragma unroll
+  for (int u = 0; u < kBnDxU; ++u) {
+    const int64_t idx = base + u * kBlock;
+    const int64_t idc = (full || idx < nvec) ? idx : nvec - 1;
+    a[u] = io16::ld8<NT>(x, idc);
+    if constexpr (kTwo) b[u] = io16::ld8<NT>(x2, idc);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  const uint32_t ucv = (uint32_t)cv;
+  const uint32_t cb = ((blockIdx.x % ucv) * ((uint32_t)(kBlock * kBnDxU) % ucv)) % ucv;      // wave-uniform
+  const uint32_t step = (uint32_t)kBlock % ucv;                                               // wave-uniform
+  uint32_t col = (cb + threadIdx.x) % ucv;
+  const int64_t c = (int64_t)cv * 8;
+  float k[kBnFwdNConst][2][4], kk[kBnFwdNConst][2][4];
+#pragma unroll
+  for (int u = 0; u < kBnDxU; ++u) {
+    const int64_t idx = base + u * kBlock;
+    if (u > 0) {
+      col += step;
+      if (col >= ucv) col -= ucv;
+    }
+    if (u == 0 || step != 0) {
+#pragma unroll
+      for (int q = 0; q < kBnFwdNConst; ++q)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          ldv<4>(k1 + q * c + (int64_t)col * 8 + 4 * h, k[q][h]);
+          if constexpr (kBn2) ldv<4>(k2 + q * c + (int64_t)col * 8 + 4 * h, kk[q][h]);
+        }
+    }
+    if (full || idx < nvec) {
+      float xv[8], bv[8], o[8];
+      IO::unpack(a[u], xv);
+      if constexpr (kTwo) IO::unpack(b[u], bv);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int h = j >> 2, i = j & 3;
+        float t = (xv[j] - k[0][h][i]) * k[1][h][i] + k[2][h][i];
+        if constexpr (kTwo) t = t + (kBn2 ? (bv[j] - kk[0][h][i]) * kk[1][h][i] + kk[2][h][i] : bv[j]);
+        o[j] = bn_relu(t);
+      }
+      io16::vu4 v;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) v[w] = io16::down2<DT>(o[2 * w], o[2 * w + 1]);
+      io16::st8<kBnInfer16StNt>(y, idx, v);
+    }
+  }
+}
+
+// Status of the elementwise entry points before anything is launched, in bn_fwd_status's order: required pointers,
 // positive sizes and a known mode; width and range; (no workspace;) the alignment -- the constant rows are read 16 bytes at a time.
 static int bn_infer_consts_status(const float* mean, const float* var, const float* weight, const float* bias, int64_t c,
                                   const float* consts) {
@@ -958,15 +1041,17 @@ static int bn_infer_consts_status(const float* mean, const float* var, const flo
   return 0;
 }
 // A mode's own operands are required and the other mode's refused: a residual with BN_ADD_RELU only, x2 and consts2 with
-// BN2_ADD_RELU only.
-static int bn_infer_act_status(const float* x, const float* consts, const float* x2, const float* consts2,
-                               const float* residual, const float* y, int64_t m, int64_t c, int mode) {
+// BN2_ADD_RELU only.  kw: the channels of a lane's 16 bytes (4, or 8 with the dtype of a 16-bit call, checked behind the mode
+// as in bn_bwd_status).
+static int bn_infer_act_status(const void* x, const float* consts, const void* x2, const float* consts2,
+                               const void* residual, const void* y, int64_t m, int64_t c, int mode, int kw, int dtype) {
   if (!x || !consts || !y || m <= 0 || c <= 0) return MHAQ_FQ_EINVAL;
   if (mode != MHAQ_FQ_BN_RELU && mode != MHAQ_FQ_BN_ADD_RELU && mode != MHAQ_FQ_BN2_ADD_RELU) return MHAQ_FQ_EINVAL;
   if (!residual != (mode != MHAQ_FQ_BN_ADD_RELU) || !x2 != (mode != MHAQ_FQ_BN2_ADD_RELU) || !x2 != !consts2)
     return MHAQ_FQ_EINVAL;
-  if ((c & 3) || c > kBnMaxChannels || m > (INT64_MAX >> 3) / c ||
-      (m * (c >> 2) + kBlock * kBnDxU - 1) / (kBlock * kBnDxU) > 0x7fffffff)
+  if (kw == 8 && !io16::known_dtype(dtype)) return MHAQ_FQ_EINVAL;
+  if ((c & (kw - 1)) || c > kBnMaxChannels || m > (INT64_MAX >> 3) / c ||
+      (m * (c / kw) + kBlock * kBnDxU - 1) / (kBlock * kBnDxU) > 0x7fffffff)
     return MHAQ_FQ_EUNSUPPORTED;
   if (!bn_aligned(x, 16) || !bn_aligned(consts, 16) || !bn_aligned(x2, 16) || !bn_aligned(consts2, 16) ||
       !bn_aligned(residual, 16) || !bn_aligned(y, 16))
@@ -984,6 +1069,19 @@ static int bn_infer_act_launch(const float* x, const float* k1, const float* x2,
   MHAQ_LAUNCH((big ? (nt ? bn_infer_act_kernel<true, true, MODE> : bn_infer_act_kernel<false, true, MODE>)
                    : (nt ? bn_infer_act_kernel<true, false, MODE> : bn_infer_act_kernel<false, false, MODE>)),
               dim3((unsigned)grid), dim3(kBlock), 0, st, x, x2, y, nvec, (int)(c >> 2), k1, k2);
+  return launch_status();
+}
+// ... and on 16-bit elements: the cache policy by the bytes of the input streams, the occupancy by elements
+template <int MODE, int DT>
+static int bn_infer_act16_launch(const void* x, const float* k1, const void* x2, const float* k2, void* y, int64_t m,
+                                 int64_t c, hipStream_t st) {
+  const int64_t nvec = m * (c >> 3);
+  const int64_t grid = (nvec + kBlock * kBnDxU - 1) / (kBlock * kBnDxU);
+  const bool nt = m * c * (MODE == MHAQ_FQ_BN_RELU ? 1 : 2) >= kBnInfer16NtElems, big = m * c >= kBnInfer16BigElems;
+  MHAQ_LAUNCH((big ? (nt ? bn_infer_act16_kernel<true, true, MODE, DT> : bn_infer_act16_kernel<false, true, MODE, DT>)
+                   : (nt ? bn_infer_act16_kernel<true, false, MODE, DT> : bn_infer_act16_kernel<false, false, MODE, DT>)),
+              dim3((unsigned)grid), dim3(kBlock), 0, st, (const uint16_t*)x, (const uint16_t*)x2, (uint16_t*)y, nvec,
+              (int)(c >> 3), k1, k2);
   return launch_status();
 }
 
@@ -1141,6 +1239,60 @@ __global__ __launch_bounds__(kBlock) void maxpool3s2_fwd16_kernel(
                                           cd[4] | (cd[5] << 8) | (cd[6] << 16) | (cd[7] << 24)};
 }
 
+// The frozen stem on a dense 16-bit NHWC x (mhaq_fq_bn_relu_pool3s2_x16): the kernel above without the codes and with the
+// constants of the lane's eight channels under the nine loads, as bn_relu_pool3s2_kernel relates to the fp32 pool forward.
+// Every in-range value is upcast exactly, takes bn_infer_act_kernel's fp32 arithmetic and is compared in fp32; the maximum is
+// rounded to 16 bits ONCE at the end -- rounding is monotone, so this is the value of rounding all nine first, for 4 packed
+// converts instead of 36.  A NaN that wins stays a NaN through the cast.
+template <int DT>
+__global__ __launch_bounds__(kBlock) void bn_relu_pool3s2_16_kernel(
+    const uint16_t* __restrict__ x, uint16_t* __restrict__ p, uint32_t h, uint32_t w, uint32_t oh, uint32_t ow, uint32_t cv,
+    int64_t nvec, const float* __restrict__ consts) {
+  const uint32_t bq = blockIdx.x / cv, br = (blockIdx.x - bq * cv) * (uint32_t)kBlock, brq = br / cv;
+  const uint32_t tt = br - brq * cv + threadIdx.x, tq = tt / cv;
+  const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool ok = idx < nvec;
+  const uint32_t pixel = ok ? bq * (uint32_t)kBlock + brq + tq : 0u, col = tt - tq * cv;
+  const uint32_t q = pixel / ow, n = q / oh, po = q - n * oh, pw = pixel - q * ow;
+  const int ih0 = (int)(po * 2u) - 1, iw0 = (int)(pw * 2u) - 1;
+  io16::vu4 v[9];
+  bool in[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const int ih = ih0 + k / 3, iw = iw0 + k % 3;
+    in[k] = ih >= 0 && ih < (int)h && iw >= 0 && iw < (int)w;
+    const uint32_t ihc = (uint32_t)(ih < 0 ? 0 : (ih < (int)h ? ih : (int)h - 1));
+    const uint32_t iwc = (uint32_t)(iw < 0 ? 0 : (iw < (int)w ? iw : (int)w - 1));
+    v[k] = io16::ld8<false>(x, (int64_t)((n * h + ihc) * w + iwc) * cv + col);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  float kc[kBnFwdNConst][2][4];
+#pragma unroll
+  for (int r = 0; r < kBnFwdNConst; ++r)
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) ldv<4>(consts + ((int64_t)r * cv + col) * 8 + 4 * hh, kc[r][hh]);
+  if (!ok) return;
+  float mx[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) mx[j] = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    float e[8];
+    Io16<DT>::unpack(v[k], e);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int hh = j >> 2, i = j & 3;
+      const float r = bn_relu((e[j] - kc[0][hh][i]) * kc[1][hh][i] + kc[2][hh][i]);
+      const bool take = in[k] && (r > mx[j] || r != r);
+      mx[j] = take ? r : mx[j];
+    }
+  }
+  io16::vu4 pv;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) pv[i] = io16::down2<DT>(mx[2 * i], mx[2 * i + 1]);
+  reinterpret_cast<io16::vu4*>(p)[idx] = pv;
+}
+
 // pooled extent of kernel 3, stride 2, padding 1, dilation 1, ceil_mode = false
 static inline int64_t pool_out(int64_t in) { return (in - 1) / 2 + 1; }
 // n, h, w, c of a pool entry point (kw channels per lane): 0, or the error code
@@ -1248,11 +1400,41 @@ int mhaq_fq_bn_infer_consts(const float* running_mean, const float* running_var,
 
 int mhaq_fq_bn_infer_act(const float* x, const float* consts, const float* x2, const float* consts2, const float* residual,
                          float* y, int64_t m, int64_t c, int mode, void* stream) {
-  if (const int rc = bn_infer_act_status(x, consts, x2, consts2, residual, y, m, c, mode)) return rc;
+  if (const int rc = bn_infer_act_status(x, consts, x2, consts2, residual, y, m, c, mode, 4, 0)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (mode == MHAQ_FQ_BN_RELU) return bn_infer_act_launch<MHAQ_FQ_BN_RELU>(x, consts, nullptr, nullptr, y, m, c, st);
   if (mode == MHAQ_FQ_BN_ADD_RELU) return bn_infer_act_launch<MHAQ_FQ_BN_ADD_RELU>(x, consts, residual, nullptr, y, m, c, st);
   return bn_infer_act_launch<MHAQ_FQ_BN2_ADD_RELU>(x, consts, x2, consts2, y, m, c, st);
+}
+
+int mhaq_fq_bn_infer_act_x16(const void* x, const float* consts, const void* x2, const float* consts2, const void* residual,
+                             void* y, int64_t m, int64_t c, int mode, int dtype, void* stream) {
+  if (const int rc = bn_infer_act_status(x, consts, x2, consts2, residual, y, m, c, mode, 8, dtype)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  return io16::with_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    if (mode == MHAQ_FQ_BN_RELU) return bn_infer_act16_launch<MHAQ_FQ_BN_RELU, DT>(x, consts, nullptr, nullptr, y, m, c, st);
+    if (mode == MHAQ_FQ_BN_ADD_RELU)
+      return bn_infer_act16_launch<MHAQ_FQ_BN_ADD_RELU, DT>(x, consts, residual, nullptr, y, m, c, st);
+    return bn_infer_act16_launch<MHAQ_FQ_BN2_ADD_RELU, DT>(x, consts, x2, consts2, y, m, c, st);
+  });
+}
+
+int mhaq_fq_bn_relu_pool3s2_x16(const void* x, const float* consts, void* p, int64_t n, int64_t h, int64_t w, int64_t c,
+                                int dtype, void* stream) {
+  if (!x || !consts || !p) return MHAQ_FQ_EINVAL;
+  if (n <= 0 || h <= 0 || w <= 0 || c <= 0 || !io16::known_dtype(dtype)) return MHAQ_FQ_EINVAL;
+  if (const int rc = pool_dims_status(n, h, w, c, 8)) return rc;
+  const int64_t oh = pool_out(h), ow = pool_out(w), nvec = n * oh * ow * (c >> 3);
+  const int64_t grid = (nvec + kBlock - 1) / kBlock;
+  if (grid > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
+  if (!bn_aligned(x, 16) || !bn_aligned(consts, 16) || !bn_aligned(p, 16)) return MHAQ_FQ_EALIGN;
+  return io16::with_dtype(dtype, [&](auto dt) {
+    MHAQ_LAUNCH(bn_relu_pool3s2_16_kernel<decltype(dt)::value>, dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream,
+                (const uint16_t*)x, (uint16_t*)p, (uint32_t)h, (uint32_t)w, (uint32_t)oh, (uint32_t)ow, (uint32_t)(c >> 3),
+                nvec, consts);
+    return launch_status();
+  });
 }
 
 int mhaq_fq_bn_relu_pool3s2(const float* x, const float* consts, float* p, int64_t n, int64_t h, int64_t w, int64_t c,

@@ -59,6 +59,7 @@ namespace {
   X(mhaq_fq_bn_pool_bwd_workspace_bytes) X(mhaq_fq_bn_pool_bwd) X(mhaq_fq_bn_bwd_x16_workspace_bytes)                 \
   X(mhaq_fq_bn_bwd_x16) X(mhaq_fq_bn_fwd_workspace_bytes) X(mhaq_fq_bn_fwd)                                         \
   X(mhaq_fq_bn_infer_consts) X(mhaq_fq_bn_infer_act) X(mhaq_fq_bn_relu_pool3s2)                                     \
+  X(mhaq_fq_bn_infer_act_x16) X(mhaq_fq_bn_relu_pool3s2_x16)                                                        \
   X(mhaq_fq_radam_chunk_elements) X(mhaq_fq_radam_step)
 
 struct Api {
@@ -942,11 +943,15 @@ Tensor bn_pool_train(const Tensor& x, const std::optional<Tensor>& w, const std:
 // mhaq_fq_bn_infer_*).  Plain functions, not nodes: the teacher runs without grad.  The caller has settled that the place may
 // be fused; what arrives here and does not fit the kernels is an error, never a quiet framework path.  Outputs come from the
 // caching allocator, the launch goes to the current stream of the input's device: no host synchronisation, capture-safe.
-std::atomic<int64_t> g_teacher_fused_calls{0};   // launches of mhaq_fq_bn_infer_act and mhaq_fq_bn_relu_pool3s2 so far
+std::atomic<int64_t> g_teacher_fused_calls{0};   // launches of mhaq_fq_bn_infer_act and mhaq_fq_bn_relu_pool3s2 so far, fp32 and 16-bit
+std::atomic<int64_t> g_teacher_fused_x16_calls{0};   // ... of them, the 16-bit ones (mhaq_fq_bn_infer_act_x16 / _relu_pool3s2_x16)
 
-inline void check_frozen_input(const Tensor& x, const Tensor& consts, const char* what) {
-  TORCH_CHECK(bn_hip_eligible(x, Tensor()) && x.scalar_type() == at::kFloat, what,
-              ": x must be a non-empty dense channels_last float32 device tensor with C % 4 == 0");
+// x16: the caller takes bf16 / fp16 inputs too (C % 8 == 0); without it a 16-bit input is refused like any other non-fp32 one
+inline void check_frozen_input(const Tensor& x, const Tensor& consts, const char* what, bool x16 = false) {
+  TORCH_CHECK(bn_hip_eligible(x, Tensor()) && (x.scalar_type() == at::kFloat || x16), what,
+              x16 ? ": x must be a non-empty dense channels_last device tensor, float32 with C % 4 == 0 or bfloat16 / float16 "
+                    "with C % 8 == 0"
+                  : ": x must be a non-empty dense channels_last float32 device tensor with C % 4 == 0");
   TORCH_CHECK(consts.defined() && consts.is_cuda() && consts.device() == x.device() && consts.scalar_type() == at::kFloat &&
                   consts.is_contiguous() && consts.numel() == 3 * x.size(1) && aligned16(consts),
               what, ": the constants must be a contiguous float32 [3, C] slab on x's device");
@@ -970,33 +975,50 @@ void bn_infer_consts(const Tensor& running_mean, const Tensor& running_var, cons
         "mhaq_fq_bn_infer_consts");
 }
 
+// x16 (here and in bn_relu_pool): a bf16 / fp16 x takes the *_x16 entry point; an fp32 x takes the fp32 one either way.
 Tensor bn_infer_act(const Tensor& x, const Tensor& consts, int64_t mode, const std::optional<Tensor>& x2,
-                    const std::optional<Tensor>& consts2, const std::optional<Tensor>& residual) {
+                    const std::optional<Tensor>& consts2, const std::optional<Tensor>& residual, bool x16) {
   need_lib();
-  check_frozen_input(x, consts, "bn_infer_act");
+  check_frozen_input(x, consts, "bn_infer_act", x16);
   const Tensor b = opt_tensor(x2), k2 = opt_tensor(consts2), r = opt_tensor(residual);
   for (const Tensor* t : {&b, &r})
-    TORCH_CHECK(!t->defined() || (t->is_cuda() && t->device() == x.device() && t->scalar_type() == at::kFloat &&
+    TORCH_CHECK(!t->defined() || (t->is_cuda() && t->device() == x.device() && t->scalar_type() == x.scalar_type() &&
                                   t->sizes() == x.sizes() && t->strides() == x.strides() && aligned16(*t)),
                 "bn_infer_act: the second input and the residual must have x's dtype, device, sizes and strides");
-  if (b.defined()) check_frozen_input(b, k2, "bn_infer_act (second input)");
+  if (b.defined()) check_frozen_input(b, k2, "bn_infer_act (second input)", x16);
   MHAQ_ON_DEVICE_OF(x);
   const int64_t c = x.size(1), m = x.numel() / c;
+  const int dt = act_dtype(x);
   Tensor y = at::empty_like(x);
-  check(A.mhaq_fq_bn_infer_act(fptr(x), fptr(consts), fptr_or_null(b), fptr_or_null(k2), fptr_or_null(r), fptr_mut(y), m, c,
-                               (int)mode, cur_stream(x)),
-        "mhaq_fq_bn_infer_act");
+  if (dt) {
+    auto vptr = [](const Tensor& t) { return t.defined() ? t.const_data_ptr() : nullptr; };
+    check(A.mhaq_fq_bn_infer_act_x16(x.const_data_ptr(), fptr(consts), vptr(b), fptr_or_null(k2), vptr(r), y.mutable_data_ptr(),
+                                     m, c, (int)mode, dt, cur_stream(x)),
+          "mhaq_fq_bn_infer_act_x16");
+    g_teacher_fused_x16_calls.fetch_add(1, std::memory_order_relaxed);
+  } else {
+    check(A.mhaq_fq_bn_infer_act(fptr(x), fptr(consts), fptr_or_null(b), fptr_or_null(k2), fptr_or_null(r), fptr_mut(y), m, c,
+                                 (int)mode, cur_stream(x)),
+          "mhaq_fq_bn_infer_act");
+  }
   g_teacher_fused_calls.fetch_add(1, std::memory_order_relaxed);
   return y;
 }
 
-Tensor bn_relu_pool(const Tensor& x, const Tensor& consts) {
+Tensor bn_relu_pool(const Tensor& x, const Tensor& consts, bool x16) {
   need_lib();
-  check_frozen_input(x, consts, "bn_relu_pool");
+  check_frozen_input(x, consts, "bn_relu_pool", x16);
   MHAQ_ON_DEVICE_OF(x);
   const int64_t n = x.size(0), c = x.size(1), h = x.size(2), wd = x.size(3);
+  const int dt = act_dtype(x);
   Tensor p = at::empty({n, c, (h - 1) / 2 + 1, (wd - 1) / 2 + 1}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  check(A.mhaq_fq_bn_relu_pool3s2(fptr(x), fptr(consts), fptr_mut(p), n, h, wd, c, cur_stream(x)), "mhaq_fq_bn_relu_pool3s2");
+  if (dt) {
+    check(A.mhaq_fq_bn_relu_pool3s2_x16(x.const_data_ptr(), fptr(consts), p.mutable_data_ptr(), n, h, wd, c, dt, cur_stream(x)),
+          "mhaq_fq_bn_relu_pool3s2_x16");
+    g_teacher_fused_x16_calls.fetch_add(1, std::memory_order_relaxed);
+  } else {
+    check(A.mhaq_fq_bn_relu_pool3s2(fptr(x), fptr(consts), fptr_mut(p), n, h, wd, c, cur_stream(x)), "mhaq_fq_bn_relu_pool3s2");
+  }
   g_teacher_fused_calls.fetch_add(1, std::memory_order_relaxed);
   return p;
 }
@@ -1783,10 +1805,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_infer_consts", &bn_infer_consts, py::arg("running_mean"), py::arg("running_var"), py::arg("weight"),
         py::arg("bias"), py::arg("eps"), py::arg("consts"));
   m.def("bn_infer_act", &bn_infer_act, py::arg("x"), py::arg("consts"), py::arg("mode"), py::arg("x2") = py::none(),
-        py::arg("consts2") = py::none(), py::arg("residual") = py::none());
-  m.def("bn_relu_pool", &bn_relu_pool, py::arg("x"), py::arg("consts"));
+        py::arg("consts2") = py::none(), py::arg("residual") = py::none(), py::arg("x16") = false);
+  m.def("bn_relu_pool", &bn_relu_pool, py::arg("x"), py::arg("consts"), py::arg("x16") = false);
   m.def("teacher_fused_calls", []() { return g_teacher_fused_calls.load(); },
-        "number of fused launches so far on a frozen network's elementwise chain (bn_infer_act and bn_relu_pool)");
+        "number of fused launches so far on a frozen network's elementwise chain (bn_infer_act and bn_relu_pool), 16-bit included");
+  m.def("teacher_fused_x16_calls", []() { return g_teacher_fused_x16_calls.load(); },
+        "number of those launches that took the 16-bit entry points (mhaq_fq_bn_infer_act_x16, mhaq_fq_bn_relu_pool3s2_x16)");
 
   // weight layers
   m.def("weight_layer", &weight_layer, py::arg("w"), py::arg("log_wght_s"), py::arg("method"),

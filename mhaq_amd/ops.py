@@ -434,6 +434,52 @@ def bn_relu_pool(x, consts):
     return p
 
 
+def _nhwc_x16(t, name):
+    t = t.detach()
+    if not t.is_cuda:
+        raise _lib.MhaqFqError(f"{name} is on {t.device}: the kernels run only on an MI355X (no CPU fallback by design)")
+    if t.dtype not in _X16:
+        raise TypeError(f"{name} must be bfloat16 or float16, got {t.dtype}")
+    if t.dim() != 4 or not t.is_contiguous(memory_format=torch.channels_last):
+        raise ValueError(f"{name} must be a dense channels_last [N, C, H, W] tensor")
+    return t
+
+
+@_on_device
+def bn_infer_act_x16(x, consts, mode=BN_RELU, x2=None, consts2=None, residual=None):
+    """bn_infer_act on dense channels_last bfloat16 / float16 tensors (mhaq_fq_bn_infer_act_x16; no autograd): the fp32
+    arithmetic on the upcast inputs with the float32 slabs of bn_infer_consts, rounded once into a y of x's dtype."""
+    x = _nhwc_x16(x, "x")
+    c = x.shape[1]
+    others = [None if t is None else _nhwc_x16(t, name) for t, name in ((x2, "x2"), (residual, "residual"))]
+    if any(t is not None and (t.shape != x.shape or t.device != x.device or t.dtype != x.dtype) for t in others):
+        raise ValueError("bn_infer_act_x16: x2 and residual must have x's shape, dtype and device")
+    slabs = [None if k is None else _require_cuda_f32(k.detach(), "a constant slab") for k in (consts, consts2)]
+    if any(k is not None and (k.numel() != 3 * c or k.device != x.device) for k in slabs):
+        raise ValueError("bn_infer_act_x16: a constant slab must be [3, C] on x's device")
+    y = torch.empty_like(x)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    _lib.check(_lib.lib().mhaq_fq_bn_infer_act_x16(x.data_ptr(), ptr(slabs[0]), ptr(others[0]), ptr(slabs[1]), ptr(others[1]),
+                                                   y.data_ptr(), x.numel() // max(c, 1), c, int(mode), _X16[x.dtype],
+                                                   _stream()), "mhaq_fq_bn_infer_act_x16")
+    return y
+
+
+@_on_device
+def bn_relu_pool_x16(x, consts):
+    """bn_relu_pool on a dense channels_last bfloat16 / float16 tensor (mhaq_fq_bn_relu_pool3s2_x16; no autograd)."""
+    x = _nhwc_x16(x, "x")
+    n, c, h, w = x.shape
+    k = _require_cuda_f32(consts.detach(), "the constant slab")
+    if k.numel() != 3 * c or k.device != x.device:
+        raise ValueError("bn_relu_pool_x16: the constant slab must be [3, C] on x's device")
+    p = torch.empty((n, c, (h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=x.dtype, device=x.device,
+                    memory_format=torch.channels_last)
+    _lib.check(_lib.lib().mhaq_fq_bn_relu_pool3s2_x16(x.data_ptr(), k.data_ptr(), p.data_ptr(), n, h, w, c, _X16[x.dtype],
+                                                      _stream()), "mhaq_fq_bn_relu_pool3s2_x16")
+    return p
+
+
 # ----------------------------------------------------------------------------- per-tensor op
 def _pt_forward(x, s, zp, lo, hi, want_q=False, want_stats=False):
     L = _lib.lib()

@@ -74,6 +74,10 @@ class QATConfig:
     # the frozen teacher's BatchNorm, ReLU, residual add and stem pool in one HIP launch per place (frozen_blocks.py; fp32,
     # agrees with the stock eval modules to rounding, not bit for bit).  MHAQ_TEACHER_FUSED=0 in the environment switches it off.
     fuse_teacher: bool = True
+    # ... and on the 16-bit tensors its places see under autocast_dtype (mhaq_fq_bn_infer_act_x16 / _relu_pool3s2_x16: the fp32
+    # arithmetic on the upcast inputs, rounded once, where the stock bf16 modules round after every op; the teacher's logits
+    # change in their last bf16 bits).  Off by default; MHAQ_TEACHER_FUSED_X16=1 / 0 in the environment overrides it.
+    fuse_teacher_16bit: bool = False
     # the optimizer step as one HIP launch (optim.py: FusedRAdam, the bits of torch.optim.RAdam's foreach form) where the
     # trainer builds the optimizer itself, on a GPU; an optimizer_factory is never replaced.  MHAQ_FUSED_RADAM=1 / 0 in the
     # environment overrides it.
@@ -241,7 +245,7 @@ class QATTrainer:
         if cfg.fuse_teacher and cfg.distillation and layers is None and self.device.type == "cuda":
             from . import frozen_blocks
             if frozen_blocks.enabled_by_env():
-                frozen_blocks.install(self.teacher)
+                frozen_blocks.install(self.teacher, x16=frozen_blocks.x16_enabled(cfg.fuse_teacher_16bit))
         self.net = net
         self.teacher_stream = None
         if cfg.distillation and cfg.overlap_teacher and self.device.type == "cuda":
