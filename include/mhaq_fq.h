@@ -494,7 +494,8 @@ int mhaq_fq_bn_relu_pool3s2_x16(const void* x, const float* consts, void* p, int
  *   b = sqrt(v);  b = b + eps;  b = b / c2;  b = 1 / b;  b = b + c1
  *   p = p + m * b
  * "Rounded once" includes the framework's contractions, measured on the device against its foreach kernels (DESIGN
- * section 14): the multiply-adds of the lerp and of the second moment are FUSED -- m = fmaf(w1, g - m, m),
+ * section 14): the multiply-adds of the lerp and of the second moment are FUSED -- m = fmaf(w1, g - m, m), or
+ * m = fmaf(g - m, -(1 - w1), g) where |w1| >= 0.5 (the negation on the weight: a NaN g - m keeps its sign),
  * v = fmaf(w2, g * g, v) --, and the last line is fmaf(1, m * b, p) with the 1 a run-time operand, as the framework's
  * addcmul multiplies by its `value`: that rounds like p + m * b, and where p and m * b are both NaN it keeps the bits
  * (the sign) the framework keeps.  While c2 is -0.0 the chain runs through -inf and -0.0 to b = c1: plain IEEE

@@ -18,6 +18,10 @@
 //                                              argument, 1 here, at run time; fused or not the sum rounds the same, but
 //                                              where p and m * b are both NaN the instruction decides whose bits survive
 //   bit 3   the second moment's product as (w2 * g) * g instead of w2 * (g * g) (the framework's CPU kernel's order)
+//   bit 4   lerp's second branch (|w| >= 0.5, beta1 <= 0.5), g - (g - m) * (1 - w), where bit 0 fuses it: the negation on
+//           the weight, fmaf(g - m, -(1 - w), g), instead of on the difference, fmaf(-(g - m), 1 - w, g).  Every finite
+//           value rounds the same; where g - m is NaN the negated operand hands its flipped sign on, and the framework's
+//           instruction keeps the sign of g - m (tests/test_gpu_fused_radam_edges.py; the first branch has no negation)
 // Cache policy (profiles/r19_fused_radam_micro.txt): every load is non-temporal, the stores take the
 // default policy.  g is read once; p, m and v would fit the 256 MB Infinity Cache together, but a training step moves
 // gigabytes between two optimizer steps, so nothing of them is left to hit: measured cold, non-temporal loads of all four
@@ -29,7 +33,7 @@
 #include "fq_common.hpp"
 
 #ifndef MHAQ_RADAM_FORM
-#define MHAQ_RADAM_FORM 7
+#define MHAQ_RADAM_FORM 23
 #endif
 #ifndef MHAQ_RADAM_G_NT
 #define MHAQ_RADAM_G_NT 1
@@ -59,7 +63,7 @@ __device__ __forceinline__ void radam_element(float& p, float g, float& m, float
     m = (kRadamForm & 1) ? fmaf(k.w1, d, m) : m + k.w1 * d;
   } else {
     const float u = 1.0f - k.w1;
-    m = (kRadamForm & 1) ? fmaf(-d, u, g) : g - d * u;
+    m = !(kRadamForm & 1) ? g - d * u : (kRadamForm & 16) ? fmaf(d, -u, g) : fmaf(-d, u, g);
   }
   v = v * k.beta2;
   float a, b;

@@ -7,12 +7,14 @@ import ctypes
 import dataclasses
 import os
 import re
+import struct
 
 import pytest
 import torch
 
 from mhaq_amd import _lib, optim
 from mhaq_amd.qat import QATConfig
+from tests import radam_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BETA1, BETA2, EPS = 0.9, 0.999, 1e-8
@@ -66,13 +68,14 @@ def _planted(gen, shape, step):
     return g
 
 
-def _chain(p, g, m, v, c1, c2):
-    """The contract's op chain (include/mhaq_fq.h) with torch CPU ops: every line one op, rounded once."""
-    m.lerp_(g, 1 - BETA1)
-    v.mul_(BETA2)
-    v.addcmul_(g, g, value=1 - BETA2)
+def _chain(p, g, m, v, c1, c2, beta1=BETA1, beta2=BETA2, eps=EPS):
+    """The contract's op chain (include/mhaq_fq.h) with torch CPU ops: every line one op, rounded once.  lerp_ takes its
+    second branch, g - (g - m) (1 - w), when float(1 - beta1) >= 0.5."""
+    m.lerp_(g, 1 - beta1)
+    v.mul_(beta2)
+    v.addcmul_(g, g, value=1 - beta2)
     b = v.sqrt()
-    b.add_(EPS)
+    b.add_(eps)
     b.div_(c2)
     b.reciprocal_()
     b.add_(c1)
@@ -111,6 +114,209 @@ def test_op_chain_and_host_scalars_equal_torch_foreach_radam_bit_for_bit_over_ni
             st = opt.state[ref]
             for a, b in ((p, ref.detach()), (m, st["exp_avg"]), (v, st["exp_avg_sq"])):
                 assert torch.equal(a.view(torch.int32), b.view(torch.int32)), step
+
+
+def _intercept_scalar_lists(monkeypatch):
+    """-> seen: {"c1", "c2"} refilled at every step with torch's own scalar lists, as _multi_tensor_radam hands them to
+    _foreach_add_ (unrect_step_size) and _foreach_div_ (bias_correction2)."""
+    seen = {}
+    real_div, real_add = torch._foreach_div_, torch._foreach_add_
+    monkeypatch.setattr(torch, "_foreach_div_", lambda a, b: (seen.__setitem__("c2", list(b)), real_div(a, b))[1])
+
+    def add(a, b, **kw):
+        if isinstance(b, list):
+            seen["c1"] = list(b)
+        return real_add(a, b, **kw)
+    monkeypatch.setattr(torch, "_foreach_add_", add)
+    return seen
+
+
+def _double_bits(xs):
+    return [struct.pack("<d", float(x)) for x in xs]          # value AND sign of zero
+
+
+@pytest.mark.parametrize("eps", R.EPSS, ids=lambda e: f"eps={e!r}")
+@pytest.mark.parametrize("betas", R.BETAS, ids=R.case_id)
+def test_op_chain_equals_torch_foreach_radam_over_the_betas_and_eps_matrix(betas, eps, monkeypatch):
+    """The restatement the kernel follows, at both branches of lerp_ (float(1 - beta1) < 0.5 and >= 0.5, 0.5 +- 1e-10
+    included), rectified from step 6 (beta2 0.999 / 0.99 / 0.9) and never (0.5 / 0.0), eps 1e-8 / 1e-3 / 0.  With eps = 0 the
+    elements whose gradient history is all zero are 0 / -0.0 = NaN: NaN at the same elements with the same bits."""
+    beta1, beta2 = betas
+    gen = torch.Generator().manual_seed(7)
+    shapes = [(1,), (5,), (64,), (8, 4, 3, 3), (1023,)]
+    ps = [torch.randn(s, generator=gen).requires_grad_(True) for s in shapes]
+    opt = torch.optim.RAdam(ps, lr=3e-3, betas=betas, eps=eps, foreach=True)
+    mine = [(p.detach().clone(), torch.zeros(s), torch.zeros(s)) for p, s in zip(ps, shapes)]
+    seen = _intercept_scalar_lists(monkeypatch)
+    rect0 = R.first_rectified_step(beta2)
+    assert rect0 == (6 if beta2 in (0.999, 0.99, 0.9) else None)
+    saw_nan = False
+    for step in range(1, 10):
+        lr = R.LRS[step - 1]
+        opt.param_groups[0]["lr"] = lr
+        grads = [_planted(gen, s, step) for s in shapes]
+        for p, g in zip(ps, grads):
+            p.grad = g.clone()
+        opt.step()
+        c1, c2 = optim.radam_scalars(float(step), lr, beta1, beta2)
+        assert _double_bits(seen["c1"]) == _double_bits([c1] * len(ps))
+        assert _double_bits(seen["c2"]) == _double_bits([c2] * len(ps))
+        assert (str(c2) == "-0.0") == (rect0 is None or step < rect0 or lr == 0.0)
+        for (p, m, v), g, ref in zip(mine, grads, ps):
+            _chain(p, g, m, v, c1, c2, beta1, beta2, eps)
+            st = opt.state[ref]
+            for a, b in ((p, ref.detach()), (m, st["exp_avg"]), (v, st["exp_avg_sq"])):
+                assert torch.equal(a.view(torch.int32), b.view(torch.int32)), step
+        saw_nan = saw_nan or bool(torch.isnan(mine[-1][0].view(-1)[:3]).all())
+    # element 0, 1 and 2 of the planted tensor: gradient 0.0, -0.0 and a subnormal whose square is 0 at every step
+    assert saw_nan == (eps == 0.0)
+
+
+PLANTED_COUNTS = [6, 7, 100, 10 ** 4, 10 ** 6]
+
+
+@pytest.mark.parametrize("betas", [R.DEFAULT_BETAS] + R.BETAS, ids=R.case_id)
+def test_host_scalars_equal_torchs_lists_at_step_counts_planted_through_load_state_dict(betas, monkeypatch):
+    """A run resumed from a checkpoint: tensor i steps at PLANTED_COUNTS[i], + 1 and + 2 (the middle one at lr = 0)."""
+    beta1, beta2 = betas
+    ps = [torch.ones(3).requires_grad_(True) for _ in PLANTED_COUNTS]
+    opt = torch.optim.RAdam(ps, lr=3e-3, betas=betas, foreach=True)
+    for p in ps:
+        p.grad = torch.ones(3)
+    opt.step()
+    sd = opt.state_dict()
+    for i, k in enumerate(PLANTED_COUNTS):
+        sd["state"][i]["step"] = torch.tensor(float(k - 1))
+    opt.load_state_dict(sd)
+    seen = _intercept_scalar_lists(monkeypatch)
+    for ahead, lr in enumerate([3e-3, 0.0, 1e-3]):
+        opt.param_groups[0]["lr"] = lr
+        opt.step()
+        counts = [float(k + ahead) for k in PLANTED_COUNTS]
+        assert [float(opt.state[p]["step"]) for p in ps] == counts
+        mine = [optim.radam_scalars(k, lr, beta1, beta2) for k in counts]
+        assert _double_bits(seen["c1"]) == _double_bits([c[0] for c in mine]), (ahead, seen["c1"], mine)
+        assert _double_bits(seen["c2"]) == _double_bits([c[1] for c in mine]), (ahead, seen["c2"], mine)
+        if lr == 0.0:
+            assert all(str(x) == "-0.0" for c in mine for x in c)
+        elif R.first_rectified_step(beta2) == 6:
+            assert all(str(c[0]) == "-0.0" and c[1] < 0 for c in mine)           # every planted count is rectified
+        else:
+            assert all(c[0] < 0 and str(c[1]) == "-0.0" for c in mine)
+
+
+# ---------------------------------------------------------------------------------------------- the float64 oracle
+def test_the_float64_oracle_has_the_algorithms_closed_forms():
+    """radam_ref against what the algorithm gives by hand, independent of any op chain: step 1 from a zero state is
+    p - lr g (m_hat = g, rho_1 <= 5); at t -> inf (beta^t = 0, rho_t = rho_inf, r = 1) it is p - lr m / (sqrt(v) + eps)."""
+    gen = torch.Generator().manual_seed(5)
+    for beta1, beta2 in [R.DEFAULT_BETAS] + R.BETAS:
+        p0, g = torch.randn(33, generator=gen, dtype=torch.float64), torch.randn(33, generator=gen, dtype=torch.float64)
+        p, m, v = p0.clone(), torch.zeros(33, dtype=torch.float64), torch.zeros(33, dtype=torch.float64)
+        R.radam_ref([p], [g], [m], [v], [1], 3e-3, beta1, beta2, 1e-8)
+        assert torch.allclose(p, p0 - 3e-3 * g, rtol=1e-13, atol=1e-15)
+        assert torch.allclose(m, (1 - beta1) * g, rtol=1e-13, atol=0) and torch.allclose(v, (1 - beta2) * g * g, rtol=1e-13, atol=0)
+        m0, v0 = torch.randn(33, generator=gen, dtype=torch.float64), torch.rand(33, generator=gen, dtype=torch.float64)
+        p, m, v = p0.clone(), m0.clone(), v0.clone()
+        R.radam_ref([p], [g], [m], [v], [10 ** 6], 3e-3, beta1, beta2, 1e-3)
+        m1, v1 = beta1 * m0 + (1 - beta1) * g, beta2 * v0 + (1 - beta2) * g * g
+        assert beta1 ** (10 ** 6) == 0.0 and beta2 ** (10 ** 6) == 0.0
+        rectified = 2 / (1 - beta2) - 1 > 5                           # rho_inf; <= 3 for beta2 0.5 and 0.0: m_hat = m alone
+        assert rectified == (R.first_rectified_step(beta2) is not None)
+        want = p0 - 3e-3 * m1 / (v1.sqrt() + 1e-3) if rectified else p0 - 3e-3 * m1
+        assert torch.allclose(p, want, rtol=1e-12, atol=1e-15), (beta1, beta2)
+        assert torch.allclose(m, m1, rtol=1e-13, atol=1e-16) and torch.allclose(v, v1, rtol=1e-13, atol=1e-16)
+
+
+def _oracle_case_on_cpu(betas, mutate=None):
+    """-> ((p, m, v) fp32 of torch's CPU foreach RAdam, (p, m, v) of the op-chain restatement [mutated], (p, m, v) float64
+    oracle, lr per element): every step's values of every tensor, concatenated."""
+    beta1, beta2 = betas
+    p0, grads, lrs = R.oracle_inputs()
+    ps = [p.clone().requires_grad_(True) for p in p0]
+    opt = torch.optim.RAdam(ps, lr=lrs[0], betas=betas, eps=R.ORACLE_EPS, foreach=True)
+    mine = [(p.clone(), torch.zeros_like(p), torch.zeros_like(p)) for p in p0]
+    ref = [[p.double() for p in p0], [torch.zeros_like(p, dtype=torch.float64) for p in p0],
+           [torch.zeros_like(p, dtype=torch.float64) for p in p0]]
+    rec_t, rec_c, rec_r, rec_lr = [], [], [], []
+    for step, (gs, lr) in enumerate(zip(grads, lrs), 1):
+        opt.param_groups[0]["lr"] = lr
+        for p, g in zip(ps, gs):
+            p.grad = g.clone()
+        opt.step()
+        skip = mutate == "missed_step" and step == 4
+        c1, c2 = optim.radam_scalars(float(step), lr * (1.001 if mutate == "lr_coefficient" else 1.0), beta1, beta2)
+        for (p, m, v), g in zip(mine, gs):
+            if not skip:
+                _chain(p, g, m, v, c1, c2, beta1, beta2, R.ORACLE_EPS)
+        R.radam_ref(ref[0], [g.double() for g in gs], ref[1], ref[2], [step] * len(gs), lr, beta1, beta2, R.ORACLE_EPS)
+        rec_t.append([torch.cat([p.detach().reshape(-1) for p in ps])] +
+                     [torch.cat([opt.state[p][k].reshape(-1) for p in ps]) for k in ("exp_avg", "exp_avg_sq")])
+        rec_c.append([torch.cat([x[j].reshape(-1) for x in mine]) for j in range(3)])
+        rec_r.append([torch.cat([x.reshape(-1) for x in ref[j]]) for j in range(3)])
+        rec_lr.append(torch.full_like(rec_r[-1][0], lr))
+    join = lambda rec: tuple(torch.cat([r[j] for r in rec]) for j in range(3))      # noqa: E731
+    return join(rec_t), join(rec_c), join(rec_r), torch.cat(rec_lr)
+
+
+@pytest.mark.parametrize("betas", [R.DEFAULT_BETAS] + R.BETAS, ids=R.case_id)
+def test_the_float64_oracle_against_torch_cpu_foreach_radam_by_the_2x_rule(betas):
+    """The yardstick of the GPU oracle test, run without a GPU: the op-chain restatement (torch's bits) passes it, and the
+    rule has teeth -- a learning-rate coefficient off by 0.1 % and one missed step both fail it."""
+    torch_run, chain_run, ref, lr = _oracle_case_on_cpu(betas)
+    ok, errs = R.within_twice((chain_run, ref), (torch_run, ref), lr)
+    assert ok, errs
+    # the second moment is a sum of non-negative terms, so its relative error has a bound of its own: per step the fp32
+    # casts of beta2 and 1 - beta2 and at most four roundings (v beta2, g g, w2 (g g), the sum), 2^-24 each, not amplified
+    assert errs["exp_avg_sq"][1] <= 6 * len(R.ORACLE_LRS) * 2.0 ** -24, errs
+    # (exp_avg and p have none: g - m cancels, and the relative error of a cancelled value is unbounded)
+    for mutant in ("lr_coefficient", "missed_step"):
+        _, bad_run, _, _ = _oracle_case_on_cpu(betas, mutate=mutant)
+        ok, errs = R.within_twice((bad_run, ref), (torch_run, ref), lr)
+        assert not ok, (mutant, errs)
+
+
+# ---------------------------------------------------------------------------------------------- slabs and guard bands
+@pytest.mark.parametrize("case", list(R.ALIGN_CASES))
+def test_banded_slabs_with_a_planted_state_are_accepted_by_both_classes_and_take_the_launch(case):
+    """The construction of the GPU guard-band test on the CPU: both classes step the planted state on the offset views and
+    leave it there, neither writes a band or the gradient slab, and every layout passes the fused launch's tensor rule."""
+    runs = []
+    for cls, kw in ((torch.optim.RAdam, dict(foreach=True)), (optim.FusedRAdam, {})):
+        opt, ps, streams = R.banded_optimizer(cls, case, "cpu", **kw)
+        gen = torch.Generator().manual_seed(22)
+        for i, (p, s) in enumerate(zip(ps, streams)):
+            off = R.ALIGN_CASES[case](i)
+            assert tuple(s[k].view.data_ptr() % 16 for k in "pgmv") == tuple(4 * o for o in off)
+            assert optim.tensor_fallback_reason(p, p.grad, s["m"].view, s["v"].view, require_gpu=False) is None, (case, i)
+        for step in range(1, 4):
+            for s in streams:
+                s["g"].view.copy_(R.planted_gradient(gen, s["g"].n, plant=True))
+            before = [s["g"].bits() for s in streams]
+            opt.step()
+            for i, (p, s) in enumerate(zip(ps, streams)):
+                assert all(s[k].bands_intact() for k in "pgmv"), (case, step, i)
+                assert torch.equal(s["g"].bits(), before[i])
+                st = opt.state[p]
+                assert float(st["step"]) == step and not st["step"].is_cuda
+                assert st["exp_avg"].data_ptr() == s["m"].view.data_ptr() and st["exp_avg_sq"].data_ptr() == s["v"].view.data_ptr()
+        assert any(bool(s["m"].view.ne(0).any()) for s in streams)                  # the planted moments were stepped
+        runs.append([torch.cat([s[k].bits() for k in "pmv"]) for s in streams])
+    for a, b in zip(*runs):
+        assert torch.equal(a, b)
+
+
+def test_the_alignment_cases_cover_every_listed_offset():
+    n = len(R.BAND_SIZES)
+    offs = {c: {f(i) for i in range(n)} for c, f in R.ALIGN_CASES.items()}
+    assert offs["all_aligned"] == {(0, 0, 0, 0)}
+    assert [offs[f"all_plus{k}_byte{4 * k}"] for k in (1, 2, 3)] == [{(k,) * 4} for k in (1, 2, 3)]
+    for c, j in (("only_p_misaligned", 0), ("only_g_misaligned", 1), ("only_exp_avg_misaligned", 2)):
+        assert {o[j] for o in offs[c]} == {1, 2, 3}                                  # byte offsets 4, 8 and 12
+        assert all(o[k] == 0 for o in offs[c] for k in range(4) if k != j)
+    C = R.CHUNK
+    assert R.BAND_SIZES == [1, 3, 4, 5, 1020, 1023, 1024, 1028, 4092, 4095, C, C + 1, C + 4, 2 * C, 2 * C + 3]
+    assert C == _lib.lib().mhaq_fq_radam_chunk_elements() and R.BAND >= 64
 
 
 # ---------------------------------------------------------------------------------------------- switches
