@@ -342,7 +342,34 @@ int mhaq_fq_bn_fwd(const float* x, const float* weight, const float* bias, float
                    void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
- * The same on 16-bit tensors (the BatchNorm behind a convolution under torch.autocast).  Additive to ABI v4 --
+ * The forward on 16-bit tensors (the BatchNorm behind a convolution under torch.autocast).  Additive to ABI v4 --
+ * MHAQ_FQ_ABI_VERSION stays 4; a caller discovers these entry points by symbol.
+ *   x, y            dense NHWC seen as [m][c], of the type named by `dtype` (MHAQ_FQ_DT_BF16 or MHAQ_FQ_DT_F16, anything else:
+ *                   MHAQ_FQ_EINVAL); m >= 2, c % 8 == 0 and c <= 2^22 (else MHAQ_FQ_EUNSUPPORTED); x, y and `workspace`
+ *                   16-byte aligned (else MHAQ_FQ_EALIGN).  y == NULL skips the third launch.
+ *   weight, bias, save_mean, save_invstd, running_mean, running_var and everything in `workspace`: fp32 / fp64, exactly as
+ *                   in mhaq_fq_bn_fwd (weight, bias NULL = 1, 0; the running statistics both given or both NULL).
+ * Argument errors are returned before any launch, with mhaq_fq_bn_fwd's codes in its order; the dtype is checked behind the
+ * required pointers and positive sizes and before width and range, as in mhaq_fq_bn_bwd_x16.
+ * Arithmetic: the contract of mhaq_fq_bn_fwd on the exactly upcast input.  With k = up(x[row 0][.]), S1 = sum (up(x) - k) and
+ * S2 = sum (up(x) - k)^2 are fixed-order fp64 sums of exact fp64 terms; mean, invstd and the running statistics are formed in
+ * fp64 as above and each rounded to fp32 ONCE; and, with a = weight * save_invstd (an fp32 product),
+ *   y = R16((up(x) - save_mean) * a + bias)
+ * is evaluated in fp32 in this order, without contraction, and rounded to nearest-even ONCE (a plain conversion: NaN stays
+ * NaN, an fp16 overflow gives +-inf).  The clamp of var at 0 is a select, so a channel that holds a NaN or an infinity is NaN
+ * in every element of y and in its statistics; a constant channel gives mean = the constant, var = 0 and y = R16(bias) bit
+ * for bit.  The partial-row geometry differs from mhaq_fq_bn_fwd's (a lane owns 8 channels): size the workspace with
+ * mhaq_fq_bn_fwd_x16_workspace_bytes (0 for an unsupported shape).  Three launches, deterministic (y, the statistics and
+ * every byte of the workspace), no float atomics.  Stream-ordered, capture-safe, stateless.
+ * ---------------------------------------------------------------------- */
+size_t mhaq_fq_bn_fwd_x16_workspace_bytes(int64_t m, int64_t c);
+int mhaq_fq_bn_fwd_x16(const void* x, const float* weight, const float* bias, void* y,
+                       float* save_mean, float* save_invstd, float* running_mean, float* running_var,
+                       double factor, double eps, int64_t m, int64_t c, int dtype,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
+ * The backward on 16-bit tensors (the BatchNorm behind a convolution under torch.autocast).  Additive to ABI v4 --
  * MHAQ_FQ_ABI_VERSION stays 4; a caller discovers these entry points by symbol.
  *   x, dy, dx       dense NHWC seen as [m][c], of the type named by `dtype` (MHAQ_FQ_DT_BF16 or MHAQ_FQ_DT_F16, anything else:
  *                   MHAQ_FQ_EINVAL); c % 8 == 0 and c <= 2^22 (else MHAQ_FQ_EUNSUPPORTED); x, dy, dx and `workspace`

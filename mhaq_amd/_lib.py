@@ -63,6 +63,8 @@ SIGNATURES = {
     # ... and on 16-bit tensors: `dtype` after c, its own workspace query (additive, ABI v4 kept)
     "mhaq_fq_bn_bwd_x16_workspace_bytes": (_sz, [_i64, _i64]),
     "mhaq_fq_bn_bwd_x16": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _int, _p, _sz, _p]),
+    "mhaq_fq_bn_fwd_x16_workspace_bytes": (_sz, [_i64, _i64]),
+    "mhaq_fq_bn_fwd_x16": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_double, _i64, _i64, _int, _p, _sz, _p]),
     # the stem's 3x3 / stride 2 max pool with 1-byte argmax codes, and the BatchNorm backward that gathers its dy from them
     "mhaq_fq_maxpool3s2_fwd": (_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _p]),
     "mhaq_fq_bn_pool_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),

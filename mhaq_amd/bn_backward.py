@@ -17,7 +17,7 @@ non-float32 input (so under autocast, where the convolution in front hands over 
 16-bit inputs.  install(model, x16=True) also sends a bf16 / fp16 device input (float32 parameters) through the node and
 enables its 16-bit backward (mhaq_fq_bn_bwd_x16: the fp32 arithmetic on the exactly upcast x and dy, dx rounded to
 nearest-even once; C % 8 == 0 and a dy of x's dtype, else the node falls back to the framework's backward, bit for bit).
-The forward is still the framework's.  This is OFF by default -- it changes the gradient bits of every bf16 run --:
+The forward is still the framework's (unless hip_forward_x16, below, is set as well).  This is OFF by default -- it changes the gradient bits of every bf16 run --:
 QATConfig.hip_bn_backward_16bit=True switches it on per trainer, MHAQ_BN_BACKWARD_X16=1 (or "true" / "on") in the
 environment for an unchanged benchmark; the variable, when set, overrides the configuration either way.
 
@@ -28,9 +28,17 @@ gradient.  float32 only (takes_pooled_node): a 16-bit stem stays maxpool(bn(c)),
 HIP forward.  install(model, hip_forward=True) also runs the FORWARD of a float32 input on the kernels of csrc/bn_bwd.hip
 (mhaq_fq_bn_fwd: shifted fp64 sums, statistics rounded once, y = (x - mean) * (gamma * invstd) + beta); the node falls back to
 the framework's forward, bit for bit, where that does not apply (NCHW, C % 4 != 0).  16-bit inputs keep the framework's
-forward.  OFF by default -- it changes the bits of y and of the saved and running statistics --:
+forward under this flag.  OFF by default -- it changes the bits of y and of the saved and running statistics --:
 QATConfig.hip_bn_forward=True switches it on per trainer, MHAQ_BN_FORWARD=1 in the environment for an unchanged benchmark,
 with the semantics of MHAQ_BN_BACKWARD_X16.
+
+HIP forward, 16-bit.  install(model, x16=True, hip_forward_x16=True) runs the forward of a bf16 / fp16 input on
+mhaq_fq_bn_fwd_x16: the same contract on the exactly upcast input -- float32 statistics, y rounded to nearest-even once --,
+with C % 8 == 0 and N * H * W >= 2, else the framework's forward bit for bit.  It has an effect only TOGETHER with x16: the
+16-bit HIP backward is the only backward of such a node, so hip_forward_x16 alone changes nothing (and does not raise).  The
+stem keeps maxpool(bn(c)) on the unpooled node.  OFF by default -- it changes the bits of y and of the saved and running
+statistics of every bf16 run --: QATConfig.hip_bn_forward_16bit=True per trainer (next to hip_bn_backward_16bit),
+MHAQ_BN_FORWARD_X16=1 in the environment (next to MHAQ_BN_BACKWARD_X16=1), with the same semantics.
 
 MHAQ_BN_BACKWARD=0 in the environment keeps QATTrainer from installing (A/B runs of an unchanged benchmark);
 QATConfig.hip_bn_backward=False does the same per trainer.
@@ -45,8 +53,10 @@ from torch import nn
 ENV_SWITCH = "MHAQ_BN_BACKWARD"
 ENV_SWITCH_X16 = "MHAQ_BN_BACKWARD_X16"
 ENV_SWITCH_FORWARD = "MHAQ_BN_FORWARD"
+ENV_SWITCH_FORWARD_X16 = "MHAQ_BN_FORWARD_X16"
 _X16 = "_mhaq_bn_x16"          # per-module flag in the instance __dict__ (not a parameter, buffer or state_dict entry)
 _HIP_FWD = "_mhaq_bn_hip_forward"      # likewise
+_HIP_FWD_X16 = "_mhaq_bn_hip_forward_x16"      # likewise
 
 
 def enabled_by_env() -> bool:
@@ -64,6 +74,12 @@ def hip_forward_enabled(configured: bool = False) -> bool:
     """The HIP forward's switch: `configured` (QATConfig.hip_bn_forward) unless MHAQ_BN_FORWARD is set, which then decides,
     as in x16_enabled()."""
     return _env_or(ENV_SWITCH_FORWARD, configured)
+
+
+def hip_forward_x16_enabled(configured: bool = False) -> bool:
+    """The 16-bit HIP forward's switch: `configured` (QATConfig.hip_bn_forward_16bit) unless MHAQ_BN_FORWARD_X16 is set, which
+    then decides, as in x16_enabled().  The forward runs only where the 16-bit backward's switch is on as well."""
+    return _env_or(ENV_SWITCH_FORWARD_X16, configured)
 
 
 def _env_or(name: str, configured: bool) -> bool:
@@ -91,6 +107,11 @@ class HipBackwardBatchNorm2d(nn.BatchNorm2d):
         """True when install(..., hip_forward=True) enabled the HIP forward (of float32 inputs) for this module."""
         return bool(self.__dict__.get(_HIP_FWD, False))
 
+    def takes_hip_forward_x16(self) -> bool:
+        """True when install(..., hip_forward_x16=True) enabled the HIP forward of 16-bit inputs for this module (it runs only
+        where takes_x16() holds as well)."""
+        return bool(self.__dict__.get(_HIP_FWD_X16, False))
+
     def takes_pooled_node(self, input) -> bool:
         """True when forward_pooled() applies: the pooled node's kernels are float32."""
         return input.dtype == torch.float32 and self.takes_node(input)
@@ -117,7 +138,8 @@ class HipBackwardBatchNorm2d(nn.BatchNorm2d):
             return super().forward(input)
         from . import _ext
         x16 = input.dtype != torch.float32
-        return self._node(_ext.ext().bn_train, input, x16, not x16 and self.takes_hip_forward())
+        return self._node(_ext.ext().bn_train, input, x16, not x16 and self.takes_hip_forward(),
+                          x16 and self.takes_x16() and self.takes_hip_forward_x16())
 
     def forward_pooled(self, input):
         """max_pool2d(self(input), 3, 2, 1) as one node (bn_pool_train: the BatchNorm output is not kept, the backward
@@ -126,9 +148,10 @@ class HipBackwardBatchNorm2d(nn.BatchNorm2d):
         return self._node(_ext.ext().bn_pool_train, input, input.dtype == torch.float32 and self.takes_hip_forward())
 
 
-def install(model: nn.Module, x16: bool = False, hip_forward: bool = False) -> int:
+def install(model: nn.Module, x16: bool = False, hip_forward: bool = False, hip_forward_x16: bool = False) -> int:
     """Give every nn.BatchNorm2d of `model` (the exact type) the forward above; x16=True also enables the 16-bit backward
-    on them, hip_forward=True the HIP forward of float32 inputs.  Returns the number of modules switched."""
+    on them, hip_forward=True the HIP forward of float32 inputs, hip_forward_x16=True (with x16) that of 16-bit inputs.
+    Returns the number of modules switched."""
     switched = 0
     for m in model.modules():
         if type(m) is nn.BatchNorm2d:
@@ -137,6 +160,8 @@ def install(model: nn.Module, x16: bool = False, hip_forward: bool = False) -> i
                 m.__dict__[_X16] = True
             if hip_forward:
                 m.__dict__[_HIP_FWD] = True
+            if hip_forward_x16:
+                m.__dict__[_HIP_FWD_X16] = True
             switched += 1
     return switched
 
@@ -147,3 +172,4 @@ def uninstall(model: nn.Module) -> None:
             m.__class__ = nn.BatchNorm2d
             m.__dict__.pop(_X16, None)
             m.__dict__.pop(_HIP_FWD, None)
+            m.__dict__.pop(_HIP_FWD_X16, None)

@@ -1,8 +1,8 @@
 // Backward of training-mode BatchNorm for gfx950, dense NHWC seen as [M = N*H*W][C]: fp32 with C % 4 == 0, or bf16 / fp16
 // with C % 8 == 0 (a lane owns 16 bytes of a row either way).
 //
-// By default the forward stays with the framework (it saves the batch mean and invstd; the opt-in mhaq_fq_bn_fwd, fp32, is
-// further down: "the training forward"); this file replaces the three launches of its backward with three bandwidth-bound ones:
+// By default the forward stays with the framework (it saves the batch mean and invstd; the opt-in mhaq_fq_bn_fwd and its
+// 16-bit form mhaq_fq_bn_fwd_x16 are further down: "the training forward"); this file replaces the three launches of its backward with three bandwidth-bound ones:
 //   bn_bwd_reduce_kernel     one read of x and dy   -> per-block fp64 partial rows of  sum dy  and  sum dy * (x - mean)
 //   bn_bwd_finalize_kernel   fixed-order fp64 sum of the partial rows -> dbias, dweight, per-channel constants
 //   bn_bwd_dx_kernel         a 2R1W stream in the shape of pt_bwd_kernel (fq_pt.hip):
@@ -604,7 +604,7 @@ static int bn_bwd_launch(const BnCall& a, const Dy dy, int64_t m, int64_t c) {
   return launch_status();
 }
 
-// ---------------------------------------------------------------- the training forward (mhaq_fq_bn_fwd)
+// ---------------------------------------------------------------- the training forward (mhaq_fq_bn_fwd, mhaq_fq_bn_fwd_x16)
 // The sibling of the three launches above, over the same partition:
 //   bn_fwd_reduce_kernel     one read of x -> per-block fp64 partial rows of  sum (x - k)  and  sum (x - k)^2
 //   bn_fwd_finalize_kernel   fixed-order fp64 sum of the partial rows -> mean, invstd, the running statistics, the constants
@@ -625,6 +625,16 @@ static int bn_bwd_launch(const BnCall& a, const Dy dy, int64_t m, int64_t c) {
 #endif
 constexpr int64_t kBnFwdReduceNtElems = MHAQ_BN_FWD_REDUCE_NT_ELEMS;
 constexpr int64_t kBnFwdNormNtElems = MHAQ_BN_FWD_NORM_NT_ELEMS;
+// The same two for 16-bit elements (mhaq_fq_bn_fwd_x16), by BYTES: one 2-byte stream fits the cache up to four times the
+// backward's fp32 element count.  tools/bn_fwd_bench.py --dtype times builds with a forced policy next to the product's.
+#ifndef MHAQ_BN_FWD16_REDUCE_NT_ELEMS
+#define MHAQ_BN_FWD16_REDUCE_NT_ELEMS (112ll << 20)
+#endif
+#ifndef MHAQ_BN_FWD16_NORM_NT_ELEMS
+#define MHAQ_BN_FWD16_NORM_NT_ELEMS (112ll << 20)
+#endif
+constexpr int64_t kBnFwd16ReduceNtElems = MHAQ_BN_FWD16_REDUCE_NT_ELEMS;
+constexpr int64_t kBnFwd16NormNtElems = MHAQ_BN_FWD16_NORM_NT_ELEMS;
 constexpr int kBnFwdNConst = 3;       // per-channel constants of the norm kernel: mean, gamma * invstd, beta
 constexpr int kBnFwdRows32 = kBnFwdNConst + 1;      // fp32 rows at the head of the workspace: the constants and the shift
 
@@ -831,7 +841,9 @@ static int bn_fwd_launch(const BnFwdCall& a, int64_t m, int64_t c) {
   float* shift = consts + kBnFwdNConst * c;
   double* parts = (double*)(consts + kBnFwdRows32 * c);     // 16 * c bytes in: 16-byte aligned
   const int cv = (int)(c / IO::kW);
-  const bool nt_r = m * c >= kBnFwdReduceNtElems, nt_n = m * c >= kBnFwdNormNtElems, big = m * c >= kBnBigElems;
+  constexpr bool x16 = IO::kW == 8;
+  const bool nt_r = m * c >= (x16 ? kBnFwd16ReduceNtElems : kBnFwdReduceNtElems);
+  const bool nt_n = m * c >= (x16 ? kBnFwd16NormNtElems : kBnFwdNormNtElems), big = m * c >= kBnBigElems;
   const dim3 rgrid((unsigned)g.nchunks, (unsigned)g.ncol);
   MHAQ_LAUNCH((nt_r ? bn_fwd_reduce_kernel<true, IO, kBnRedU> : bn_fwd_reduce_kernel<false, IO, kBnRedU>), rgrid,
               dim3(kBlock), 0, st, x, shift, parts, m, cv, g.rows);
@@ -1388,6 +1400,19 @@ int mhaq_fq_bn_fwd(const float* x, const float* weight, const float* bias, float
                     workspace_bytes, stream};
   if (const int rc = bn_fwd_status(a, 4, m, c)) return rc;
   return bn_fwd_launch<IoF32>(a, m, c);
+}
+
+size_t mhaq_fq_bn_fwd_x16_workspace_bytes(int64_t m, int64_t c) { return bn_fwd_workspace_bytes(m, c, 8); }
+
+int mhaq_fq_bn_fwd_x16(const void* x, const float* weight, const float* bias, void* y, float* save_mean, float* save_invstd,
+                       float* running_mean, float* running_var, double factor, double eps, int64_t m, int64_t c, int dtype,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+  const BnFwdCall a{x, weight, bias, y, save_mean, save_invstd, running_mean, running_var, factor, eps, workspace,
+                    workspace_bytes, stream};
+  const int rc = bn_fwd_status(a, 8, m, c);
+  if (rc == MHAQ_FQ_EINVAL || !io16::known_dtype(dtype)) return MHAQ_FQ_EINVAL;      // the dtype: behind the NULL checks
+  if (rc) return rc;
+  return io16::with_dtype(dtype, [&](auto dt) { return bn_fwd_launch<Io16<decltype(dt)::value>>(a, m, c); });
 }
 
 int mhaq_fq_bn_infer_consts(const float* running_mean, const float* running_var, const float* weight, const float* bias,

@@ -58,6 +58,7 @@ namespace {
   X(mhaq_fq_bn_bwd_workspace_bytes) X(mhaq_fq_bn_bwd) X(mhaq_fq_maxpool3s2_fwd)                                       \
   X(mhaq_fq_bn_pool_bwd_workspace_bytes) X(mhaq_fq_bn_pool_bwd) X(mhaq_fq_bn_bwd_x16_workspace_bytes)                 \
   X(mhaq_fq_bn_bwd_x16) X(mhaq_fq_bn_fwd_workspace_bytes) X(mhaq_fq_bn_fwd)                                         \
+  X(mhaq_fq_bn_fwd_x16_workspace_bytes) X(mhaq_fq_bn_fwd_x16)                                                       \
   X(mhaq_fq_bn_infer_consts) X(mhaq_fq_bn_infer_act) X(mhaq_fq_bn_relu_pool3s2)                                     \
   X(mhaq_fq_bn_infer_act_x16) X(mhaq_fq_bn_relu_pool3s2_x16)                                                        \
   X(mhaq_fq_radam_chunk_elements) X(mhaq_fq_radam_step)
@@ -712,35 +713,49 @@ std::atomic<int64_t> g_bn_pool_hip_backwards{0};   // ... that took mhaq_fq_bn_p
 // ... and the opt-in HIP FORWARD (mhaq_fq_bn_fwd; `hip_forward` of bn_train / bn_pool_train): taken where bn_hip_eligible
 // holds for an fp32 x with N * H * W >= 2, the bias is eligible like the weight, and the running statistics are both absent or
 // both fp32 contiguous device tensors of length C.  Anything else is the framework's forward, as without the flag.
+// A 16-bit x takes mhaq_fq_bn_fwd_x16 under the same conditions (C % 8 == 0 by bn_hip_eligible) where bn_train's caller set
+// `hip_forward_x16` next to `x16`: the 16-bit backward is the only backward such a node has.
 std::atomic<int64_t> g_bn_hip_forwards{0};   // forwards of both nodes that took mhaq_fq_bn_fwd
+std::atomic<int64_t> g_bn_hip_forwards_x16{0};   // forwards of bn_train that took mhaq_fq_bn_fwd_x16
 
 inline Tensor opt_tensor(const std::optional<Tensor>& t) { return t.has_value() ? *t : Tensor(); }
 
-inline bool bn_hip_forward_eligible(const Tensor& x, const Tensor& w, const Tensor& b, const Tensor& rm, const Tensor& rv) {
+// x16: the eligibility of a 16-bit x (mhaq_fq_bn_fwd_x16) instead of an fp32 one
+inline bool bn_hip_forward_eligible(const Tensor& x, const Tensor& w, const Tensor& b, const Tensor& rm, const Tensor& rv,
+                                    bool x16 = false) {
   if (rm.defined() != rv.defined()) return false;
-  return bn_hip_eligible(x, w) && x.scalar_type() == at::kFloat && x.numel() / x.size(1) >= 2 &&
+  return bn_hip_eligible(x, w) && (x16 ? act_dtype(x) != 0 : x.scalar_type() == at::kFloat) && x.numel() / x.size(1) >= 2 &&
          bn_hip_eligible(x, b, rm.defined() ? &rm : nullptr, rv.defined() ? &rv : nullptr);
 }
 
 // One HIP BatchNorm forward of an eligible x: {y, mean, invstd}; the running statistics are updated in place, with their
-// version counters bumped as the framework's in-place update bumps them.
+// version counters bumped as the framework's in-place update bumps them.  The entry point follows from x's dtype; the
+// statistics are fp32 either way.
 std::array<Tensor, 3> bn_hip_forward(const Tensor& x, const Tensor& w, const Tensor& b, const Tensor& rm, const Tensor& rv,
                                      double momentum, double eps) {
   need_lib();
   const int64_t c = x.size(1), m = x.numel() / c;
   Tensor y = at::empty_like(x);
-  Tensor mean = at::empty({c}, x.options()), invstd = at::empty({c}, x.options());
-  const size_t nb = A.mhaq_fq_bn_fwd_workspace_bytes(m, c);
+  const int dt = act_dtype(x);
+  Tensor mean = at::empty({c}, x.options().dtype(at::kFloat)), invstd = at::empty({c}, x.options().dtype(at::kFloat));
+  const size_t nb = dt ? A.mhaq_fq_bn_fwd_x16_workspace_bytes(m, c) : A.mhaq_fq_bn_fwd_workspace_bytes(m, c);
   Tensor ws = at::empty({(int64_t)nb}, x.options().dtype(at::kByte));
-  check(A.mhaq_fq_bn_fwd(fptr(x), fptr_or_null(w), fptr_or_null(b), fptr_mut(y), fptr_mut(mean), fptr_mut(invstd),
-                         rm.defined() ? fptr_mut(rm) : nullptr, rv.defined() ? fptr_mut(rv) : nullptr, momentum, eps, m, c,
-                         ws.mutable_data_ptr(), nb, cur_stream(x)),
-        "mhaq_fq_bn_fwd");
+  float *rmp = rm.defined() ? fptr_mut(rm) : nullptr, *rvp = rv.defined() ? fptr_mut(rv) : nullptr;
+  if (dt) {
+    check(A.mhaq_fq_bn_fwd_x16(x.const_data_ptr(), fptr_or_null(w), fptr_or_null(b), y.mutable_data_ptr(), fptr_mut(mean),
+                               fptr_mut(invstd), rmp, rvp, momentum, eps, m, c, dt, ws.mutable_data_ptr(), nb, cur_stream(x)),
+          "mhaq_fq_bn_fwd_x16");
+    g_bn_hip_forwards_x16.fetch_add(1, std::memory_order_relaxed);
+  } else {
+    check(A.mhaq_fq_bn_fwd(fptr(x), fptr_or_null(w), fptr_or_null(b), fptr_mut(y), fptr_mut(mean), fptr_mut(invstd), rmp, rvp,
+                           momentum, eps, m, c, ws.mutable_data_ptr(), nb, cur_stream(x)),
+          "mhaq_fq_bn_fwd");
+    g_bn_hip_forwards.fetch_add(1, std::memory_order_relaxed);
+  }
   if (rm.defined()) {
     torch::autograd::impl::bump_version(rm);
     torch::autograd::impl::bump_version(rv);
   }
-  g_bn_hip_forwards.fetch_add(1, std::memory_order_relaxed);
   return {y, mean, invstd};
 }
 
@@ -791,17 +806,20 @@ class BatchNormTrainFn : public torch::autograd::Function<BatchNormTrainFn> {
   static Tensor forward(AutogradContext* ctx, const Tensor& x, const std::optional<Tensor>& w,
                         const std::optional<Tensor>& b, const std::optional<Tensor>& running_mean,
                         const std::optional<Tensor>& running_var, double momentum, double eps, bool cudnn_enabled,
-                        bool x16, bool hip_forward) {
+                        bool x16, bool hip_forward, bool hip_forward_x16) {
     const bool has_w = w.has_value() && w->defined();
     ctx->saved_data["hip_fwd"] = false;
-    if (hip_forward && bn_hip_forward_eligible(x, opt_tensor(w), opt_tensor(b), opt_tensor(running_mean),
-                                               opt_tensor(running_var))) {
+    // a 16-bit x: only with the 16-bit backward enabled next to it (`x16`), the one backward such a node can take
+    const bool fwd16 = act_dtype(x) != 0;
+    if ((fwd16 ? hip_forward_x16 && x16 : hip_forward) &&
+        bn_hip_forward_eligible(x, opt_tensor(w), opt_tensor(b), opt_tensor(running_mean), opt_tensor(running_var), fwd16)) {
       // the HIP forward: no reserve, no implementation index; such a node is eligible for the HIP backward by construction
+      // (autograd hands a dy of y's dtype and sizes)
       auto out = bn_hip_forward(x, opt_tensor(w), opt_tensor(b), opt_tensor(running_mean), opt_tensor(running_var), momentum,
                                 eps);
       ctx->save_for_backward({x, has_w ? *w : Tensor(), out[1], out[2], Tensor()});
       ctx->saved_data["hip_fwd"] = true;
-      ctx->saved_data["x16"] = false;
+      ctx->saved_data["x16"] = fwd16;
       ctx->set_materialize_grads(false);
       return out[0];
     }
@@ -819,7 +837,7 @@ class BatchNormTrainFn : public torch::autograd::Function<BatchNormTrainFn> {
   }
 
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    variable_list out(10);
+    variable_list out(11);
     if (!grads[0].defined()) return out;
     TORCH_CHECK(!(at::GradMode::is_enabled() && grads[0].requires_grad()),
                 "bn_train: the node is once-differentiable (no double backward)");
@@ -833,14 +851,14 @@ class BatchNormTrainFn : public torch::autograd::Function<BatchNormTrainFn> {
     if (hip && act_dtype(x) != 0 && ctx->saved_data["x16"].toBool() && grads[0].scalar_type() == x.scalar_type() &&
         grads[0].sizes() == x.sizes()) {
       const Tensor dy = like_layout(grads[0], x);
-      if (dy.is_cuda()) return bn_hip_backward(10, x, dy, Tensor(), w, mean, invstd, mask);
+      if (dy.is_cuda()) return bn_hip_backward(11, x, dy, Tensor(), w, mean, invstd, mask);
     }
     if (hip && x.scalar_type() == at::kFloat) {
       const Tensor dy = like_layout(grads[0].scalar_type() == at::kFloat ? grads[0] : grads[0].to(at::kFloat), x);
-      return bn_hip_backward(10, x, dy, Tensor(), w, mean, invstd, mask);
+      return bn_hip_backward(11, x, dy, Tensor(), w, mean, invstd, mask);
     }
-    TORCH_CHECK(!ctx->saved_data["hip_fwd"].toBool(), "bn_train: a node whose forward was mhaq_fq_bn_fwd has no framework "
-                "backward to fall back to");
+    TORCH_CHECK(!ctx->saved_data["hip_fwd"].toBool(), "bn_train: a node whose forward was mhaq_fq_bn_fwd / mhaq_fq_bn_fwd_x16 "
+                "has no framework backward to fall back to");
     auto opt = [](const Tensor& t) { return t.defined() ? std::optional<Tensor>(t) : std::nullopt; };
     auto get = [&](const char* k) {
       return ctx->saved_data.count(k) ? std::optional<Tensor>(ctx->saved_data[k].toTensor()) : std::nullopt;
@@ -857,11 +875,12 @@ class BatchNormTrainFn : public torch::autograd::Function<BatchNormTrainFn> {
 
 Tensor bn_train(const Tensor& x, const std::optional<Tensor>& w, const std::optional<Tensor>& b,
                 const std::optional<Tensor>& running_mean, const std::optional<Tensor>& running_var, double momentum,
-                double eps, bool cudnn_enabled, bool x16, bool hip_forward) {
+                double eps, bool cudnn_enabled, bool x16, bool hip_forward, bool hip_forward_x16) {
   TORCH_CHECK(w.has_value() && w->defined() && b.has_value() && b->defined(),
               "bn_train: an affine BatchNorm (weight and bias) is required");
   MHAQ_ON_DEVICE_OF(x);
-  return BatchNormTrainFn::apply(x, w, b, running_mean, running_var, momentum, eps, cudnn_enabled, x16, hip_forward);
+  return BatchNormTrainFn::apply(x, w, b, running_mean, running_var, momentum, eps, cudnn_enabled, x16, hip_forward,
+                                 hip_forward_x16);
 }
 
 // ------------------------------------------------------------------------------------------------ BatchNorm + stem pool
@@ -932,7 +951,7 @@ Tensor bn_pool_train(const Tensor& x, const std::optional<Tensor>& w, const std:
   // the fused node: fp32, with the 32-bit pixel arithmetic of its kernels (n * h * w < 2^31)
   if (!(bn_hip_eligible(x, *w) && x.scalar_type() == at::kFloat && x.numel() / x.size(1) < (1ll << 31)))
     return at::max_pool2d(BatchNormTrainFn::apply(x, w, b, running_mean, running_var, momentum, eps, cudnn_enabled,
-                                                  /*x16=*/false, hipf),
+                                                  /*x16=*/false, hipf, /*hip_forward_x16=*/false),
                           {3, 3}, {2, 2}, {1, 1});
   need_lib();
   return BatchNormPoolTrainFn::apply(x, *w, *b, running_mean, running_var, momentum, eps, cudnn_enabled, hipf);
@@ -1786,9 +1805,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // training BatchNorm: the framework's forward (mhaq_fq_bn_fwd with hip_forward, where eligible), the HIP backward
   m.def("bn_train", &bn_train, py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("running_mean"),
         py::arg("running_var"), py::arg("momentum"), py::arg("eps"), py::arg("cudnn_enabled") = true,
-        py::arg("x16") = false, py::arg("hip_forward") = false);
+        py::arg("x16") = false, py::arg("hip_forward") = false, py::arg("hip_forward_x16") = false);
   m.def("bn_hip_forwards", []() { return g_bn_hip_forwards.load(); },
         "number of BatchNorm forwards so far (bn_train and bn_pool_train) that ran mhaq_fq_bn_fwd instead of the framework's");
+  m.def("bn_hip_forwards_x16", []() { return g_bn_hip_forwards_x16.load(); },
+        "number of BatchNorm forwards so far (bn_train) that ran the 16-bit HIP kernels (mhaq_fq_bn_fwd_x16)");
 
   m.def("bn_hip_backwards", []() { return g_bn_hip_backwards.load(); },
         "number of BatchNorm backwards so far that ran the fp32 HIP kernels instead of the framework's backward");

@@ -446,6 +446,32 @@ def _nhwc_x16(t, name):
 
 
 @_on_device
+def bn_forward_train_x16(x, weight=None, bias=None, running_mean=None, running_var=None, factor=0.1, eps=1e-5):
+    """bn_forward_train on a dense channels_last bfloat16 / float16 tensor (mhaq_fq_bn_fwd_x16; no autograd: the compiled node
+    bn_train(x16=True, hip_forward_x16=True) is the differentiable form): the fp32 contract on the upcast input, y rounded
+    once into x's dtype.  The per-channel vectors and the returned statistics are float32."""
+    x = _nhwc_x16(x, "x")
+    c = x.shape[1]
+    m = x.numel() // max(c, 1)
+    vecs = [None if t is None else _require_cuda_f32(t.detach(), "a per-channel vector")
+            for t in (weight, bias, running_mean, running_var)]
+    if any(t is not None and (t.numel() != c or t.device != x.device) for t in vecs):
+        raise ValueError("bn_forward_train_x16: per-channel vectors must have C elements on x's device")
+    if any(t is not None and t.data_ptr() != o.data_ptr() for t, o in zip(vecs[2:], (running_mean, running_var))):
+        raise ValueError("bn_forward_train_x16: the running statistics must be contiguous (they are updated in place)")
+    L = _lib.lib()
+    y = torch.empty_like(x)
+    mean, invstd = (torch.empty(c, dtype=torch.float32, device=x.device) for _ in range(2))
+    nb = L.mhaq_fq_bn_fwd_x16_workspace_bytes(m, c)
+    ws = _workspace(max(nb, 16), x.device)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    _lib.check(L.mhaq_fq_bn_fwd_x16(x.data_ptr(), *map(ptr, vecs[:2]), y.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
+                                    *map(ptr, vecs[2:]), float(factor), float(eps), m, c, _X16[x.dtype], ws.data_ptr(), nb,
+                                    _stream()), "mhaq_fq_bn_fwd_x16")
+    return y, mean, invstd
+
+
+@_on_device
 def bn_infer_act_x16(x, consts, mode=BN_RELU, x2=None, consts2=None, residual=None):
     """bn_infer_act on dense channels_last bfloat16 / float16 tensors (mhaq_fq_bn_infer_act_x16; no autograd): the fp32
     arithmetic on the upcast inputs with the float32 slabs of bn_infer_consts, rounded once into a y of x's dtype."""

@@ -71,6 +71,10 @@ class QATConfig:
     # ... and the FORWARD of float32 inputs on mhaq_fq_bn_fwd, where hip_bn_backward installs (the bits of y and of the saved
     # and running statistics change).  Off by default; MHAQ_BN_FORWARD=1 / 0 in the environment overrides it.
     hip_bn_forward: bool = False
+    # ... and the forward of the 16-bit inputs of an autocast step on mhaq_fq_bn_fwd_x16 (the bits of y and of the statistics of a
+    # bf16 run change).  It has an effect only together with hip_bn_backward_16bit / MHAQ_BN_BACKWARD_X16 -- such a node has no
+    # other backward --; alone it changes nothing.  Off by default; MHAQ_BN_FORWARD_X16=1 / 0 in the environment overrides it.
+    hip_bn_forward_16bit: bool = False
     # the frozen teacher's BatchNorm, ReLU, residual add and stem pool in one HIP launch per place (frozen_blocks.py; fp32,
     # agrees with the stock eval modules to rounding, not bit for bit).  MHAQ_TEACHER_FUSED=0 in the environment switches it off.
     fuse_teacher: bool = True
@@ -241,7 +245,8 @@ class QATTrainer:
             from . import bn_backward
             if bn_backward.enabled_by_env():
                 bn_backward.install(net, x16=bn_backward.x16_enabled(cfg.hip_bn_backward_16bit),
-                                    hip_forward=bn_backward.hip_forward_enabled(cfg.hip_bn_forward))
+                                    hip_forward=bn_backward.hip_forward_enabled(cfg.hip_bn_forward),
+                                    hip_forward_x16=bn_backward.hip_forward_x16_enabled(cfg.hip_bn_forward_16bit))
         if cfg.fuse_teacher and cfg.distillation and layers is None and self.device.type == "cuda":
             from . import frozen_blocks
             if frozen_blocks.enabled_by_env():
