@@ -450,6 +450,30 @@ int mhaq_fq_bn_pool_bwd_x16(const void* x, const void* g, const uint8_t* code, c
                             int64_t c, int dtype, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * The training stem's forward on 16-bit tensors without a stored BatchNorm output: the third launch of mhaq_fq_bn_fwd_x16 and
+ * mhaq_fq_maxpool3s2_fwd_x16 in one.  Additive to ABI v4 -- MHAQ_FQ_ABI_VERSION stays 4; a caller discovers it by symbol.
+ *   x               dense NHWC [n, h, w, c] of the type named by `dtype`; p [n, oh, ow, c] of the same type and code
+ *                   [n, oh, ow, c] (one byte each) as in mhaq_fq_maxpool3s2_fwd_x16, with its limits and alignments: c % 8 == 0,
+ *                   c <= 2^22, n * h * w < 2^31; x and p 16-byte aligned, code 8-byte aligned
+ *   mean, invstd    fp32 [c], required: the batch statistics, as mhaq_fq_bn_fwd_x16 saves them (called with y == NULL it
+ *                   computes them, and updates the running statistics, in two launches)
+ *   weight, bias    fp32 [c], NULL = 1, 0; these four 4-byte aligned
+ * Contract: p and code are, bit for bit, what mhaq_fq_maxpool3s2_fwd_x16 writes from the y that mhaq_fq_bn_fwd_x16 writes from
+ * the same x, mean, invstd, weight and bias.  With a = weight * invstd (an fp32 product), every element of a window becomes
+ *   y = R16((up(x) - mean) * a + bias)
+ * in fp32, in this order, without contraction, rounded to nearest-even ONCE; the pool's selection runs on those ROUNDED values
+ * (the in-range positions in kh, then kw order, from -inf, replaced on  val > max || isnan(val)), p keeps the chosen y's 16
+ * bits, and the code 4 / code 9 rule is unchanged.  Pooling x and normalizing the winner is a different function: two x that
+ * round to one y tie, and the first in-range position wins; weight < 0 reverses the order; weight == 0 ties every window.
+ * Argument errors are returned before any launch, in mhaq_fq_maxpool3s2_fwd_x16's order with mean and invstd among the
+ * required pointers: NULL pointers, then the dtype, then non-positive sizes (MHAQ_FQ_EINVAL); width and range
+ * (MHAQ_FQ_EUNSUPPORTED); the alignment (MHAQ_FQ_EALIGN).  One launch, no workspace: stream-ordered, capture-safe, stateless.
+ * ---------------------------------------------------------------------- */
+int mhaq_fq_bn_norm_pool3s2_fwd_x16(const void* x, const float* mean, const float* invstd, const float* weight,
+                                    const float* bias, void* p, uint8_t* code, int64_t n, int64_t h, int64_t w, int64_t c,
+                                    int dtype, void* stream);
+
+/* ------------------------------------------------------------------------
  * Eval-mode BatchNorm of a FROZEN network (a distillation teacher: parameters and running statistics fixed between calls)
  * with what follows it in a ResNet block, one launch per place.  Additive to ABI v4 -- MHAQ_FQ_ABI_VERSION stays 4; a caller
  * discovers these entry points by symbol.  Tensors are dense fp32 NHWC seen as [m][c]; m >= 1, c % 4 == 0 and c <= 2^22

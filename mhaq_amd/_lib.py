@@ -73,6 +73,8 @@ SIGNATURES = {
     "mhaq_fq_maxpool3s2_fwd_x16": (_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _int, _p]),
     "mhaq_fq_bn_pool_bwd_x16_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "mhaq_fq_bn_pool_bwd_x16": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _int, _p, _sz, _p]),
+    # the 16-bit stem's forward from saved statistics: normalisation and pool in one launch, no stored y (additive, ABI v4 kept)
+    "mhaq_fq_bn_norm_pool3s2_fwd_x16": (_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _int, _p]),
     # eval-mode BatchNorm of a frozen network with its ReLU, residual add and stem pool (additive, ABI v4 kept)
     "mhaq_fq_bn_infer_consts": (_int, [_p, _p, _p, _p, C.c_double, _i64, _p, _p]),
     "mhaq_fq_bn_infer_act": (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _int, _p]),

@@ -23,7 +23,18 @@ environment for an unchanged benchmark; the variable, when set, overrides the co
 
 forward_pooled() is the same module with the ResNet stem's max pool behind it in one node (fused_blocks.FusedResNet18 calls
 it; csrc/torch_binding.cpp, BatchNormPoolTrainFn): same forward bits, and a backward that never materializes the pool's
-gradient.  float32 only (takes_pooled_node): a 16-bit stem stays maxpool(bn(c)), with the 16-bit backward above where enabled.
+gradient.  float32 by default (takes_pooled_node): a 16-bit stem stays maxpool(bn(c)), with the 16-bit backward above where
+enabled, unless the 16-bit pooled node below is switched on.
+
+Pooled node, 16-bit.  install(model, x16=True, pool_x16=True) lets forward_pooled() take a bf16 / fp16 input.  The node never
+calls the framework's 16-bit BatchNorm forward: mhaq_fq_bn_fwd_x16 without an output leaves the statistics (two launches),
+mhaq_fq_bn_norm_pool3s2_fwd_x16 normalizes and pools in one more -- the BatchNorm output and int64 indices are never written --,
+and the backward is mhaq_fq_bn_pool_bwd_x16.  Every output, statistic and gradient is, bit for bit, that of
+max_pool2d(bn(c)) with x16 and hip_forward_x16.  Where the compiled side finds the input ineligible (NCHW, C % 8 != 0,
+N * H * W == 1) it runs exactly that composition under the module's other flags.  Like hip_forward_x16 it has an effect only
+TOGETHER with x16.  OFF by default -- the stem's y and its saved and running statistics become the HIP forward's --:
+QATConfig.fuse_stem_pool_16bit=True per trainer (next to hip_bn_backward_16bit), MHAQ_STEM_POOL_X16=1 in the environment (next
+to MHAQ_BN_BACKWARD_X16=1), with the same semantics.
 
 HIP forward.  install(model, hip_forward=True) also runs the FORWARD of a float32 input on the kernels of csrc/bn_bwd.hip
 (mhaq_fq_bn_fwd: shifted fp64 sums, statistics rounded once, y = (x - mean) * (gamma * invstd) + beta); the node falls back to
@@ -36,7 +47,7 @@ HIP forward, 16-bit.  install(model, x16=True, hip_forward_x16=True) runs the fo
 mhaq_fq_bn_fwd_x16: the same contract on the exactly upcast input -- float32 statistics, y rounded to nearest-even once --,
 with C % 8 == 0 and N * H * W >= 2, else the framework's forward bit for bit.  It has an effect only TOGETHER with x16: the
 16-bit HIP backward is the only backward of such a node, so hip_forward_x16 alone changes nothing (and does not raise).  The
-stem keeps maxpool(bn(c)) on the unpooled node.  OFF by default -- it changes the bits of y and of the saved and running
+stem keeps maxpool(bn(c)) on the unpooled node (without pool_x16).  OFF by default -- it changes the bits of y and of the saved and running
 statistics of every bf16 run --: QATConfig.hip_bn_forward_16bit=True per trainer (next to hip_bn_backward_16bit),
 MHAQ_BN_FORWARD_X16=1 in the environment (next to MHAQ_BN_BACKWARD_X16=1), with the same semantics.
 
@@ -54,9 +65,11 @@ ENV_SWITCH = "MHAQ_BN_BACKWARD"
 ENV_SWITCH_X16 = "MHAQ_BN_BACKWARD_X16"
 ENV_SWITCH_FORWARD = "MHAQ_BN_FORWARD"
 ENV_SWITCH_FORWARD_X16 = "MHAQ_BN_FORWARD_X16"
+ENV_SWITCH_POOL_X16 = "MHAQ_STEM_POOL_X16"
 _X16 = "_mhaq_bn_x16"          # per-module flag in the instance __dict__ (not a parameter, buffer or state_dict entry)
 _HIP_FWD = "_mhaq_bn_hip_forward"      # likewise
 _HIP_FWD_X16 = "_mhaq_bn_hip_forward_x16"      # likewise
+_POOL_X16 = "_mhaq_bn_pool_x16"      # likewise
 
 
 def enabled_by_env() -> bool:
@@ -80,6 +93,12 @@ def hip_forward_x16_enabled(configured: bool = False) -> bool:
     """The 16-bit HIP forward's switch: `configured` (QATConfig.hip_bn_forward_16bit) unless MHAQ_BN_FORWARD_X16 is set, which
     then decides, as in x16_enabled().  The forward runs only where the 16-bit backward's switch is on as well."""
     return _env_or(ENV_SWITCH_FORWARD_X16, configured)
+
+
+def pool_x16_enabled(configured: bool = False) -> bool:
+    """The 16-bit pooled stem node's switch: `configured` (QATConfig.fuse_stem_pool_16bit) unless MHAQ_STEM_POOL_X16 is set,
+    which then decides, as in x16_enabled().  The node runs only where the 16-bit backward's switch is on as well."""
+    return _env_or(ENV_SWITCH_POOL_X16, configured)
 
 
 def _env_or(name: str, configured: bool) -> bool:
@@ -112,9 +131,16 @@ class HipBackwardBatchNorm2d(nn.BatchNorm2d):
         where takes_x16() holds as well)."""
         return bool(self.__dict__.get(_HIP_FWD_X16, False))
 
+    def takes_pool_x16(self) -> bool:
+        """True when install(..., pool_x16=True) enabled the 16-bit pooled node for this module (it runs only where takes_x16()
+        holds as well)."""
+        return bool(self.__dict__.get(_POOL_X16, False))
+
     def takes_pooled_node(self, input) -> bool:
-        """True when forward_pooled() applies: the pooled node's kernels are float32."""
-        return input.dtype == torch.float32 and self.takes_node(input)
+        """True when forward_pooled() applies: a float32 input, or a 16-bit one on a module with x16 and pool_x16."""
+        if not self.takes_node(input):
+            return False
+        return input.dtype == torch.float32 or (self.takes_x16() and self.takes_pool_x16())
 
     def _step_average_factor(self) -> float:
         """The bookkeeping of _BatchNorm.forward (training mode, tracked statistics): counts the batch, returns the
@@ -143,15 +169,21 @@ class HipBackwardBatchNorm2d(nn.BatchNorm2d):
 
     def forward_pooled(self, input):
         """max_pool2d(self(input), 3, 2, 1) as one node (bn_pool_train: the BatchNorm output is not kept, the backward
-        gathers its dy from the pooled gradient).  Call only when takes_pooled_node(input) holds."""
+        gathers its dy from the pooled gradient).  Call only when takes_pooled_node(input) holds.  A 16-bit input the compiled
+        side finds ineligible (NCHW, C % 8 != 0, N * H * W == 1) runs as max_pool2d(self(input), 3, 2, 1) there, under this
+        module's other flags."""
         from . import _ext
-        return self._node(_ext.ext().bn_pool_train, input, input.dtype == torch.float32 and self.takes_hip_forward())
+        if input.dtype == torch.float32:
+            return self._node(_ext.ext().bn_pool_train, input, self.takes_hip_forward())
+        return self._node(_ext.ext().bn_pool_train, input, False, self.takes_x16(), self.takes_pool_x16(),
+                          self.takes_x16() and self.takes_hip_forward_x16())
 
 
-def install(model: nn.Module, x16: bool = False, hip_forward: bool = False, hip_forward_x16: bool = False) -> int:
+def install(model: nn.Module, x16: bool = False, hip_forward: bool = False, hip_forward_x16: bool = False,
+            pool_x16: bool = False) -> int:
     """Give every nn.BatchNorm2d of `model` (the exact type) the forward above; x16=True also enables the 16-bit backward
-    on them, hip_forward=True the HIP forward of float32 inputs, hip_forward_x16=True (with x16) that of 16-bit inputs.
-    Returns the number of modules switched."""
+    on them, hip_forward=True the HIP forward of float32 inputs, hip_forward_x16=True (with x16) that of 16-bit inputs,
+    pool_x16=True (with x16) the pooled node on 16-bit inputs.  Returns the number of modules switched."""
     switched = 0
     for m in model.modules():
         if type(m) is nn.BatchNorm2d:
@@ -162,6 +194,8 @@ def install(model: nn.Module, x16: bool = False, hip_forward: bool = False, hip_
                 m.__dict__[_HIP_FWD] = True
             if hip_forward_x16:
                 m.__dict__[_HIP_FWD_X16] = True
+            if pool_x16:
+                m.__dict__[_POOL_X16] = True
             switched += 1
     return switched
 
@@ -173,3 +207,4 @@ def uninstall(model: nn.Module) -> None:
             m.__dict__.pop(_X16, None)
             m.__dict__.pop(_HIP_FWD, None)
             m.__dict__.pop(_HIP_FWD_X16, None)
+            m.__dict__.pop(_POOL_X16, None)

@@ -24,7 +24,7 @@
 // 16 bits in registers where the framework's pool backward rounds the tensor it would have written.
 //
 // The host side is written once ("the host path of the entry points" below): bn_bwd_status is the argument check of all four
-// backward entry points and pool_fwd_status that of the two pool forwards, bn_workspace_bytes stands behind the four workspace
+// backward entry points and pool_fwd_status that of the pool forwards (the pooled stem forward included), bn_workspace_bytes stands behind the four workspace
 // queries, and io16::with_dtype (fq_io16.hpp) turns the dtype of an *_x16 call into the template argument, so that every
 // bn_bwd_launch<Dy, RU> is named in one place.
 #include "fq_io16.hpp"
@@ -742,7 +742,11 @@ __global__ __launch_bounds__(kBlock) void bn_fwd_finalize_kernel(
   }
 }
 
-// y = (x - mean) * a + beta in fp32, in this order (the build contracts nothing).  Block, loads and the column arithmetic of
+// The element body of the training forward, y = (x - mean) * a + beta in fp32, in this order (the build contracts nothing):
+// bn_fwd_norm_kernel's, and that of the pooled stem forward at the end of this file (bn_norm_pool3s2_fwd16_kernel).
+__device__ __forceinline__ float bn_norm_elem(float x, float mean, float a, float beta) { return (x - mean) * a + beta; }
+
+// y = bn_norm_elem(x, ..) per element.  Block, loads and the column arithmetic of
 // the constants are bn_bwd_dx_kernel's; occupancy by size likewise.
 template <class IO>
 constexpr int kBnFwdWaves = IO::kW == 8 ? 6 : 8;
@@ -788,7 +792,7 @@ __launch_bounds__(kBlock) void bn_fwd_norm_kernel(
 #pragma unroll
       for (int j = 0; j < K; ++j) {
         const int h = j >> 2, i = j & 3;
-        o[j] = (xv[j] - k[0][h][i]) * k[1][h][i] + k[2][h][i];
+        o[j] = bn_norm_elem(xv[j], k[0][h][i], k[1][h][i], k[2][h][i]);
       }
       IO::st(y, idx, o);
     }
@@ -1198,10 +1202,60 @@ __global__ __launch_bounds__(kBlock) void bn_relu_pool3s2_kernel(
 // The same pool on a dense 16-bit NHWC tensor of the element type DT: one lane per 8 output channels, nine 16-byte loads, a
 // 16-byte store of p and an 8-byte store of codes.  Selection and codes as above, compared on the exactly upcast values (the
 // framework's kernel compares in fp32 too); what is stored is the chosen element's ORIGINAL 16 bits, so a NaN keeps its payload.
-template <int DT>
+// The kernel is written once for two entry points.  `Pre` says what the pool is taken of: the loaded tensor itself (PoolOfTensor,
+// mhaq_fq_maxpool3s2_fwd_x16: no further argument, and nothing is compiled in -- the instruction stream is that of the kernel
+// before `Pre` existed) or the training BatchNorm's output of it, which is never stored (PoolOfNorm,
+// mhaq_fq_bn_norm_pool3s2_fwd_x16: the stem's forward, the BatchNorm's third launch and the pool in one).  A `Pre` is built from
+// the kernel's trailing arguments, fetches what it needs for the lane's eight channels under the data loads and turns each
+// loaded vector into the 16-bit values the selection runs on.
+struct PoolOfTensor {
+  static constexpr bool kTransforms = false;
+  struct K {};
+};
+// y = R16(bn_norm_elem(up(x), mean, a, beta)), the 16 bits bn_fwd_norm_kernel stores: a = weight * invstd is
+// bn_fwd_finalize_kernel's fp32 product, the rounding Io16::st's io16::down2.  The selection then runs on THOSE values, not on
+// x: two x that round to one y are a tie that the first in-range position wins, gamma < 0 reverses the order and gamma == 0
+// ties every window, as in the pool of the stored y.  (All nine vectors are converted, the out-of-range ones too: 36 packed
+// converts and no branch.)  The four rows are fp32 [C], 4-byte aligned: scalar indexing, as bn_bwd_reduce_kernel reads the mean.
+struct PoolOfNorm {
+  static constexpr bool kTransforms = true;
+  const float* __restrict__ mean;
+  const float* __restrict__ invstd;
+  const float* __restrict__ weight;                // NULL: 1
+  const float* __restrict__ bias;                  // NULL: 0
+  struct K { float mu[8], a[8], beta[8]; };
+  __device__ __forceinline__ K fetch(uint32_t col) const {
+    K k;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uint32_t ch = col * 8u + (uint32_t)j;
+      k.mu[j] = mean[ch];
+      k.a[j] = (weight ? weight[ch] : 1.0f) * invstd[ch];
+      k.beta[j] = bias ? bias[ch] : 0.0f;
+      // Where two NaNs meet in one multiply or add, the operand ORDER of the instruction decides whose sign and payload survive,
+      // and the compiler orders the operands of each kernel as it likes.  bn_fwd_norm_kernel has them in the order of the
+      // source -- the NaN of x - mean survives a NaN a, the NaN of the product a NaN beta --, so the channels in which two can
+      // meet (a NaN statistic: an x that holds a NaN) get constants that cannot be NaN where the result is decided anyway:
+      // y = NaN(x - mean) * 1 + 0 under a NaN mean, y = NaN(.. * a) + 0 under a NaN a.  The same bits, in either operand order.
+      if (k.mu[j] != k.mu[j]) k.a[j] = 1.0f;
+      if (k.mu[j] != k.mu[j] || k.a[j] != k.a[j]) k.beta[j] = 0.0f;
+    }
+    return k;
+  }
+  template <int DT>
+  static __device__ __forceinline__ void apply(const K& k, io16::vu4& v) {
+    float e[8];
+    Io16<DT>::unpack(v, e);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) e[j] = bn_norm_elem(e[j], k.mu[j], k.a[j], k.beta[j]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = io16::down2<DT>(e[2 * i], e[2 * i + 1]);
+  }
+};
+template <int DT, class Pre = PoolOfTensor, class... PreArgs>
 __global__ __launch_bounds__(kBlock) void maxpool3s2_fwd16_kernel(
     const uint16_t* __restrict__ t, uint16_t* __restrict__ p, uint8_t* __restrict__ code, uint32_t h, uint32_t w, uint32_t oh,
-    uint32_t ow, uint32_t cv, int64_t nvec) {
+    uint32_t ow, uint32_t cv, int64_t nvec, PreArgs... pre_args) {
   typedef uint32_t vu2 __attribute__((ext_vector_type(2)));
   const uint32_t bq = blockIdx.x / cv, br = (blockIdx.x - bq * cv) * (uint32_t)kBlock, brq = br / cv;
   const uint32_t tt = br - brq * cv + threadIdx.x, tq = tt / cv;
@@ -1221,7 +1275,13 @@ __global__ __launch_bounds__(kBlock) void maxpool3s2_fwd16_kernel(
     v[k] = io16::ld8<false>(t, (int64_t)((n * h + ihc) * w + iwc) * cv + col);
   }
   __builtin_amdgcn_sched_barrier(0);
+  [[maybe_unused]] typename Pre::K pk;
+  if constexpr (Pre::kTransforms) pk = Pre{pre_args...}.fetch(col);
   if (!ok) return;
+  if constexpr (Pre::kTransforms) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Pre::template apply<DT>(pk, v[k]);
+  }
   const uint32_t start = (po == 0u && pw == 0u) ? 4u : kPoolNoneChosen;     // the framework's initial index 0
   float mx[8];
   uint32_t raw[8], cd[8];                         // raw: the chosen element's 16 bits (-inf until one is chosen)
@@ -1251,7 +1311,8 @@ __global__ __launch_bounds__(kBlock) void maxpool3s2_fwd16_kernel(
                                           cd[4] | (cd[5] << 8) | (cd[6] << 16) | (cd[7] << 24)};
 }
 
-// The frozen stem on a dense 16-bit NHWC x (mhaq_fq_bn_relu_pool3s2_x16): the kernel above without the codes and with the
+
+// The frozen stem on a dense 16-bit NHWC x (mhaq_fq_bn_relu_pool3s2_x16): maxpool3s2_fwd16_kernel without the codes and with the
 // constants of the lane's eight channels under the nine loads, as bn_relu_pool3s2_kernel relates to the fp32 pool forward.
 // Every in-range value is upcast exactly, takes bn_infer_act_kernel's fp32 arithmetic and is compared in fp32; the maximum is
 // rounded to 16 bits ONCE at the end -- rounding is monotone, so this is the value of rounding all nine first, for 4 packed
@@ -1356,15 +1417,21 @@ static int pool_fwd_status(const void* t, const void* p, const uint8_t* code, in
   if (!bn_aligned(t, 16) || !bn_aligned(p, 16) || !bn_aligned(code, kw)) return MHAQ_FQ_EALIGN;
   return 0;
 }
-template <class T>
-static int pool_fwd_launch(void (*kernel)(const T*, T*, uint8_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int64_t),
-                           const void* t, void* p, uint8_t* code, int64_t n, int64_t h, int64_t w, int64_t c, void* stream) {
+// (more: what the kernel takes behind nvec -- the statistics and parameters of PoolOfNorm)
+template <class... More>
+using Pool16Kernel = void (*)(const uint16_t*, uint16_t*, uint8_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int64_t,
+                              More...);
+template <class T, class... More>
+static int pool_fwd_launch(void (*kernel)(const T*, T*, uint8_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int64_t,
+                                          More...),
+                           const void* t, void* p, uint8_t* code, int64_t n, int64_t h, int64_t w, int64_t c, void* stream,
+                           More... more) {
   constexpr int64_t kw = 16 / sizeof(T);
   const int64_t oh = pool_out(h), ow = pool_out(w), nvec = n * oh * ow * (c / kw);
   const int64_t grid = (nvec + kBlock - 1) / kBlock;
   if (grid > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
   MHAQ_LAUNCH(kernel, dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream, (const T*)t, (T*)p, code, (uint32_t)h,
-              (uint32_t)w, (uint32_t)oh, (uint32_t)ow, (uint32_t)(c / kw), nvec);
+              (uint32_t)w, (uint32_t)oh, (uint32_t)ow, (uint32_t)(c / kw), nvec, more...);
   return launch_status();
 }
 
@@ -1496,7 +1563,22 @@ int mhaq_fq_maxpool3s2_fwd_x16(const void* t, void* p, uint8_t* code, int64_t n,
                                void* stream) {
   if (const int rc = pool_fwd_status(t, p, code, 8, dtype, n, h, w, c)) return rc;
   return io16::with_dtype(dtype, [&](auto dt) {
-    return pool_fwd_launch<uint16_t>(maxpool3s2_fwd16_kernel<decltype(dt)::value>, t, p, code, n, h, w, c, stream);
+    const Pool16Kernel<> k = maxpool3s2_fwd16_kernel<decltype(dt)::value>;
+    return pool_fwd_launch(k, t, p, code, n, h, w, c, stream);
+  });
+}
+
+int mhaq_fq_bn_norm_pool3s2_fwd_x16(const void* x, const float* mean, const float* invstd, const float* weight,
+                                    const float* bias, void* p, uint8_t* code, int64_t n, int64_t h, int64_t w, int64_t c,
+                                    int dtype, void* stream) {
+  // mhaq_fq_maxpool3s2_fwd_x16's checks in its order, the statistics among the required pointers and the 4-byte rows last
+  if (!mean || !invstd) return MHAQ_FQ_EINVAL;
+  if (const int rc = pool_fwd_status(x, p, code, 8, dtype, n, h, w, c)) return rc;
+  if (!bn_aligned(mean, 4) || !bn_aligned(invstd, 4) || !bn_aligned(weight, 4) || !bn_aligned(bias, 4)) return MHAQ_FQ_EALIGN;
+  return io16::with_dtype(dtype, [&](auto dt) {
+    const Pool16Kernel<const float*, const float*, const float*, const float*> k =
+        maxpool3s2_fwd16_kernel<decltype(dt)::value, PoolOfNorm>;
+    return pool_fwd_launch(k, x, p, code, n, h, w, c, stream, mean, invstd, weight, bias);
   });
 }
 

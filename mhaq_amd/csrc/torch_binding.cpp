@@ -59,6 +59,7 @@ namespace {
   X(mhaq_fq_bn_pool_bwd_workspace_bytes) X(mhaq_fq_bn_pool_bwd) X(mhaq_fq_bn_bwd_x16_workspace_bytes)                 \
   X(mhaq_fq_bn_bwd_x16) X(mhaq_fq_bn_fwd_workspace_bytes) X(mhaq_fq_bn_fwd)                                         \
   X(mhaq_fq_bn_fwd_x16_workspace_bytes) X(mhaq_fq_bn_fwd_x16)                                                       \
+  X(mhaq_fq_bn_pool_bwd_x16_workspace_bytes) X(mhaq_fq_bn_pool_bwd_x16) X(mhaq_fq_bn_norm_pool3s2_fwd_x16)          \
   X(mhaq_fq_bn_infer_consts) X(mhaq_fq_bn_infer_act) X(mhaq_fq_bn_relu_pool3s2)                                     \
   X(mhaq_fq_bn_infer_act_x16) X(mhaq_fq_bn_relu_pool3s2_x16)                                                        \
   X(mhaq_fq_radam_chunk_elements) X(mhaq_fq_radam_step)
@@ -696,7 +697,7 @@ inline bool aligned16(const Tensor& t) { return (reinterpret_cast<uintptr_t>(t.c
 // What every HIP route asks: x a non-empty dense channels_last device tensor of fp32, bf16 or fp16, 16-byte aligned, C a multiple
 // of the channels in a lane's 16 bytes (4, 8 for 16-bit elements); the statistics (absent before the forward has produced them)
 // and the optional weight fp32, contiguous and of length C.  The 16-bit route adds "dy has x's dtype and sizes", the pooled
-// node "fp32, n * h * w < 2^31 and a weight", at their call sites.
+// node "n * h * w < 2^31 and a weight" (and, for a 16-bit x, the HIP forward's eligibility), at their call sites.
 inline bool bn_hip_eligible(const Tensor& x, const Tensor& w, const Tensor* mean = nullptr, const Tensor* invstd = nullptr) {
   if (!x.is_cuda() || (x.scalar_type() != at::kFloat && act_dtype(x) == 0) || x.dim() != 4 || x.numel() == 0) return false;
   if (!x.is_contiguous(at::MemoryFormat::ChannelsLast) || (x.size(1) & (act_dtype(x) ? 7 : 3)) || !aligned16(x)) return false;
@@ -709,6 +710,8 @@ inline bool bn_hip_eligible(const Tensor& x, const Tensor& w, const Tensor* mean
 std::atomic<int64_t> g_bn_hip_backwards{0};   // backwards that took mhaq_fq_bn_bwd (tests: the fallback is never silent)
 std::atomic<int64_t> g_bn_hip_backwards_x16{0};   // ... that took mhaq_fq_bn_bwd_x16
 std::atomic<int64_t> g_bn_pool_hip_backwards{0};   // ... that took mhaq_fq_bn_pool_bwd
+std::atomic<int64_t> g_bn_pool_hip_backwards_x16{0};   // ... that took mhaq_fq_bn_pool_bwd_x16
+std::atomic<int64_t> g_bn_pool_hip_forwards_x16{0};   // forwards of the 16-bit pooled node (mhaq_fq_bn_norm_pool3s2_fwd_x16)
 
 // ... and the opt-in HIP FORWARD (mhaq_fq_bn_fwd; `hip_forward` of bn_train / bn_pool_train): taken where bn_hip_eligible
 // holds for an fp32 x with N * H * W >= 2, the bias is eligible like the weight, and the running statistics are both absent or
@@ -730,22 +733,25 @@ inline bool bn_hip_forward_eligible(const Tensor& x, const Tensor& w, const Tens
 
 // One HIP BatchNorm forward of an eligible x: {y, mean, invstd}; the running statistics are updated in place, with their
 // version counters bumped as the framework's in-place update bumps them.  The entry point follows from x's dtype; the
-// statistics are fp32 either way.
+// statistics are fp32 either way.  with_y = false (the 16-bit pooled node): the statistics alone, y stays undefined and the
+// third launch is skipped (y == NULL); that call belongs to the pooled node's counter, not to bn_hip_forwards_x16.
 std::array<Tensor, 3> bn_hip_forward(const Tensor& x, const Tensor& w, const Tensor& b, const Tensor& rm, const Tensor& rv,
-                                     double momentum, double eps) {
+                                     double momentum, double eps, bool with_y = true) {
   need_lib();
   const int64_t c = x.size(1), m = x.numel() / c;
-  Tensor y = at::empty_like(x);
+  Tensor y = with_y ? at::empty_like(x) : Tensor();
   const int dt = act_dtype(x);
+  TORCH_CHECK(with_y || dt, "bn_hip_forward: the statistics-only form is the 16-bit pooled node's");
   Tensor mean = at::empty({c}, x.options().dtype(at::kFloat)), invstd = at::empty({c}, x.options().dtype(at::kFloat));
   const size_t nb = dt ? A.mhaq_fq_bn_fwd_x16_workspace_bytes(m, c) : A.mhaq_fq_bn_fwd_workspace_bytes(m, c);
   Tensor ws = at::empty({(int64_t)nb}, x.options().dtype(at::kByte));
   float *rmp = rm.defined() ? fptr_mut(rm) : nullptr, *rvp = rv.defined() ? fptr_mut(rv) : nullptr;
   if (dt) {
-    check(A.mhaq_fq_bn_fwd_x16(x.const_data_ptr(), fptr_or_null(w), fptr_or_null(b), y.mutable_data_ptr(), fptr_mut(mean),
-                               fptr_mut(invstd), rmp, rvp, momentum, eps, m, c, dt, ws.mutable_data_ptr(), nb, cur_stream(x)),
+    check(A.mhaq_fq_bn_fwd_x16(x.const_data_ptr(), fptr_or_null(w), fptr_or_null(b), with_y ? y.mutable_data_ptr() : nullptr,
+                               fptr_mut(mean), fptr_mut(invstd), rmp, rvp, momentum, eps, m, c, dt, ws.mutable_data_ptr(), nb,
+                               cur_stream(x)),
           "mhaq_fq_bn_fwd_x16");
-    g_bn_hip_forwards_x16.fetch_add(1, std::memory_order_relaxed);
+    if (with_y) g_bn_hip_forwards_x16.fetch_add(1, std::memory_order_relaxed);
   } else {
     check(A.mhaq_fq_bn_fwd(fptr(x), fptr_or_null(w), fptr_or_null(b), fptr_mut(y), fptr_mut(mean), fptr_mut(invstd), rmp, rvp,
                            momentum, eps, m, c, ws.mutable_data_ptr(), nb, cur_stream(x)),
@@ -761,23 +767,28 @@ std::array<Tensor, 3> bn_hip_forward(const Tensor& x, const Tensor& w, const Ten
 
 // One HIP BatchNorm backward of an eligible x: {dx, dweight, dbias} in the first three of `slots` outputs, undefined where the
 // mask says so.  The gradient comes as dy in x's layout or, with `code`, as the pooled gradient in the layout of its argmax
-// codes; the entry point follows from that and from x's dtype.  (The 16-bit pooled form, which the binding does not load,
-// would be one more case.)
+// codes (of x's dtype either way); the entry point follows from that and from x's dtype: four cases.
 variable_list bn_hip_backward(size_t slots, const Tensor& x, const Tensor& grad, const Tensor& code, const Tensor& w,
                               const Tensor& mean, const Tensor& invstd, const std::array<bool, 3>& mask) {
   need_lib();
   const int64_t n = x.size(0), c = x.size(1), h = x.size(2), wd = x.size(3), m = x.numel() / c;
   const int dt = act_dtype(x);
-  TORCH_CHECK(!(code.defined() && dt), "bn_hip_backward: there is no 16-bit pooled route");
   Tensor dx = mask[0] ? at::empty_like(x) : Tensor();
   Tensor dw = mask[1] ? at::empty_like(w) : Tensor();
   Tensor db = mask[2] ? at::empty({c}, mean.options()) : Tensor();
-  const size_t nb = code.defined() ? A.mhaq_fq_bn_pool_bwd_workspace_bytes(n, h, wd, c)
+  const size_t nb = code.defined() ? (dt ? A.mhaq_fq_bn_pool_bwd_x16_workspace_bytes(n, h, wd, c)
+                                         : A.mhaq_fq_bn_pool_bwd_workspace_bytes(n, h, wd, c))
                                    : dt ? A.mhaq_fq_bn_bwd_x16_workspace_bytes(m, c) : A.mhaq_fq_bn_bwd_workspace_bytes(m, c);
   Tensor ws = at::empty({(int64_t)nb}, x.options().dtype(at::kByte));
   void* dxp = mask[0] ? dx.mutable_data_ptr() : nullptr;
   float *dwp = mask[1] ? fptr_mut(dw) : nullptr, *dbp = mask[2] ? fptr_mut(db) : nullptr;
-  if (code.defined()) {
+  if (code.defined() && dt) {
+    check(A.mhaq_fq_bn_pool_bwd_x16(x.const_data_ptr(), grad.const_data_ptr(), static_cast<const uint8_t*>(code.const_data_ptr()),
+                                    fptr(mean), fptr(invstd), fptr_or_null(w), dxp, dwp, dbp, n, h, wd, c, dt,
+                                    ws.mutable_data_ptr(), nb, cur_stream(x)),
+          "mhaq_fq_bn_pool_bwd_x16");
+    g_bn_pool_hip_backwards_x16.fetch_add(1, std::memory_order_relaxed);
+  } else if (code.defined()) {
     check(A.mhaq_fq_bn_pool_bwd(fptr(x), fptr(grad), static_cast<const uint8_t*>(code.const_data_ptr()), fptr(mean),
                                 fptr(invstd), fptr_or_null(w), static_cast<float*>(dxp), dwp, dbp, n, h, wd, c,
                                 ws.mutable_data_ptr(), nb, cur_stream(x)),
@@ -891,12 +902,36 @@ Tensor bn_train(const Tensor& x, const std::optional<Tensor>& w, const std::opti
 // of reading a materialized one.  Output, running statistics and the three gradients are the bits of the two nodes run one
 // after the other.  Taken under BatchNormTrainFn's own conditions (and n * h * w < 2^31); outside them bn_pool_train IS
 // that composition.
+// The 16-bit form (`pool_x16` next to `x16`; a bf16 / fp16 x under autocast) never calls the framework's 16-bit BatchNorm forward:
+// mhaq_fq_bn_fwd_x16 with y == NULL leaves the statistics (and updates the running ones) in two launches, and
+// mhaq_fq_bn_norm_pool3s2_fwd_x16 writes the pooled tensor and the codes from x and those statistics in a third: neither the
+// BatchNorm output nor int64 indices exist at any time.  Backward: mhaq_fq_bn_pool_bwd_x16 on a pooled gradient of x's dtype.
+// Its outputs, statistics and gradients are the bits of max_pool2d(bn_train(x, .., x16, hip_forward_x16 = true)).  Taken where
+// that 16-bit HIP forward would apply (bn_hip_forward_eligible) and n * h * w < 2^31; a 16-bit x outside that is
+// max_pool2d(bn_train(x, ..)) with the caller's x16 and hip_forward_x16.
 class BatchNormPoolTrainFn : public torch::autograd::Function<BatchNormPoolTrainFn> {
  public:
   static Tensor forward(AutogradContext* ctx, const Tensor& x, const Tensor& w, const Tensor& b,
                         const std::optional<Tensor>& running_mean, const std::optional<Tensor>& running_var,
-                        double momentum, double eps, bool cudnn_enabled, bool hip_forward) {
-    // hip_forward: bn_pool_train has checked bn_hip_forward_eligible before this node was entered
+                        double momentum, double eps, bool cudnn_enabled, bool hip_forward, bool pool_x16) {
+    // hip_forward, pool_x16: bn_pool_train has checked bn_hip_forward_eligible before this node was entered
+    const int64_t n = x.size(0), c = x.size(1), h = x.size(2), wd = x.size(3);
+    if (pool_x16) {
+      // a 16-bit x: the statistics from mhaq_fq_bn_fwd_x16 without a y (two launches; the running statistics are updated), then
+      // normalisation and pool in one launch.  The framework's 16-bit BatchNorm forward is not called on this path.
+      auto out = bn_hip_forward(x, w, b, opt_tensor(running_mean), opt_tensor(running_var), momentum, eps, /*with_y=*/false);
+      const Tensor &mean = out[1], &invstd = out[2];
+      Tensor p = at::empty({n, c, (h - 1) / 2 + 1, (wd - 1) / 2 + 1}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
+      Tensor code = at::empty_like(p, p.options().dtype(at::kByte));      // p's strides: NHWC, one byte per element
+      check(A.mhaq_fq_bn_norm_pool3s2_fwd_x16(x.const_data_ptr(), fptr(mean), fptr(invstd), fptr(w), fptr(b), p.mutable_data_ptr(),
+                                              static_cast<uint8_t*>(code.mutable_data_ptr()), n, h, wd, c, act_dtype(x),
+                                              cur_stream(x)),
+            "mhaq_fq_bn_norm_pool3s2_fwd_x16");
+      g_bn_pool_hip_forwards_x16.fetch_add(1, std::memory_order_relaxed);
+      ctx->save_for_backward({x, w, mean, invstd, code});
+      ctx->set_materialize_grads(false);
+      return p;
+    }
     Tensor t, mean, invstd;
     if (hip_forward) {
       auto out = bn_hip_forward(x, w, b, opt_tensor(running_mean), opt_tensor(running_var), momentum, eps);
@@ -909,7 +944,6 @@ class BatchNormPoolTrainFn : public torch::autograd::Function<BatchNormPoolTrain
     }
     TORCH_CHECK(bn_hip_eligible(x, w, &mean, &invstd), "bn_pool_train: the BatchNorm forward left statistics the HIP "
                 "backward cannot read (there is no fallback behind this point)");
-    const int64_t n = x.size(0), c = x.size(1), h = x.size(2), wd = x.size(3);
     Tensor p = at::empty({n, c, (h - 1) / 2 + 1, (wd - 1) / 2 + 1}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
     Tensor code = at::empty_like(p, p.options().dtype(at::kByte));
     check(A.mhaq_fq_maxpool3s2_fwd(fptr(t), fptr_mut(p), static_cast<uint8_t*>(code.mutable_data_ptr()), n, h, wd, c,
@@ -921,7 +955,7 @@ class BatchNormPoolTrainFn : public torch::autograd::Function<BatchNormPoolTrain
   }
 
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    variable_list out(9);
+    variable_list out(10);
     if (!grads[0].defined()) return out;
     TORCH_CHECK(!(at::GradMode::is_enabled() && grads[0].requires_grad()),
                 "bn_pool_train: the node is once-differentiable (no double backward)");
@@ -929,23 +963,39 @@ class BatchNormPoolTrainFn : public torch::autograd::Function<BatchNormPoolTrain
     auto saved = ctx->get_saved_variables();
     const Tensor &x = saved[0], &w = saved[1], &mean = saved[2], &invstd = saved[3], &code = saved[4];
     const std::array<bool, 3> mask = {ctx->needs_input_grad(0), ctx->needs_input_grad(1), ctx->needs_input_grad(2)};
-    // the pooled gradient in the memory order of the pooled tensor (= the codes')
-    Tensor g = grads[0].scalar_type() == at::kFloat ? grads[0] : grads[0].to(at::kFloat);
+    // the pooled gradient in x's dtype (fp32, or the 16-bit node's) and the memory order of the pooled tensor (= the codes')
+    const auto gt = x.scalar_type();
+    Tensor g = grads[0].scalar_type() == gt ? grads[0] : grads[0].to(gt);
     if (g.sizes() != code.sizes() || g.strides() != code.strides()) {
-      Tensor dense = at::empty_like(code, code.options().dtype(at::kFloat));
+      Tensor dense = at::empty_like(code, code.options().dtype(gt));
       dense.copy_(g);
       g = dense;
     }
-    return bn_hip_backward(9, x, g, code, w, mean, invstd, mask);
+    return bn_hip_backward(10, x, g, code, w, mean, invstd, mask);
   }
 };
 
 Tensor bn_pool_train(const Tensor& x, const std::optional<Tensor>& w, const std::optional<Tensor>& b,
                      const std::optional<Tensor>& running_mean, const std::optional<Tensor>& running_var, double momentum,
-                     double eps, bool cudnn_enabled, bool hip_forward) {
+                     double eps, bool cudnn_enabled, bool hip_forward, bool x16, bool pool_x16, bool hip_forward_x16) {
   TORCH_CHECK(w.has_value() && w->defined() && b.has_value() && b->defined(),
               "bn_pool_train: an affine BatchNorm (weight and bias) is required");
   MHAQ_ON_DEVICE_OF(x);
+  if (act_dtype(x) != 0) {
+    // A 16-bit x.  x16, hip_forward_x16: the flags of the unpooled node (bn_train).  The pooled node, with x16 and pool_x16: where
+    // the 16-bit HIP forward applies (its statistics are that forward's) and the pool kernels' 32-bit pixel arithmetic holds.
+    // Anything else is the unpooled node under its own flags and the framework's pool: what ran before pool_x16 existed.
+    if (x16 && pool_x16 &&
+        bn_hip_forward_eligible(x, *w, *b, opt_tensor(running_mean), opt_tensor(running_var), /*x16=*/true) &&
+        x.numel() / x.size(1) < (1ll << 31)) {
+      need_lib();
+      return BatchNormPoolTrainFn::apply(x, *w, *b, running_mean, running_var, momentum, eps, cudnn_enabled,
+                                         /*hip_forward=*/false, /*pool_x16=*/true);
+    }
+    return at::max_pool2d(BatchNormTrainFn::apply(x, w, b, running_mean, running_var, momentum, eps, cudnn_enabled, x16,
+                                                  /*hip_forward=*/false, hip_forward_x16),
+                          {3, 3}, {2, 2}, {1, 1});
+  }
   // the HIP forward's eligibility is settled here, before either node runs: nothing a fallback needs is dropped later
   const bool hipf = hip_forward && bn_hip_forward_eligible(x, *w, *b, opt_tensor(running_mean), opt_tensor(running_var));
   // the fused node: fp32, with the 32-bit pixel arithmetic of its kernels (n * h * w < 2^31)
@@ -954,7 +1004,8 @@ Tensor bn_pool_train(const Tensor& x, const std::optional<Tensor>& w, const std:
                                                   /*x16=*/false, hipf, /*hip_forward_x16=*/false),
                           {3, 3}, {2, 2}, {1, 1});
   need_lib();
-  return BatchNormPoolTrainFn::apply(x, *w, *b, running_mean, running_var, momentum, eps, cudnn_enabled, hipf);
+  return BatchNormPoolTrainFn::apply(x, *w, *b, running_mean, running_var, momentum, eps, cudnn_enabled, hipf,
+                                     /*pool_x16=*/false);
 }
 
 // ------------------------------------------------------------------------------------------------ the frozen teacher
@@ -1818,9 +1869,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // ... with the stem's 3x3 / stride 2 max pool in the same node
   m.def("bn_pool_train", &bn_pool_train, py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("running_mean"),
         py::arg("running_var"), py::arg("momentum"), py::arg("eps"), py::arg("cudnn_enabled") = true,
-        py::arg("hip_forward") = false);
+        py::arg("hip_forward") = false, py::arg("x16") = false, py::arg("pool_x16") = false,
+        py::arg("hip_forward_x16") = false);
   m.def("bn_pool_hip_backwards", []() { return g_bn_pool_hip_backwards.load(); },
         "number of BatchNorm + pool backwards so far that ran mhaq_fq_bn_pool_bwd (the fallback is the two separate nodes)");
+  m.def("bn_pool_hip_forwards_x16", []() { return g_bn_pool_hip_forwards_x16.load(); },
+        "number of 16-bit BatchNorm + pool forwards so far that ran mhaq_fq_bn_fwd_x16 (statistics) and mhaq_fq_bn_norm_pool3s2_fwd_x16");
+  m.def("bn_pool_hip_backwards_x16", []() { return g_bn_pool_hip_backwards_x16.load(); },
+        "number of 16-bit BatchNorm + pool backwards so far that ran mhaq_fq_bn_pool_bwd_x16");
 
   // the frozen teacher's eval-mode BatchNorm with its ReLU, residual add and stem pool (no autograd)
   m.def("bn_infer_consts", &bn_infer_consts, py::arg("running_mean"), py::arg("running_var"), py::arg("weight"),

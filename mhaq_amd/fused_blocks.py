@@ -38,9 +38,11 @@ fused path is the same under DDP and SyncBatchNorm.
     the pool is exactly nn.MaxPool2d(3, 2, 1), both hook-free, BatchNorm and pool run as ONE node
     (HipBackwardBatchNorm2d.forward_pooled): the [N,64,112,112] BatchNorm output is not kept for the backward, no int64
     indices are written, and the BatchNorm backward gathers its dy from the pooled gradient instead of reading one the
-    pool's backward wrote.  Same bits in every output and gradient.  fp32 only: under autocast
-    takes_pooled_node() is false and the stem runs maxpool(bn(c)) in front of the fused quantizer (a 16-bit input is refused
-    up front, also where the BatchNorm's own 16-bit backward is enabled).
+    pool's backward wrote.  Same bits in every output and gradient.  fp32 by default: under autocast
+    takes_pooled_node() is false and the stem runs maxpool(bn(c)) in front of the fused quantizer, also where the BatchNorm's
+    own 16-bit backward is enabled -- unless bn_backward.install(x16=True, pool_x16=True) flagged the module, which makes
+    takes_pooled_node() true for a 16-bit input and sends it through the 16-bit pooled node (opt-in,
+    the stem's y and statistics become the HIP forward's).
 
 MHAQ_FUSE_BLOCKS=0 in the environment keeps QATTrainer from installing (A/B runs of an unchanged benchmark);
 QATConfig.fuse_blocks=False does the same per trainer.  MHAQ_STEM_POOL=0 / QATConfig.fuse_stem_pool=False keep only the

@@ -75,6 +75,12 @@ class QATConfig:
     # bf16 run change).  It has an effect only together with hip_bn_backward_16bit / MHAQ_BN_BACKWARD_X16 -- such a node has no
     # other backward --; alone it changes nothing.  Off by default; MHAQ_BN_FORWARD_X16=1 / 0 in the environment overrides it.
     hip_bn_forward_16bit: bool = False
+    # ... and the stem's BatchNorm and max pool as one node on the 16-bit tensors of an autocast step (bn_backward.py, "Pooled
+    # node, 16-bit": statistics from mhaq_fq_bn_fwd_x16, mhaq_fq_bn_norm_pool3s2_fwd_x16, mhaq_fq_bn_pool_bwd_x16; the stem's y and
+    # its saved and running statistics become the HIP forward's, so their bits change).  It has an effect only together with
+    # hip_bn_backward_16bit / MHAQ_BN_BACKWARD_X16, and where fuse_stem_pool lets the stem run a pooled node at all.  Off by
+    # default; MHAQ_STEM_POOL_X16=1 / 0 in the environment overrides it.
+    fuse_stem_pool_16bit: bool = False
     # the frozen teacher's BatchNorm, ReLU, residual add and stem pool in one HIP launch per place (frozen_blocks.py; fp32,
     # agrees with the stock eval modules to rounding, not bit for bit).  MHAQ_TEACHER_FUSED=0 in the environment switches it off.
     fuse_teacher: bool = True
@@ -246,7 +252,8 @@ class QATTrainer:
             if bn_backward.enabled_by_env():
                 bn_backward.install(net, x16=bn_backward.x16_enabled(cfg.hip_bn_backward_16bit),
                                     hip_forward=bn_backward.hip_forward_enabled(cfg.hip_bn_forward),
-                                    hip_forward_x16=bn_backward.hip_forward_x16_enabled(cfg.hip_bn_forward_16bit))
+                                    hip_forward_x16=bn_backward.hip_forward_x16_enabled(cfg.hip_bn_forward_16bit),
+                                    pool_x16=bn_backward.pool_x16_enabled(cfg.fuse_stem_pool_16bit))
         if cfg.fuse_teacher and cfg.distillation and layers is None and self.device.type == "cuda":
             from . import frozen_blocks
             if frozen_blocks.enabled_by_env():

@@ -12,7 +12,12 @@ writes it), TB/s is bytes / min.
 
 --lib adds builds of the same library (cache policies, rows in flight) as further rows; the product library is always first.
 --dtype bf16 / fp16 times the 16-bit forms on the same tensor in that type: torch's 16-bit pool, mhaq_fq_maxpool3s2_fwd_x16,
-mhaq_fq_bn_bwd_x16 on torch's 16-bit dy and mhaq_fq_bn_pool_bwd_x16 (profiles/r15_stem_pool16_micro.txt).
+mhaq_fq_bn_bwd_x16 on torch's 16-bit dy and mhaq_fq_bn_pool_bwd_x16 (profiles/r15_stem_pool16_micro.txt) -- and three rows for
+the stem's forward from the convolution's output (x is the rewritten tensor there): the framework's BatchNorm forward + torch's
+pool, mhaq_fq_bn_fwd_x16 + mhaq_fq_maxpool3s2_fwd_x16, and mhaq_fq_bn_fwd_x16 without a y + mhaq_fq_bn_norm_pool3s2_fwd_x16
+(profiles/r22_stem_pool16_micro.txt).
+--step [--steps K] [--warmup W]: not a kernel timing but tools/amp_bench.py's captured ResNet-18 batch-250 bf16 step in this
+process's configuration, for A/B runs of MHAQ_STEM_POOL_X16 (profiles/r22_stem_pool16_ab.txt).
 """
 import argparse
 import ctypes
@@ -41,7 +46,28 @@ def main():
     ap.add_argument("--lib", action="append", default=[], metavar="LABEL=PATH")
     ap.add_argument("--dtype", choices=["fp32", "bf16", "fp16"], default="fp32")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--step", action="store_true")
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
     args = ap.parse_args()
+    if args.step:
+        # tools/amp_bench.py's ResNet-18 batch-250 bf16 step, captured, in THIS process's configuration (MHAQ_BN_BACKWARD_X16 and
+        # MHAQ_STEM_POOL_X16 as the environment has them): one JSON line with the step, the pooled node's counters and the peak
+        # of allocated device memory over the process
+        import json
+        from tools import amp_bench                    # (seeds the private MIOpen database before MIOpen is first used)
+        from mhaq_amd import _ext, bn_backward
+        torch.backends.cudnn.benchmark = False
+        rec = {"tool": "stem_pool_bench", "device": torch.cuda.get_device_name(0), "bn_backward_x16": bn_backward.x16_enabled(),
+               "stem_pool_x16": bn_backward.pool_x16_enabled()}
+        rec["bf16_captured"] = amp_bench.step(torch.device("cuda:0"), True, True, args.steps, max(args.warmup, 4))
+        E = _ext.ext()
+        rec["pool_x16_forwards_recorded"] = E.bn_pool_hip_forwards_x16()
+        rec["pool_x16_backwards_recorded"] = E.bn_pool_hip_backwards_x16()
+        rec["x16_backwards_recorded"] = E.bn_hip_backwards_x16()
+        rec["peak_allocated_mb"] = round(torch.cuda.max_memory_allocated() / 1e6, 1)
+        print(json.dumps(rec), flush=True)
+        return
     dtype = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype]
     x16 = args.dtype != "fp32"
     dt = {"bf16": _lib.DT_BF16, "fp16": _lib.DT_F16}.get(args.dtype)
@@ -149,6 +175,52 @@ def main():
         8 * pel + es * pel + es * elems + 5 * es * elems)
     for label, L in libs:
         row(f"mhaq_fq_bn_pool_bwd{sfx}", label, timed(lambda: hip_bwd(L), rew_g), 2 * (es * elems + es * pel + pel) + es * elems)
+    if x16:
+        # the stem's forward from the convolution's output x: BatchNorm and pool as the bf16 step runs them (the framework's
+        # BatchNorm, torch's pool), as the two HIP entry points one after the other, and as the pooled node runs them
+        # (statistics without a y, then normalisation and pool in one launch); x is rewritten before every timed call
+        L0 = libs[0][1]
+        x0 = x.clone(memory_format=torch.preserve_format)
+        rew_x = lambda: x.copy_(x0)
+        beta = torch.randn(c, device=dev, generator=gen)
+        rm, rv = torch.zeros(c, device=dev), torch.ones(c, device=dev)
+        sm, si = torch.empty(c, device=dev), torch.empty(c, device=dev)
+        y = torch.empty_like(x)
+        nbf = L0.mhaq_fq_bn_fwd_x16_workspace_bytes(n * h * w, c)
+        wsf = torch.empty(nbf, dtype=torch.uint8, device=dev)
+
+        def stock_fwd():
+            out = torch.ops.aten._batch_norm_impl_index(x, gamma, beta, rm, rv, True, 0.1, 1e-5, True)
+            torch.ops.aten.max_pool2d_with_indices(out[0], k3, s2, p1, d1, False)
+
+        def stats(L, yp):
+            assert L.mhaq_fq_bn_fwd_x16(P(x), P(gamma), P(beta), yp, P(sm), P(si), P(rm), P(rv), 0.1, 1e-5, n * h * w, c, dt,
+                                        P(wsf), nbf, st) == 0
+
+        def hip_two(L):
+            stats(L, P(y))
+            assert L.mhaq_fq_maxpool3s2_fwd_x16(P(y), P(p), P(code), n, h, w, c, dt, st) == 0
+
+        def hip_fused(L):
+            stats(L, None)
+            assert L.mhaq_fq_bn_norm_pool3s2_fwd_x16(P(x), P(sm), P(si), P(gamma), P(beta), P(p), P(code), n, h, w, c, dt,
+                                                     st) == 0
+
+        hip_two(L0)
+        ref = (p.clone(), code.clone())
+        p.zero_()
+        code.zero_()
+        hip_fused(L0)
+        assert torch.equal(bits(ref[0]), bits(p)) and torch.equal(ref[1], code), "pooled forward differs from the two launches"
+        del ref
+        row("framework BatchNorm fwd + torch pool", "torch", timed(stock_fwd, rew_x),
+            3 * es * elems + es * elems + es * pel + 8 * pel)
+        for label, L in libs:
+            row("bn_fwd_x16 + maxpool3s2_fwd_x16", label, timed(lambda: hip_two(L), rew_x),
+                3 * es * elems + es * elems + es * pel + pel)
+        for label, L in libs:
+            row("bn_fwd_x16(y=NULL) + bn_norm_pool3s2", label, timed(lambda: hip_fused(L), rew_x),
+                2 * es * elems + es * pel + pel)
     head = (f"Stem pool and BatchNorm backward stand-alone, {tuple(args.shape)} {args.dtype} channels_last ({elems / 1e6:.1f} M elements), one "
             f"{torch.cuda.get_device_name(0)}.\nBefore every timed call a 1 GiB buffer is written and the producer's tensor (t for the "
             f"forward, the pooled gradient for the backward;\nnothing for the line that times mhaq_fq_bn_bwd alone: its dy stays as the "
