@@ -224,7 +224,7 @@ int mhaq_fq_act_bwd_finalize_multi(const mhaq_act_finalize_desc* descs_device, i
  * of _bwd_partials_x16 have the layout of mhaq_fq_act_bwd_partials: mhaq_fq_act_bwd_finalize_multi reduces 16-bit and
  * fp32 quantizers in the same launch.
  * ---------------------------------------------------------------------- */
-enum { MHAQ_FQ_DT_BF16 = 1, MHAQ_FQ_DT_F16 = 2 };
+enum { MHAQ_FQ_DT_F32 = 0 /* only where an entry point says so */, MHAQ_FQ_DT_BF16 = 1, MHAQ_FQ_DT_F16 = 2 };
 int mhaq_fq_act_fwd_x16(const void* x, void* y, int64_t n, int dtype,
                         const float* log_act_s, const float* log_act_q, const float* act_b,
                         float* params_out /* [5] */, float* qstats, int32_t* flags,
@@ -576,6 +576,44 @@ typedef struct {
 int64_t mhaq_fq_radam_chunk_elements(void);
 int mhaq_fq_radam_step(const mhaq_radam_desc* descs_device, int ntensors, const mhaq_radam_work* work_device,
                        int64_t nwork, float w1, float beta2, float w2, float eps, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Distillation losses over two logit tensors: the six softmax-family losses a config can name (Cross-Entropy, Symmetrical
+ * Cross-Entropy, KL, Symmetrical KL, JSD, Hellinger) in two launches forward and one backward.  Additive to ABI v4 --
+ * MHAQ_FQ_ABI_VERSION stays 4; a caller discovers these entry points by symbol.
+ *   x, t          the student's and the teacher's logits, dense row-major [rows][cols]; each of them MHAQ_FQ_DT_F32,
+ *                 MHAQ_FQ_DT_BF16 or MHAQ_FQ_DT_F16 (x_dtype, t_dtype; the two may differ), aligned to its element size.
+ *                 16-bit elements are converted up exactly; everything else is fp32 arithmetic, reduced in fp64.
+ *   kind          MHAQ_FQ_DISTILL_*
+ *   loss          [1] fp32: sum of the terms below over all elements / denom, summed in fp64 and rounded once
+ *   gunit         NULL, or [rows][cols] fp32: d loss / d x for an upstream gradient of 1
+ *   workspace     mhaq_fq_distill_loss_workspace_bytes(rows) bytes, 8-byte aligned: one fp64 partial per row
+ * With ps, pt = softmax(x), softmax(t) per row (row maximum subtracted), ls, lt the log-softmaxes, d = ls - lt,
+ * B = rows, N = rows * cols and r_j = denom * gunit_j:
+ *   CE         term -pt * ls             denom B    r_j = ps_j - pt_j
+ *   SCE        term -pt * ls - ps * lt   denom B    r_j = ps_j - pt_j - ps_j * (lt_j - M),  M = sum_c ps_c * lt_c
+ *   KL         term pt * (lt - ls)       denom N    r_j = ps_j - pt_j
+ *   SKL        term (ps - pt) * d        denom B    r_j = ps_j - pt_j + ps_j * (d_j - K),   K = sum_c ps_c * d_c
+ *   JSD        term (ps - pt) * d        denom 2N   r_j as SKL
+ *   HELLINGER  term (sqrt ps - sqrt pt)^2  denom N  r_j = h_j - ps_j * H,  h = sqrt ps * (sqrt ps - sqrt pt),  H = sum_c h_c
+ * A NaN or infinite logit makes its own row's partial and gunit row NaN (and so the loss) and leaves other rows' gunit
+ * alone.  The same inputs give the same bits at every call: no atomics, fixed summation orders.
+ * _fwd: launch one, one workgroup per row (rows of up to 4096 columns are held in registers, longer ones are walked
+ * once per pass); launch two, one workgroup, sums the row partials.  _bwd: gx[i] = gunit[i] * g[0], rounded to nearest-
+ * even once into gx_dtype (fp32, bf16 or fp16); g is read on the device, so a replayed hipGraph sees the current value.
+ * Argument errors are returned before any launch: NULL x / t / loss / workspace (gunit / g / gx), rows, cols or n <= 0,
+ * an unknown kind or dtype (MHAQ_FQ_EINVAL); a short workspace (MHAQ_FQ_EWORKSPACE); a pointer not aligned to its
+ * element size (MHAQ_FQ_EALIGN); rows > 2^31 - 1 (MHAQ_FQ_EUNSUPPORTED).  Stream-ordered, no host synchronisation, stateless.
+ * ---------------------------------------------------------------------- */
+enum { MHAQ_FQ_DISTILL_CE = 0, MHAQ_FQ_DISTILL_SCE = 1, MHAQ_FQ_DISTILL_KL = 2,
+       MHAQ_FQ_DISTILL_SKL = 3, MHAQ_FQ_DISTILL_JSD = 4, MHAQ_FQ_DISTILL_HELLINGER = 5 };
+size_t mhaq_fq_distill_loss_workspace_bytes(int64_t rows);
+int mhaq_fq_distill_loss_fwd(const void* x, int x_dtype, const void* t, int t_dtype,
+                             int64_t rows, int64_t cols, int kind,
+                             float* loss /* [1] */, float* gunit /* [rows*cols], nullable */,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int mhaq_fq_distill_loss_bwd(const float* gunit, const float* g /* [1], device */,
+                             void* gx, int gx_dtype, int64_t n, void* stream);
 
 /* Whole-tensor min / max (zero point of a PER_TENSOR weight quantizer,
  * gdnsq_conv2d.py:82-83; min/max observer, calib/minmaxobserver.py:19-36).

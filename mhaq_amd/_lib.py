@@ -20,7 +20,8 @@ _u64 = C.c_uint64
 _sz = C.c_size_t
 _int = C.c_int
 
-# element types of the 16-bit entry points (include/mhaq_fq.h)
+# element types of the 16-bit entry points (include/mhaq_fq.h); DT_F32 only where an entry point takes it
+DT_F32 = 0
 DT_BF16 = 1
 DT_F16 = 2
 
@@ -85,6 +86,11 @@ SIGNATURES = {
     # one-pass RAdam over a descriptor table and a (tensor, chunk) work list (additive, ABI v4 kept)
     "mhaq_fq_radam_chunk_elements": (_i64, []),
     "mhaq_fq_radam_step": (_int, [_p, _int, _p, _i64, C.c_float, C.c_float, C.c_float, C.c_float, _p]),
+    # the six softmax-family distillation losses: x, x_dtype, t, t_dtype, rows, cols, kind, loss, gunit, workspace (additive,
+    # ABI v4 kept)
+    "mhaq_fq_distill_loss_workspace_bytes": (_sz, [_i64]),
+    "mhaq_fq_distill_loss_fwd": (_int, [_p, _int, _p, _int, _i64, _i64, _int, _p, _p, _p, _sz, _p]),
+    "mhaq_fq_distill_loss_bwd": (_int, [_p, _p, _p, _int, _i64, _p]),
     "mhaq_fq_minmax_workspace_bytes": (_sz, [_i64]),
     "mhaq_fq_minmax": (_int, [_p, _i64, _p, _p, _sz, _p]),
     "mhaq_fq_row_minmax": (_int, [_p, _i64, _i64, _p, _p, _p]),

@@ -62,7 +62,8 @@ namespace {
   X(mhaq_fq_bn_pool_bwd_x16_workspace_bytes) X(mhaq_fq_bn_pool_bwd_x16) X(mhaq_fq_bn_norm_pool3s2_fwd_x16)          \
   X(mhaq_fq_bn_infer_consts) X(mhaq_fq_bn_infer_act) X(mhaq_fq_bn_relu_pool3s2)                                     \
   X(mhaq_fq_bn_infer_act_x16) X(mhaq_fq_bn_relu_pool3s2_x16)                                                        \
-  X(mhaq_fq_radam_chunk_elements) X(mhaq_fq_radam_step)
+  X(mhaq_fq_radam_chunk_elements) X(mhaq_fq_radam_step)                                                          \
+  X(mhaq_fq_distill_loss_workspace_bytes) X(mhaq_fq_distill_loss_fwd) X(mhaq_fq_distill_loss_bwd)
 
 struct Api {
 #define X(n) decltype(&::n) n = nullptr;
@@ -1771,6 +1772,62 @@ void radam_step(const std::vector<Tensor>& params, const std::vector<Tensor>& gr
   g_fused_radam_steps.fetch_add(1, std::memory_order_relaxed);
 }
 
+// ------------------------------------------------------------------------------------------------ distillation loss
+// One of the six softmax-family distillation losses (mhaq_amd/loss.py: FusedDistillLoss) over the student's and the teacher's
+// logits: mhaq_fq_distill_loss_fwd -- two launches -- forward, mhaq_fq_distill_loss_bwd -- one -- backward.  The workspace and
+// gunit (d loss / d x for an upstream gradient of 1) come from the caching allocator; gunit only where x takes a gradient.
+std::atomic<int64_t> g_distill_fused_launches{0};   // kernel launches of the two entry points so far: 2 forward, 1 backward
+
+inline int distill_dtype(const Tensor& x) { return x.scalar_type() == at::kFloat ? MHAQ_FQ_DT_F32 : act_dtype(x); }
+
+class DistillLossFn : public torch::autograd::Function<DistillLossFn> {
+ public:
+  static Tensor forward(AutogradContext* ctx, const Tensor& x, const Tensor& t, int64_t kind, bool need_grad) {
+    const int64_t rows = x.size(0), cols = x.size(1);
+    Tensor loss = at::empty({}, x.options().dtype(at::kFloat));
+    Tensor ws = at::empty({(int64_t)A.mhaq_fq_distill_loss_workspace_bytes(rows)}, x.options().dtype(at::kByte));
+    Tensor gunit;
+    if (need_grad) gunit = at::empty({rows, cols}, x.options().dtype(at::kFloat));
+    check(A.mhaq_fq_distill_loss_fwd(x.const_data_ptr(), distill_dtype(x), t.const_data_ptr(), distill_dtype(t), rows, cols,
+                                     (int)kind, fptr_mut(loss), need_grad ? fptr_mut(gunit) : nullptr, ws.mutable_data_ptr(),
+                                     (size_t)ws.numel(), cur_stream(x)),
+          "mhaq_fq_distill_loss_fwd");
+    g_distill_fused_launches.fetch_add(2, std::memory_order_relaxed);
+    if (need_grad) ctx->save_for_backward({gunit});
+    ctx->saved_data["dtype"] = (int64_t)distill_dtype(x);
+    return loss;
+  }
+
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    auto saved = ctx->get_saved_variables();
+    TORCH_CHECK(!saved.empty(), "distill_loss: the forward ran without a gradient to keep");
+    const Tensor& gunit = saved[0];
+    Tensor g = grads[0].reshape({1}).to(at::kFloat).contiguous();
+    const int dt = (int)ctx->saved_data["dtype"].toInt();
+    Tensor gx = at::empty(gunit.sizes(), gunit.options().dtype(dt == MHAQ_FQ_DT_F32    ? at::kFloat
+                                                               : dt == MHAQ_FQ_DT_BF16 ? at::kBFloat16
+                                                                                       : at::kHalf));
+    check(A.mhaq_fq_distill_loss_bwd(fptr(gunit), fptr(g), gx.mutable_data_ptr(), dt, gunit.numel(), cur_stream(gunit)),
+          "mhaq_fq_distill_loss_bwd");
+    g_distill_fused_launches.fetch_add(1, std::memory_order_relaxed);
+    return {gx, Tensor(), Tensor(), Tensor()};
+  }
+};
+
+Tensor distill_loss(const Tensor& x, const Tensor& t, int64_t kind) {
+  need_lib();
+  if (!x.is_cuda() || !t.is_cuda()) throw MhaqError("distill_loss: device tensors are required (there is no CPU path)");
+  MHAQ_ON_DEVICE_OF(x);
+  for (const Tensor* p : {&x, &t})
+    TORCH_CHECK(p->dim() == 2 && p->is_contiguous() && p->device() == x.device() &&
+                    (p->scalar_type() == at::kFloat || act_dtype(*p) != 0),
+                "distill_loss: input and target must be contiguous [rows, cols] float32, bfloat16 or float16 tensors on one device");
+  TORCH_CHECK(x.sizes() == t.sizes() && x.numel() > 0, "distill_loss: input and target must have one non-empty shape");
+  TORCH_CHECK(!(t.requires_grad() && at::GradMode::is_enabled()),
+              "distill_loss: the target (the teacher's logits) takes no gradient; detach it");
+  return DistillLossFn::apply(x, t, kind, x.requires_grad() && at::GradMode::is_enabled());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1932,6 +1989,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("radam_step", &radam_step, py::arg("params"), py::arg("grads"), py::arg("exp_avgs"), py::arg("exp_avg_sqs"),
         py::arg("c1s"), py::arg("c2s"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
         "one launch of mhaq_fq_radam_step over the listed tensors (mhaq_amd/optim.py)");
+  m.def("distill_loss", &distill_loss, py::arg("input"), py::arg("target"), py::arg("kind"));
+  m.def("distill_fused_launches", []() { return g_distill_fused_launches.load(); },
+        "kernel launches of mhaq_fq_distill_loss_fwd (2) / _bwd (1) so far in this process");
   m.def("fused_radam_steps", []() { return g_fused_radam_steps.load(); },
         "launches of mhaq_fq_radam_step so far (tests: the optimizer step took the HIP kernel)");
 }

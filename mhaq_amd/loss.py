@@ -5,10 +5,15 @@
   FusedPotentialLossNoPred  same with a precomputed base loss (gdnsq_loss.py:88-168)
                             -- both with the hinge arithmetic in the HIP library (mhaq_fq_potential_loss_fwd / _bwd)
   SymmetricalKL             distillation loss of the ResNet-18 configs (src/aux/loss/symm_kl_loss.py)
+  FusedDistillLoss          the six softmax-family distillation losses of src/aux/loss in the HIP library
+                            (mhaq_fq_distill_loss_fwd / _bwd: 2 + 1 launches)
+  distillation_criterion    a config's `distillation_loss` string -> module (gdnsq_quant.py: get_loss)
 
 (The torch restatement of the two PotentialLoss modules is checker code and lives in oracle/loss.py.)
 """
 from __future__ import annotations
+
+import os
 
 import torch
 import torch.nn.functional as F
@@ -96,3 +101,87 @@ class SymmetricalKL(nn.Module):
         y = F.log_softmax(target, dim=1)
         return (F.kl_div(x, y, log_target=True, reduction="batchmean")
                 + F.kl_div(y, x, log_target=True, reduction="batchmean"))
+
+
+# ----------------------------------------------------------------------------- fused distillation losses
+# the reference's config strings (gdnsq_quant.py: get_loss) of the six softmax-family losses -> MHAQ_FQ_DISTILL_*
+DISTILL_KINDS = {
+    "Cross-Entropy": 0,
+    "Symmetrical Cross-Entropy": 1,
+    "KL": 2,
+    "Symmetrical KL": 3,
+    "JSD": 4,
+    "Hellinger": 5,
+}
+ENV_SWITCH_DISTILL = "MHAQ_DISTILL_FUSED"
+
+
+def distill_fused_enabled(configured: bool = False) -> bool:
+    """The trainer's switch: `configured` (QATConfig.fused_distill_loss) unless MHAQ_DISTILL_FUSED is set, which then
+    decides: "1" / "true" / "on" / "yes" enable the fused loss, anything else disables it."""
+    v = os.environ.get(ENV_SWITCH_DISTILL)
+    if v is None or not v.strip():
+        return bool(configured)
+    return v.strip().lower() in ("1", "true", "on", "yes")
+
+
+def distill_fused_launches() -> int:
+    """Kernel launches of mhaq_fq_distill_loss_fwd (two per call) and _bwd (one) so far in this process."""
+    from . import _ext
+    return int(_ext.ext().distill_fused_launches())
+
+
+class FusedDistillLoss(nn.Module):
+    """One of the six softmax-family distillation losses of the reference (src/aux/loss: distill_ce.py, symm_ce_loss.py,
+    kl_loss.py, symm_kl_loss.py, jsdloss.py, hellinger.py) in the HIP library: two launches forward
+    (mhaq_fq_distill_loss_fwd: one workgroup per row of logits, then a one-workgroup sum), one backward
+    (mhaq_fq_distill_loss_bwd), where the framework runs log_softmax / kl_div / sum chains and their autograd mirror.
+
+    `kind` is a config string of DISTILL_KINDS or its MHAQ_FQ_DISTILL_* number.  forward(input, target) takes device
+    tensors of one shape, float32, bfloat16 or float16 each (the two may differ), [rows, C] or any shape seen as [-1, C]
+    over its last dimension, and returns a 0-dim float32 loss; the gradient goes to `input` alone, in its dtype.  There
+    is no CPU arithmetic: a CPU tensor raises MhaqFqError."""
+
+    def __init__(self, kind):
+        super().__init__()
+        if isinstance(kind, str):
+            if kind not in DISTILL_KINDS:
+                raise NotImplementedError(f"FusedDistillLoss: unknown loss {kind!r}; valid: {sorted(DISTILL_KINDS)}")
+            self.name, self.kind = kind, DISTILL_KINDS[kind]
+        else:
+            names = {v: k for k, v in DISTILL_KINDS.items()}
+            if int(kind) not in names:
+                raise NotImplementedError(f"FusedDistillLoss: unknown kind {kind!r}")
+            self.name, self.kind = names[int(kind)], int(kind)
+
+    def extra_repr(self):
+        return repr(self.name)
+
+    def forward(self, input, target):
+        from . import _ext
+        from ._lib import MhaqFqError
+        if not (input.is_cuda and target.is_cuda):
+            raise MhaqFqError("FusedDistillLoss runs only as HIP kernels: input and target must be device tensors "
+                              "(no CPU fallback by design)")
+        if input.shape != target.shape or input.dim() < 1:
+            raise ValueError(f"FusedDistillLoss: input {tuple(input.shape)} and target {tuple(target.shape)} must have "
+                             "one shape of at least one dimension")
+        c = input.shape[-1]
+        return _ext.ext().distill_loss(input.reshape(-1, c).contiguous(), target.detach().reshape(-1, c).contiguous(),
+                                       self.kind)
+
+
+def distillation_criterion(name: str, fused: bool = False) -> nn.Module:
+    """The distillation loss a config names (`distillation_loss`; gdnsq_quant.py: get_loss).  "L1" and "L2" are the
+    framework's modules.  "Symmetrical KL" is the framework chain SymmetricalKL() -- what QATTrainer always used --
+    unless `fused`; the five other softmax-family names have no earlier behaviour here and are always FusedDistillLoss."""
+    if name == "L1":
+        return nn.L1Loss()
+    if name == "L2":
+        return nn.MSELoss()
+    if name == "Symmetrical KL" and not fused:
+        return SymmetricalKL()
+    if name in DISTILL_KINDS:
+        return FusedDistillLoss(name)
+    raise NotImplementedError(f"distillation_loss {name!r} is invalid; valid options are: "
+                              f"{['L1', 'L2'] + list(DISTILL_KINDS)}")

@@ -26,7 +26,7 @@ from torch import nn
 from . import ops
 from ._lib import MhaqFqError
 from .enums import QNMethod, QScheme
-from .loss import FusedPotentialLoss, FusedPotentialLossNoPred, SymmetricalKL
+from .loss import FusedPotentialLoss, FusedPotentialLossNoPred, distill_fused_enabled, distillation_criterion
 from .wrap import get_model_values, quantize_model
 
 
@@ -92,6 +92,14 @@ class QATConfig:
     # trainer builds the optimizer itself, on a GPU; an optimizer_factory is never replaced.  MHAQ_FUSED_RADAM=1 / 0 in the
     # environment overrides it.
     fused_optimizer: bool = True
+    # the distillation loss, by the reference's config string (`distillation_loss`, gdnsq_quant.py: get_loss): "Cross-Entropy",
+    # "Symmetrical Cross-Entropy", "L1", "L2", "KL", "Hellinger", "Symmetrical KL" or "JSD" (loss.distillation_criterion).
+    distillation_loss: str = "Symmetrical KL"
+    # "Symmetrical KL" as loss.FusedDistillLoss -- 2 + 1 HIP launches instead of the framework's log_softmax / kl_div chain --
+    # where the trainer builds the HIP-backed loss itself, on a GPU.  Off by default: the loss and its gradient are then the
+    # same quantity through other roundings, not the framework's bits.  MHAQ_DISTILL_FUSED=1 / 0 in the environment
+    # overrides it.  (The five other softmax-family names are FusedDistillLoss either way.)
+    fused_distill_loss: bool = False
     criterion: nn.Module = field(default_factory=nn.CrossEntropyLoss)
     # mixed precision (the reference trainer's `precision = "bf16-mixed"`, training/trainer.py:126): torch.bfloat16 runs
     # the teacher and student forwards, the loss and validate_step's forward under torch.autocast; the activation
@@ -331,8 +339,12 @@ class QATTrainer:
                 raise MhaqFqError("QATTrainer on a CPU device needs loss_classes (and layers): the fake-quant path and "
                                   "its PotentialLoss run only as HIP kernels (no CPU fallback by design)")
             loss_classes = (FusedPotentialLoss, FusedPotentialLossNoPred)
+            fused_distill = distill_fused_enabled(cfg.fused_distill_loss)
+        else:
+            fused_distill = False       # a caller's loss classes keep the framework's Symmetrical KL
         if cfg.distillation:
-            self.loss = loss_classes[0](SymmetricalKL(), p=1, a=cfg.act_bit, w=cfg.weight_bit)
+            self.loss = loss_classes[0](distillation_criterion(cfg.distillation_loss, fused_distill), p=1,
+                                        a=cfg.act_bit, w=cfg.weight_bit)
         else:
             self.loss = loss_classes[1](cfg.criterion, p=1, a=cfg.act_bit, w=cfg.weight_bit)
         # hipGraph option (single GPU): after three eager steps the device work of a step up to the gradients --
