@@ -615,6 +615,48 @@ int mhaq_fq_distill_loss_fwd(const void* x, int x_dtype, const void* t, int t_dt
 int mhaq_fq_distill_loss_bwd(const float* gunit, const float* g /* [1], device */,
                              void* gx, int gx_dtype, int64_t n, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Super-resolution validation metrics: per-image PSNR and SSIM of the clamped prediction against the target and the L1
+ * criterion on the unclamped one, in three launches.  Additive to ABI v4 -- MHAQ_FQ_ABI_VERSION stays 4; a caller discovers
+ * these entry points by symbol.
+ *   sr, hr        the model output s and the target h, dense NCHW [n][c][h][w]; each of them MHAQ_FQ_DT_F32, MHAQ_FQ_DT_BF16
+ *                 or MHAQ_FQ_DT_F16 (the two may differ), aligned to its element size.  16-bit elements are converted up
+ *                 exactly; everything else is fp32 arithmetic (no contraction), reduced in fp64.
+ *   sr_div        s' = s / sr_div, an IEEE division (255 for a de-normalised model, else 1); finite and non-zero
+ *   to_luminance  non-zero (c must be 3): ONE plane per image, x = (s''_R * k0 + s''_G * k1) + s''_B * k2 and y the same
+ *                 from h, k = fp32([65.738, 129.057, 25.064]) / 256.  Zero: the c channels are the P = c planes.
+ *   pool          the SSIM pool factor f >= 1; the reference's value is max(1, round(min(h, w) / 256)), halves to even
+ *   psnr, ssim    [n] fp32;  l1 [1];  mean [2] = the batch means of PSNR and SSIM;  each summed in fp64 and rounded once
+ *   flags         [1] device word, OR-ed into (the caller clears it): bit 0 = a NaN or an infinity in s' or h, bit 1 = a
+ *                 target plane value outside [0, 1] (where a metrics library would refuse the input)
+ *   workspace     mhaq_fq_sr_metrics_workspace_bytes(...) bytes, 8-byte aligned: the pooled planes xp, yp as fp32
+ *                 [n][P][hp][wp] (hp = floor(h / f), wp = floor(w / f)) and the fp64 partials of the launches
+ * Definitions.  l1 = mean |s' - h| over all elements, unclamped.  s'' = clamp(s', 0, 1) where a NaN stays a NaN; h is not
+ * clamped.  PSNR of an image = -10 * log10(mean over its P * h * w plane values of (x - y)^2 + 1e-8): every pixel counts,
+ * also the remainder rows and columns the pool drops.  SSIM of an image: the planes are average-pooled with kernel and
+ * stride f in floor mode (f == 1: the planes themselves); G = the 11 x 11 Gaussian window, sigma 1.5, normalised to sum
+ * 1, applied without padding; mx, my = G * x, G * y; sxx = G * x^2 - mx^2, syy likewise, sxy = G * (x y) - mx my;
+ * c1 = 1e-4, c2 = 9e-4; cs = (2 sxy + c2) / (sxx + syy + c2); ss = (2 mx my + c1) / (mx^2 + my^2 + c1) * cs; SSIM = the
+ * mean of ss over the (hp - 10) * (wp - 10) window positions and the planes.  x^2, y^2, x y and their filtered sums are
+ * formed by the same operations in the same order, so s'' and h with equal bits give SSIM == 1.0f exactly.
+ * A NaN in one image makes that image's PSNR and / or SSIM NaN (and l1 and the batch means) by plain IEEE arithmetic; the
+ * other images' outputs keep their bits.  The same inputs give the same bits at every call: no atomics, fixed orders.
+ * Launches: prepare (one read of s and h: the division, the |s' - h| and (x - y)^2 partials, the clamp, the planes, the
+ * flags, the pooled planes), SSIM tiles (32 x 32 window positions of one plane per workgroup, separable filter in LDS, one
+ * fp64 partial per workgroup), finalize (one workgroup).
+ * Argument errors are returned before any launch, in this order: a NULL pointer; an unknown dtype; n, c, h, w <= 0,
+ * pool < 1, sr_div not finite or zero; to_luminance with c != 3 (all MHAQ_FQ_EINVAL); a short workspace
+ * (MHAQ_FQ_EWORKSPACE); sr / hr not aligned to their element size, an output or the workspace not 8-byte aligned
+ * (MHAQ_FQ_EALIGN); floor(h / pool) < 11 or floor(w / pool) < 11 (no window fits), c not in {1, 3}, more partials than a
+ * grid dimension allows (MHAQ_FQ_EUNSUPPORTED; _workspace_bytes returns 0 for every size the call refuses).
+ * Stream-ordered, capture-safe, no host synchronisation, stateless.
+ * ---------------------------------------------------------------------- */
+size_t mhaq_fq_sr_metrics_workspace_bytes(int64_t n, int64_t c, int64_t h, int64_t w, int to_luminance, int pool);
+int mhaq_fq_sr_metrics(const void* sr, int sr_dtype, const void* hr, int hr_dtype,
+                       int64_t n, int64_t c, int64_t h, int64_t w, float sr_div, int to_luminance, int pool,
+                       float* psnr /* [n] */, float* ssim /* [n] */, float* l1 /* [1] */, float* mean /* [2] */,
+                       uint32_t* flags /* [1] */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Whole-tensor min / max (zero point of a PER_TENSOR weight quantizer,
  * gdnsq_conv2d.py:82-83; min/max observer, calib/minmaxobserver.py:19-36).
  * out[0] = min, out[1] = max. */

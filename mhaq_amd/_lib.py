@@ -91,6 +91,11 @@ SIGNATURES = {
     "mhaq_fq_distill_loss_workspace_bytes": (_sz, [_i64]),
     "mhaq_fq_distill_loss_fwd": (_int, [_p, _int, _p, _int, _i64, _i64, _int, _p, _p, _p, _sz, _p]),
     "mhaq_fq_distill_loss_bwd": (_int, [_p, _p, _p, _int, _i64, _p]),
+    # super-resolution validation metrics: sr, sr_dtype, hr, hr_dtype, n, c, h, w, sr_div, to_luminance, pool, psnr, ssim,
+    # l1, mean, flags, workspace (additive, ABI v4 kept)
+    "mhaq_fq_sr_metrics_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _int, _int]),
+    "mhaq_fq_sr_metrics": (_int, [_p, _int, _p, _int, _i64, _i64, _i64, _i64, C.c_float, _int, _int, _p, _p, _p, _p, _p,
+                                  _p, _sz, _p]),
     "mhaq_fq_minmax_workspace_bytes": (_sz, [_i64]),
     "mhaq_fq_minmax": (_int, [_p, _i64, _p, _p, _sz, _p]),
     "mhaq_fq_row_minmax": (_int, [_p, _i64, _i64, _p, _p, _p]),

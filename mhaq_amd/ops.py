@@ -927,3 +927,39 @@ def potential_loss(base, las, laq, lws, lwq, state, a_bits, w_bits, p=1, lossles
         raise ValueError("potential_loss: scale and range vectors must pair up")
     return _ext().potential_loss(*vecs, state, float(a_bits), float(w_bits), float(p), bool(lossless),
                                  bool(update_state))
+
+
+# ------------------------------------------------------------------ SR validation metrics (cold: no gradient, plain ctypes)
+_SR_DT = {torch.float32: _lib.DT_F32, torch.bfloat16: _lib.DT_BF16, torch.float16: _lib.DT_F16}
+
+
+@_on_device
+def sr_metrics(sr, hr, sr_div, to_luminance, pool):
+    """mhaq_fq_sr_metrics on two dense [N, C, H, W] device tensors (float32 / bfloat16 / float16 each): three launches, no host
+    synchronisation.  Returns (psnr[N], ssim[N], l1[1], mean[2], flags[1] int32); outputs and workspace come from the
+    caching allocator.  sr_metrics.py is the public face."""
+    for t, name in ((sr, "sr"), (hr, "hr")):
+        if not t.is_cuda:
+            raise _lib.MhaqFqError(f"{name} is on {t.device}: the SR metrics run only as HIP kernels on an MI355X "
+                                   "(no CPU fallback by design)")
+        if t.dtype not in _SR_DT:
+            raise TypeError(f"{name} must be float32, bfloat16 or float16, got {t.dtype}")
+        if t.dim() != 4 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous [N, C, H, W] tensor")
+    if sr.shape != hr.shape or sr.device != hr.device:
+        raise ValueError(f"sr {tuple(sr.shape)} on {sr.device} and hr {tuple(hr.shape)} on {hr.device} do not match")
+    n, c, h, w = sr.shape
+    L = _lib.lib()
+    lum = int(bool(to_luminance))
+    nb = L.mhaq_fq_sr_metrics_workspace_bytes(n, c, h, w, lum, int(pool))
+    ws = _workspace(max(nb, 8), sr.device)
+    npad = (n + 1) & ~1                                     # every output 8-byte aligned
+    out = torch.empty(2 * npad + 4, dtype=torch.float32, device=sr.device)
+    flags = torch.zeros(2, dtype=torch.int32, device=sr.device)
+    psnr, ssim = out[:n], out[npad:npad + n]
+    l1, mean = out[2 * npad:2 * npad + 1], out[2 * npad + 2:2 * npad + 4]
+    _lib.check(L.mhaq_fq_sr_metrics(sr.data_ptr(), _SR_DT[sr.dtype], hr.data_ptr(), _SR_DT[hr.dtype], n, c, h, w,
+                                    float(sr_div), lum, int(pool), psnr.data_ptr(), ssim.data_ptr(), l1.data_ptr(),
+                                    mean.data_ptr(), flags.data_ptr(), ws.data_ptr(), nb, _stream()),
+               "mhaq_fq_sr_metrics")
+    return psnr, ssim, l1, mean, flags[:1]

@@ -106,6 +106,13 @@ class QATConfig:
     # quantizers then take the 16-bit kernels (mhaq_fq_act_*_x16), weights and quantizer parameters stay float32.
     # None = float32 throughout.  torch.float16 would need loss scaling and is refused.
     autocast_dtype: Optional[torch.dtype] = None
+    # what validate_step records: "cls" = the classification record (val_loss, top1, ...), "sr" = the super-resolution record of
+    # the reference's LVisionSR.validation_step (PSNR, SSIM and the criterion, sr_metrics.py: three HIP launches).  For "sr":
+    # sr_to_luminance = the config's `to_luminance` (PSNR / SSIM on the luminance plane), sr_denormalize = its `denormalize`
+    # (the model sees x * 255 and its output is divided by 255, LVisionSR.forward).
+    task: str = "cls"
+    sr_to_luminance: bool = True
+    sr_denormalize: bool = False
 
 
 # ----------------------------------------------------------------------------- calibration
@@ -236,6 +243,11 @@ class QATTrainer:
         (mhaq_amd/loss.py).  A CPU trainer is checker territory (tests, bench.py's cpu_baseline): it must bring its
         layers AND its loss (oracle/ref_layers.py, oracle/loss.py) -- the product has no CPU arithmetic."""
         self.cfg, self.device = cfg, torch.device(device)
+        if cfg.task not in ("cls", "sr"):
+            raise ValueError(f"QATConfig.task: {cfg.task!r} is not supported (\"cls\" or \"sr\")")
+        if cfg.task == "sr" and self.device.type != "cuda":
+            raise MhaqFqError("QATConfig.task = \"sr\" on a CPU device: the validation metrics run only as HIP kernels "
+                              "(no CPU fallback by design)")
         if cfg.autocast_dtype is not None and cfg.autocast_dtype != torch.bfloat16:
             raise ValueError(f"QATConfig.autocast_dtype: {cfg.autocast_dtype} is not supported (None or torch.bfloat16; "
                              "float16 training needs loss scaling, which this trainer does not do)")
@@ -671,16 +683,47 @@ class QATTrainer:
         their integrity flags (gdnsq.py:211-217), checked here with ONE host sync for the whole model."""
         from . import stats
         from .gdnsq import check_model_integrity
+        sr = self.cfg.task == "sr"
         self.module.eval()
         try:
             with self._autocast():
-                out = self.net(x)
+                out = self.net(x * 255 if sr and self.cfg.sr_denormalize else x)
+            if sr:                       # enqueued ahead of the integrity check's host sync: the step keeps its one sync
+                head = self._sr_record_head(out, y)
             out = out.float()            # the statistics below in float32, as without autocast
             check_model_integrity(self.net)
         finally:
             self.module.train()
         with stats.memoised():          # one HIP sweep per weight layer for the six statistics + is_converged
+            if sr:
+                return {**head, **self._bit_width_record(stats)}
             return self._validation_record(out, y, stats)
+
+    def _sr_record_head(self, out, y):
+        """LVisionSR.validation_step (vision_sr_module.py:151-167): the criterion on the scaled, unclamped prediction, PSNR and
+        SSIM of the clamped one (on the luminance planes with sr_to_luminance) -- sr_metrics.py, three launches, no host
+        sync.  `metric_flags` is the device word check_sr_flags reads."""
+        from .sr_metrics import sr_metrics
+        div = 255.0 if self.cfg.sr_denormalize else 1.0
+        m = sr_metrics(out, y, sr_div=div, to_luminance=self.cfg.sr_to_luminance)
+        crit = self.cfg.criterion
+        if type(crit) is nn.L1Loss and crit.reduction == "mean":
+            val_loss = m["l1"]
+        else:
+            val_loss = crit(out.float().div(div) if self.cfg.sr_denormalize else out.float(), y)
+        return {"PSNR": m["PSNR"], "SSIM": m["SSIM"], "psnr": m["psnr"], "ssim": m["ssim"], "metric_flags": m["flags"],
+                "val_loss": val_loss}
+
+    def _bit_width_record(self, stats):
+        return {
+            "mean_weights_bit_width": stats.get_weights_bit_width_mean(self.net),
+            "actual_weights_bit_width": stats.get_true_weights_width(self.net, max=False),
+            "actual_weights_max_bit_width": stats.get_true_weights_width(self.net),
+            "mean_activations_bit_width": stats.get_activations_bit_width_mean(self.net),
+            "actual_activations_bit_width": stats.get_true_activations_width(self.net, max=False),
+            "actual_activations_max_bit_width": stats.get_true_activations_width(self.net),
+            "converged": stats.is_converged(self.net, self.loss),
+        }
 
     def _validation_record(self, out, y, stats):
         return {
