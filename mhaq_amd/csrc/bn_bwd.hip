@@ -1,8 +1,11 @@
-// Backward of training-mode BatchNorm for gfx950, dense NHWC seen as [M = N*H*W][C]: fp32 with C % 4 == 0, or bf16 / fp16
-// with C % 8 == 0 (a lane owns 16 bytes of a row either way).
+// The BatchNorm kernels for gfx950, and the stem's max pool that some of them absorb.  Every tensor is dense NHWC seen as
+// [M = N*H*W][C]: fp32 with C % 4 == 0, or bf16 / fp16 with C % 8 == 0 -- a lane owns 16 bytes of a row either way, and every
+// streaming kernel is written ONCE over that element type (IoF32 / Io16<dtype>, "the element type" below).  A 16-bit element
+// is converted UP exactly and takes the fp32 arithmetic unchanged; a result is rounded to nearest-even ONCE on the way out
+// (IO::pack: a plain cast, NaN stays NaN, fp16 overflow gives +-inf).  Statistics, weight, bias, their gradients, the constant
+// rows and the workspaces stay fp32 / fp64.  In the order of the file:
 //
-// By default the forward stays with the framework (it saves the batch mean and invstd; the opt-in mhaq_fq_bn_fwd and its
-// 16-bit form mhaq_fq_bn_fwd_x16 are further down: "the training forward"); this file replaces the three launches of its backward with three bandwidth-bound ones:
+// The backward of training-mode BatchNorm (mhaq_fq_bn_bwd*), three bandwidth-bound launches in place of the framework's:
 //   bn_bwd_reduce_kernel     one read of x and dy   -> per-block fp64 partial rows of  sum dy  and  sum dy * (x - mean)
 //   bn_bwd_finalize_kernel   fixed-order fp64 sum of the partial rows -> dbias, dweight, per-channel constants
 //   bn_bwd_dx_kernel         a 2R1W stream in the shape of pt_bwd_kernel (fq_pt.hip):
@@ -10,23 +13,27 @@
 // The mean is NOT folded into an additive constant (B * x + D cancels when |mean| >> sigma): every term above is the
 // closed form's own, so the error of dx is bounded on |dy| + |dbias| / M + |xhat| * |dweight| / M.
 // Deterministic: fixed partition, fixed-order sums, no float atomics, no last-block ticket.
+// Where dy comes from is a template argument of the two streaming kernels: a tensor in memory (DyMem / DyMem16) or the
+// gradient of a 3x3 / stride 2 / padding 1 max pool behind the BatchNorm, gathered on the fly from the pooled gradient and a
+// 1-byte argmax code per output (DyPool, mhaq_fq_bn_pool_bwd; the codes are written by maxpool3s2_fwd_kernel).  The element
+// type comes with the source (Dy::IO); partition, sums, finalize and the dx expression are one code for all of them.  The
+// pool's gather on 16-bit tensors (DyPool16, mhaq_fq_bn_pool_bwd_x16) rounds its dy to 16 bits in registers where the
+// framework's pool backward rounds the tensor it would have written.
 //
-// Where dy comes from is a template argument of the two streaming kernels: a tensor in memory (DyMem, mhaq_fq_bn_bwd) or
-// the gradient of a 3x3 / stride 2 / padding 1 max pool behind the BatchNorm, gathered on the fly from the pooled gradient
-// and a 1-byte argmax code per output (DyPool, mhaq_fq_bn_pool_bwd; the codes are written by maxpool3s2_fwd_kernel at the
-// end of this file).  Partition, sums, finalize and the dx expression are one code for both.
+// The training forward (opt-in: mhaq_fq_bn_fwd*; by default it stays with the framework, which saves the batch mean and
+// invstd): bn_fwd_reduce_kernel, bn_fwd_finalize_kernel, bn_fwd_norm_kernel over the backward's partition.
 //
-// The element type comes with the source (Dy::IO): IoF32, or Io16<dtype> for x, dy and dx in bf16 / fp16 (DyMem16,
-// mhaq_fq_bn_bwd_x16).  A 16-bit element is converted UP exactly and takes the fp32 arithmetic unchanged -- the same fp64
-// sums, the same finalize, the same dx expression in the same order --; dx is rounded to nearest-even ONCE on the way out
-// (io16::down2: a plain cast, NaN stays NaN, fp16 overflow gives +-inf).  Statistics, weight, dweight, dbias and the
-// workspace stay fp32 / fp64.  The pool's gather on 16-bit tensors (DyPool16, mhaq_fq_bn_pool_bwd_x16) rounds its dy to
-// 16 bits in registers where the framework's pool backward rounds the tensor it would have written.
+// The frozen forward (mhaq_fq_bn_infer_*: the teacher): eval-mode BatchNorm from the running statistics with the ReLU and
+// the residual add behind it in one launch, bn_infer_act_kernel, and with the stem's pool, bn_relu_pool3s2_kernel.
 //
-// The host side is written once ("the host path of the entry points" below): bn_bwd_status is the argument check of all four
-// backward entry points and pool_fwd_status that of the pool forwards (the pooled stem forward included), bn_workspace_bytes stands behind the four workspace
-// queries, and io16::with_dtype (fq_io16.hpp) turns the dtype of an *_x16 call into the template argument, so that every
-// bn_bwd_launch<Dy, RU> is named in one place.
+// The pool's forward (mhaq_fq_maxpool3s2_fwd*): values and argmax codes, maxpool3s2_fwd_kernel; taken of the training
+// forward's output without storing it, the pooled stem forward (PoolOfNorm, mhaq_fq_bn_norm_pool3s2_fwd_x16).
+//
+// The host side is written once per family ("the host path of the entry points" at the end): a status function holds the
+// argument checks of the fp32 and the *_x16 entry point in the order include/mhaq_fq.h promises -- bn_bwd_status of all four
+// backward forms, pool_fwd_status of the pool forwards (the pooled stem forward included), bn_relu_pool_status of the frozen
+// stem --, bn_workspace_bytes stands behind the four backward workspace queries, and io16::with_dtype (fq_io16.hpp) turns the
+// dtype of an *_x16 call into the template argument, so that every launch is named in one place.
 #include "fq_io16.hpp"
 
 // The two tunables of the 16-bit pool gather (DyPool16), overridable at build time: tools/stem_pool_bench.py --dtype bf16 times
@@ -48,41 +55,68 @@ __device__ __forceinline__ vf4 bn_ld4(const float* p, int64_t vidx) {
   const vf4* q = reinterpret_cast<const vf4*>(p) + vidx;
   return NT ? __builtin_nontemporal_load(q) : *q;
 }
+template <bool NT>
 __device__ __forceinline__ void bn_st4(float* p, int64_t vidx, vf4 v) {
-  __builtin_nontemporal_store(v, reinterpret_cast<vf4*>(p) + vidx);
+  vf4* q = reinterpret_cast<vf4*>(p) + vidx;
+  if (NT) __builtin_nontemporal_store(v, q); else *q = v;
 }
 
-// ---------------------------------------------------------------- the element type of x, dy and dx
-// One 16-byte access of a lane: kW elements, unpacked to / packed from fp32.
+// ---------------------------------------------------------------- the element type of the streamed tensors
+// One 16-byte access of a lane: kW elements, unpacked to / packed from fp32 (16-bit elements: converted up exactly, rounded
+// to nearest-even once by pack).  `st` is the non-temporal store of the training kernels, whose output nothing reads soon;
+// `stv<NT>` stores a packed vector with the policy the caller names.
+// For the pool forward: `Code` is one argmax byte per element of the lane; a 16-bit type also hands out the ORIGINAL 16 bits
+// of element j of a vector (`bits`; an fp32 element is its own bits), packs eight of them again and names -inf in that form.
 struct IoF32 {
   using T = float;
   using Vec = vf4;
+  using Code = uint32_t;
   static constexpr int kW = 4;
   template <bool NT>
   static __device__ __forceinline__ Vec ld(const T* p, int64_t vidx) { return bn_ld4<NT>(p, vidx); }
   static __device__ __forceinline__ void unpack(const Vec& v, float (&o)[4]) {
     o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
   }
-  static __device__ __forceinline__ void st(T* p, int64_t vidx, const float (&o)[4]) {
-    bn_st4(p, vidx, vf4{o[0], o[1], o[2], o[3]});
+  static __device__ __forceinline__ Vec pack(const float (&o)[4]) { return vf4{o[0], o[1], o[2], o[3]}; }
+  template <bool NT>
+  static __device__ __forceinline__ void stv(T* p, int64_t vidx, Vec v) { bn_st4<NT>(p, vidx, v); }
+  static __device__ __forceinline__ void st(T* p, int64_t vidx, const float (&o)[4]) { stv<true>(p, vidx, pack(o)); }
+  static __device__ __forceinline__ Code pack_codes(const uint32_t (&cd)[4]) {
+    return cd[0] | (cd[1] << 8) | (cd[2] << 16) | (cd[3] << 24);
   }
 };
 template <int DT>
 struct Io16 {
+  typedef uint32_t vu2 __attribute__((ext_vector_type(2)));
   using T = uint16_t;
   using Vec = io16::vu4;
+  using Code = vu2;
   static constexpr int kW = 8;
+  static constexpr uint32_t kNegInfBits = DT == MHAQ_FQ_DT_BF16 ? 0xFF80u : 0xFC00u;
   template <bool NT>
   static __device__ __forceinline__ Vec ld(const T* p, int64_t vidx) { return io16::ld8<NT>(p, vidx); }
   static __device__ __forceinline__ void unpack(const Vec& v, float (&o)[8]) {
 #pragma unroll
     for (int w = 0; w < 4; ++w) io16::up2<DT>(v[w], o[2 * w], o[2 * w + 1]);
   }
-  static __device__ __forceinline__ void st(T* p, int64_t vidx, const float (&o)[8]) {
+  static __device__ __forceinline__ Vec pack(const float (&o)[8]) {
     Vec v;
 #pragma unroll
     for (int w = 0; w < 4; ++w) v[w] = io16::down2<DT>(o[2 * w], o[2 * w + 1]);
-    io16::st8<true>(p, vidx, v);
+    return v;
+  }
+  template <bool NT>
+  static __device__ __forceinline__ void stv(T* p, int64_t vidx, Vec v) { io16::st8<NT>(p, vidx, v); }
+  static __device__ __forceinline__ void st(T* p, int64_t vidx, const float (&o)[8]) { stv<true>(p, vidx, pack(o)); }
+  static __device__ __forceinline__ uint32_t bits(const Vec& v, int j) { return (v[j >> 1] >> (16 * (j & 1))) & 0xFFFFu; }
+  static __device__ __forceinline__ Vec from_bits(const uint32_t (&b)[8]) {
+    Vec v;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) v[w] = b[2 * w] | (b[2 * w + 1] << 16);
+    return v;
+  }
+  static __device__ __forceinline__ Code pack_codes(const uint32_t (&cd)[8]) {
+    return Code{cd[0] | (cd[1] << 8) | (cd[2] << 16) | (cd[3] << 24), cd[4] | (cd[5] << 8) | (cd[6] << 16) | (cd[7] << 24)};
   }
 };
 
@@ -238,7 +272,7 @@ struct DyPool {
 template <int DT>
 struct DyPool16 {
   using IO = Io16<DT>;
-  typedef uint32_t vu2 __attribute__((ext_vector_type(2)));
+  using vu2 = typename IO::Code;
   const uint16_t* __restrict__ g;
   const uint8_t* __restrict__ code;
   uint32_t h, w, oh, ow;
@@ -310,7 +344,7 @@ constexpr int kBnPoolRedU = 4;        // rows in flight with the pool's gather (
 constexpr int kBnPool16RedU = MHAQ_BN_POOL16_RED_U;      // ... and with the 16-bit gather (DyPool16)
 constexpr int kBnMinRows = 448;
 constexpr int kBnMaxChunks = 2048;
-constexpr int kBnDxU = 2;             // float4 per lane and stream in the dx kernel (kBwdU of fq_pt.hip)
+constexpr int kBnDxU = 2;             // 16-byte vectors per lane and stream in the dx kernel (kBwdU of fq_pt.hip)
 constexpr int64_t kBnMaxChannels = 1ll << 22;
 constexpr int kBnNConst = 5;          // per-channel constants of the dx kernel: mean, invstd, gamma * invstd, dbias / M, dweight / M
 
@@ -371,6 +405,31 @@ constexpr int64_t kBn16ReduceNtElems = MHAQ_BN16_REDUCE_NT_ELEMS;
 constexpr int64_t kBn16DxNtElems = MHAQ_BN16_DX_NT_ELEMS;
 constexpr int64_t kBn16BigElems = MHAQ_BN16_BIG_ELEMS;
 
+// ---------------------------------------------------------------- the two ends of a reduction's sums
+// (shared by the backward and the training forward: bn_*_reduce_kernel leaves partials[chunk][2][C], bn_*_finalize_kernel adds them)
+// The tail of a reduce kernel: the lanes' sums s1, s2 of K channels each across the block's rows of lanes -- LDS
+// [ty][2][K * cols], then thread (k, c) adds its column in row order -- into the block's two partial rows.
+template <int K>
+__device__ __forceinline__ void bn_block_partials(const double (&s1)[K], const double (&s2)[K], bool live, int ty, int tx,
+                                                  int cols, int rpp, int c0, int cv, double* __restrict__ partials) {
+  __shared__ __align__(16) double sm[kBlock * 2 * K];
+  const int w = K * cols;
+  if (live) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      sm[(ty * 2 + 0) * w + tx * K + j] = s1[j];
+      sm[(ty * 2 + 1) * w + tx * K + j] = s2[j];
+    }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < 2 * w) {
+    const int k = (int)threadIdx.x >= w ? 1 : 0, c = (int)threadIdx.x - k * w;
+    double tot = 0.0;
+    for (int r = 0; r < rpp; ++r) tot += sm[(r * 2 + k) * w + c];
+    partials[((int64_t)blockIdx.x * 2 + k) * ((int64_t)cv * K) + (int64_t)c0 * K + c] = tot;
+  }
+}
+
 // ---------------------------------------------------------------- 1. partial sums
 // partials[chunk][2][C] (fp64): row 0 = sum dy, row 1 = sum dy * (x - mean) over the chunk's rows.
 // Every sum is fp64 from the product on -- x - mean and dy * (x - mean) are exact in fp64 --, per lane, across the block
@@ -429,23 +488,7 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_kernel(
       }
     }
   }
-  // across the block's rows of lanes: LDS [ty][2][K * cols], then thread (k, c) adds its column in row order
-  __shared__ __align__(16) double sm[kBlock * 2 * K];
-  const int w = K * cols;
-  if (live) {
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-      sm[(ty * 2 + 0) * w + tx * K + j] = s1[j];
-      sm[(ty * 2 + 1) * w + tx * K + j] = s2[j];
-    }
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < 2 * w) {
-    const int k = (int)threadIdx.x >= w ? 1 : 0, c = (int)threadIdx.x - k * w;
-    double tot = 0.0;
-    for (int r = 0; r < rpp; ++r) tot += sm[(r * 2 + k) * w + c];
-    partials[((int64_t)blockIdx.x * 2 + k) * ((int64_t)cv * K) + (int64_t)c0 * K + c] = tot;
-  }
+  bn_block_partials<K>(s1, s2, live, ty, tx, cols, rpp, c0, cv, partials);
 }
 
 // ---------------------------------------------------------------- 2. fixed-order final sums and the constants of dx
@@ -486,10 +529,27 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_finalize_kernel(
 }
 
 // ---------------------------------------------------------------- 3. dx
-// Block b owns the 256 * U consecutive float4 at b * 256 * U, one pass; data loads first and unconditional (ragged lanes
-// clamp their index), the per-channel constants arrive under them.  The column of a float4 is its index modulo C / 4:
-// two wave-uniform 32-bit modulos per block, one per lane, a conditional subtract per further float4 -- and no
-// second fetch of the constants when 256 % (C / 4) == 0 (every power-of-two width up to 1024 channels).
+// The column of a lane's 16-byte vectors in the streaming kernels (dx, norm, the frozen forward), whose block b owns the
+// kBlock * kBnDxU consecutive vectors at b * kBlock * kBnDxU.  The column of a vector is its index modulo cv: (b * 512) mod cv
+// for the block's first from two wave-uniform 32-bit modulos (cv <= 2^20: the product fits), one modulo per lane, a conditional
+// subtract per further vector (next) -- and step == 0, no second fetch of the constants, when 256 % cv == 0 (every
+// power-of-two width up to 1024 fp32 channels).  (cb is computed before step, as the kernels had it written out: the other
+// order changes the instruction streams of the fp32 kernels.)
+struct BnColWalk {
+  uint32_t ucv, step, col;
+  __device__ __forceinline__ explicit BnColWalk(int cv) : ucv((uint32_t)cv) {
+    const uint32_t cb = ((blockIdx.x % ucv) * ((uint32_t)(kBlock * kBnDxU) % ucv)) % ucv;      // wave-uniform
+    step = (uint32_t)kBlock % ucv;                                                              // wave-uniform
+    col = (cb + threadIdx.x) % ucv;
+  }
+  __device__ __forceinline__ void next() {
+    col += step;
+    if (col >= ucv) col -= ucv;
+  }
+};
+
+// Block b owns the 256 * U consecutive vectors at b * 256 * U, one pass; data loads first and unconditional (ragged lanes
+// clamp their index), the per-channel constants arrive under them, by the column of each vector (BnColWalk).
 // The pool's source needs the pixel of a float4 as well: pixel and column of the block's first float4 from 32-bit
 // wave-uniform divisions (b = q * cv + r: b * 512 / cv = q * 512 + r * 512 / cv, r * 512 < 2^29), one 32-bit division by cv
 // per lane and float4 on top, two more inside the source for (n, ih, iw).
@@ -523,25 +583,18 @@ __launch_bounds__(kBlock) void bn_bwd_dx_kernel(
     b[u] = dy.template load_at_pixel<NT>(idc, pix0 + tq, ok, t - tq * (uint32_t)cv, (uint32_t)cv);
   }
   __builtin_amdgcn_sched_barrier(0);
-  // column of the block's first float4: (b * 512) mod cv from two 32-bit modulos (cv <= 2^20: the product fits)
-  const uint32_t ucv = (uint32_t)cv;
-  const uint32_t cb = ((blockIdx.x % ucv) * ((uint32_t)(kBlock * kBnDxU) % ucv)) % ucv;      // wave-uniform
-  const uint32_t step = (uint32_t)kBlock % ucv;                                               // wave-uniform
-  uint32_t col = (cb + threadIdx.x) % ucv;
+  BnColWalk cw(cv);
   const int64_t c = (int64_t)cv * K;
   float k[kBnNConst][K / 4][4];
 #pragma unroll
   for (int u = 0; u < kBnDxU; ++u) {
     const int64_t idx = base + u * kBlock;
-    if (u > 0) {
-      col += step;
-      if (col >= ucv) col -= ucv;
-    }
-    if (u == 0 || step != 0) {
+    if (u > 0) cw.next();
+    if (u == 0 || cw.step != 0) {
 #pragma unroll
       for (int q = 0; q < kBnNConst; ++q)
 #pragma unroll
-        for (int h = 0; h < K / 4; ++h) ldv<4>(consts + q * c + (int64_t)col * K + 4 * h, k[q][h]);
+        for (int h = 0; h < K / 4; ++h) ldv<4>(consts + q * c + (int64_t)cw.col * K + 4 * h, k[q][h]);
     }
     if (full || idx < nvec) {
       float xv[K], gv[K], o[K];
@@ -682,22 +735,7 @@ __global__ __launch_bounds__(kBlock) void bn_fwd_reduce_kernel(
       }
     }
   }
-  __shared__ __align__(16) double sm[kBlock * 2 * K];
-  const int w = K * cols;
-  if (live) {
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-      sm[(ty * 2 + 0) * w + tx * K + j] = s1[j];
-      sm[(ty * 2 + 1) * w + tx * K + j] = s2[j];
-    }
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < 2 * w) {
-    const int k = (int)threadIdx.x >= w ? 1 : 0, c = (int)threadIdx.x - k * w;
-    double tot = 0.0;
-    for (int r = 0; r < rpp; ++r) tot += sm[(r * 2 + k) * w + c];
-    partials[((int64_t)blockIdx.x * 2 + k) * ((int64_t)cv * K) + (int64_t)c0 * K + c] = tot;
-  }
+  bn_block_partials<K>(s1, s2, live, ty, tx, cols, rpp, c0, cv, partials);
 }
 
 // One block per group of 4 channels, the sums as in bn_bwd_finalize_kernel.  Everything is fp64 and every result is rounded
@@ -743,7 +781,7 @@ __global__ __launch_bounds__(kBlock) void bn_fwd_finalize_kernel(
 }
 
 // The element body of the training forward, y = (x - mean) * a + beta in fp32, in this order (the build contracts nothing):
-// bn_fwd_norm_kernel's, and that of the pooled stem forward at the end of this file (bn_norm_pool3s2_fwd16_kernel).
+// bn_fwd_norm_kernel's, and that of the pooled stem forward further down (PoolOfNorm in maxpool3s2_fwd_kernel).
 __device__ __forceinline__ float bn_norm_elem(float x, float mean, float a, float beta) { return (x - mean) * a + beta; }
 
 // y = bn_norm_elem(x, ..) per element.  Block, loads and the column arithmetic of
@@ -767,24 +805,18 @@ __launch_bounds__(kBlock) void bn_fwd_norm_kernel(
     a[u] = IO::template ld<NT>(x, (full || idx < nvec) ? idx : nvec - 1);
   }
   __builtin_amdgcn_sched_barrier(0);
-  const uint32_t ucv = (uint32_t)cv;
-  const uint32_t cb = ((blockIdx.x % ucv) * ((uint32_t)(kBlock * kBnDxU) % ucv)) % ucv;      // wave-uniform
-  const uint32_t step = (uint32_t)kBlock % ucv;                                               // wave-uniform
-  uint32_t col = (cb + threadIdx.x) % ucv;
+  BnColWalk cw(cv);
   const int64_t c = (int64_t)cv * K;
   float k[kBnFwdNConst][K / 4][4];
 #pragma unroll
   for (int u = 0; u < kBnDxU; ++u) {
     const int64_t idx = base + u * kBlock;
-    if (u > 0) {
-      col += step;
-      if (col >= ucv) col -= ucv;
-    }
-    if (u == 0 || step != 0) {
+    if (u > 0) cw.next();
+    if (u == 0 || cw.step != 0) {
 #pragma unroll
       for (int q = 0; q < kBnFwdNConst; ++q)
 #pragma unroll
-        for (int h = 0; h < K / 4; ++h) ldv<4>(consts + q * c + (int64_t)col * K + 4 * h, k[q][h]);
+        for (int h = 0; h < K / 4; ++h) ldv<4>(consts + q * c + (int64_t)cw.col * K + 4 * h, k[q][h]);
     }
     if (full || idx < nvec) {
       float xv[K], o[K];
@@ -875,23 +907,37 @@ static int bn_fwd_launch(const BnFwdCall& a, int64_t m, int64_t c) {
 //   bn_relu_pool3s2_kernel     max_pool2d(relu(t), 3, 2, 1) without a stored t (behind the pool's forward, further down)
 // t = (x - mean) * a + beta in fp32, in this order, uncontracted; the add and the ReLU round where torch's separate add and
 // clamp_min round, so every output is the bits of those ops on the same constants.  relu keeps a NaN.
-// Cache policy, overridable at build time (tools/teacher_fwd_bench.py times builds with forced policies next to the
-// product's): loads go by the byte rule of the training forward -- non-temporal once the INPUT streams together exceed
-// 56 Mi fp32 elements --; the output is read again by the next convolution, so stores take the default policy.
+// The two streaming kernels are written over the element type IO: fp32 (mhaq_fq_bn_infer_act, mhaq_fq_bn_relu_pool3s2) or
+// bf16 / fp16 (the *_x16 entry points: the teacher under autocast).  A 16-bit element is converted UP exactly and takes the
+// expression above unchanged -- the sum is rounded to fp32 before the ReLU --; the result is rounded to nearest-even ONCE on
+// the way out (IO::pack: a plain cast, a NaN stays a NaN, fp16 overflow gives +-inf).
+// Cache policy: loads go by the byte rule of the training forward -- non-temporal once the INPUT streams together exceed
+// 224 MiB (56 Mi fp32 elements, 112 Mi 16-bit ones) --; the output is read again by the next convolution, so stores take the
+// default policy (IO::stv<false>, not the non-temporal IO::st).  Occupancy goes by elements: kBnBigElems, and as in
+// fq_io16.hip for 16-bit tensors.  Each can be overridden at build time: tools/teacher_fwd_bench.py [--dtype bf16] times
+// builds with forced policies next to the product's.
 #ifndef MHAQ_BN_INFER_NT_ELEMS
 #define MHAQ_BN_INFER_NT_ELEMS (56ll << 20)
 #endif
 #ifndef MHAQ_BN_INFER_ST_NT
 #define MHAQ_BN_INFER_ST_NT 0
 #endif
+#ifndef MHAQ_BN_INFER16_NT_ELEMS
+#define MHAQ_BN_INFER16_NT_ELEMS (112ll << 20)
+#endif
+#ifndef MHAQ_BN_INFER16_BIG_ELEMS
+#define MHAQ_BN_INFER16_BIG_ELEMS (20ll << 20)
+#endif
+#ifndef MHAQ_BN_INFER16_ST_NT
+#define MHAQ_BN_INFER16_ST_NT 0
+#endif
 constexpr int64_t kBnInferNtElems = MHAQ_BN_INFER_NT_ELEMS;
 constexpr bool kBnInferStNt = MHAQ_BN_INFER_ST_NT != 0;
+constexpr int64_t kBnInfer16NtElems = MHAQ_BN_INFER16_NT_ELEMS;
+constexpr int64_t kBnInfer16BigElems = MHAQ_BN_INFER16_BIG_ELEMS;
+constexpr bool kBnInfer16StNt = MHAQ_BN_INFER16_ST_NT != 0;
 
 __device__ __forceinline__ float bn_relu(float v) { return v > 0.0f ? v : (v != v ? v : 0.0f); }
-__device__ __forceinline__ void bn_infer_st4(float* p, int64_t vidx, vf4 v) {
-  if constexpr (kBnInferStNt) bn_st4(p, vidx, v);
-  else reinterpret_cast<vf4*>(p)[vidx] = v;
-}
 
 __global__ __launch_bounds__(kBlock) void bn_infer_consts_kernel(
     const float* __restrict__ mean, const float* __restrict__ var, const float* __restrict__ weight,
@@ -904,143 +950,57 @@ __global__ __launch_bounds__(kBlock) void bn_infer_consts_kernel(
   consts[2 * c + i] = bias ? bias[i] : 0.0f;
 }
 
-// Block, loads, column arithmetic and occupancy are bn_fwd_norm_kernel's (fp32).  x2 is the residual (BN_ADD_RELU) or the
-// second branch's input with its constants k2 (BN2_ADD_RELU).
-template <bool NT, bool BIG, int MODE>
+// Block, loads, column arithmetic and occupancy are bn_fwd_norm_kernel's.  x2 is the residual (BN_ADD_RELU) or the second
+// branch's input with its constants k2 (BN2_ADD_RELU).
+template <bool NT, bool BIG, int MODE, class IO>
 __global__ __attribute__((amdgpu_waves_per_eu(
-    (BIG ? 1 : kBnFwdWaves<IoF32>), (BIG && kBnBigMaxWaves < kBnFwdWaves<IoF32> ? kBnBigMaxWaves : kBnFwdWaves<IoF32>))))
+    (BIG ? 1 : kBnFwdWaves<IO>), (BIG && kBnBigMaxWaves < kBnFwdWaves<IO> ? kBnBigMaxWaves : kBnFwdWaves<IO>))))
 __launch_bounds__(kBlock) void bn_infer_act_kernel(
-    const float* __restrict__ x, const float* __restrict__ x2, float* __restrict__ y, int64_t nvec, int cv,
-    const float* __restrict__ k1, const float* __restrict__ k2) {
+    const typename IO::T* __restrict__ x, const typename IO::T* __restrict__ x2, typename IO::T* __restrict__ y, int64_t nvec,
+    int cv, const float* __restrict__ k1, const float* __restrict__ k2) {
+  constexpr int K = IO::kW;
   constexpr bool kTwo = MODE != MHAQ_FQ_BN_RELU, kBn2 = MODE == MHAQ_FQ_BN2_ADD_RELU;
+  constexpr bool kStNt = K == 8 ? kBnInfer16StNt : kBnInferStNt;
   const int64_t blk0 = (int64_t)blockIdx.x * (kBlock * kBnDxU);
   const int64_t base = blk0 + threadIdx.x;
   const bool full = blk0 + kBlock * kBnDxU <= nvec;
-  vf4 a[kBnDxU], b[kBnDxU];
+  typename IO::Vec a[kBnDxU], b[kBnDxU];
 #pragma unroll
   for (int u = 0; u < kBnDxU; ++u) {
     const int64_t idx = base + u * kBlock;
     const int64_t idc = (full || idx < nvec) ? idx : nvec - 1;
-    a[u] = bn_ld4<NT>(x, idc);
-    if constexpr (kTwo) b[u] = bn_ld4<NT>(x2, idc);
+    a[u] = IO::template ld<NT>(x, idc);
+    if constexpr (kTwo) b[u] = IO::template ld<NT>(x2, idc);
   }
   __builtin_amdgcn_sched_barrier(0);
-  const uint32_t ucv = (uint32_t)cv;
-  const uint32_t cb = ((blockIdx.x % ucv) * ((uint32_t)(kBlock * kBnDxU) % ucv)) % ucv;      // wave-uniform
-  const uint32_t step = (uint32_t)kBlock % ucv;                                               // wave-uniform
-  uint32_t col = (cb + threadIdx.x) % ucv;
-  const int64_t c = (int64_t)cv * 4;
-  float k[kBnFwdNConst][4], kk[kBnFwdNConst][4];
+  BnColWalk cw(cv);
+  const int64_t c = (int64_t)cv * K;
+  float k[kBnFwdNConst][K / 4][4], kk[kBnFwdNConst][K / 4][4];
 #pragma unroll
   for (int u = 0; u < kBnDxU; ++u) {
     const int64_t idx = base + u * kBlock;
-    if (u > 0) {
-      col += step;
-      if (col >= ucv) col -= ucv;
-    }
-    if (u == 0 || step != 0) {
-#pragma unroll
-      for (int q = 0; q < kBnFwdNConst; ++q) {
-        ldv<4>(k1 + q * c + (int64_t)col * 4, k[q]);
-        if constexpr (kBn2) ldv<4>(k2 + q * c + (int64_t)col * 4, kk[q]);
-      }
-    }
-    if (full || idx < nvec) {
-      const float xv[4] = {a[u].x, a[u].y, a[u].z, a[u].w};
-      float o[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float t = (xv[j] - k[0][j]) * k[1][j] + k[2][j];
-        if constexpr (kTwo) {
-          const float bv = b[u][j];
-          t = t + (kBn2 ? (bv - kk[0][j]) * kk[1][j] + kk[2][j] : bv);
-        }
-        o[j] = bn_relu(t);
-      }
-      bn_infer_st4(y, idx, vf4{o[0], o[1], o[2], o[3]});
-    }
-  }
-}
-
-// The same launch on 16-bit tensors of the element type DT (mhaq_fq_bn_infer_act_x16: the teacher under autocast): one 16-byte
-// access per lane and stream is 8 channels, so 24 constants per slab, and cv = C / 8 in the column arithmetic.  A 16-bit element
-// is converted UP exactly and takes the expression above unchanged -- the sum is rounded to fp32 before the ReLU --; the result is
-// rounded to nearest-even ONCE on the way out (io16::down2: a plain cast, a NaN stays a NaN, fp16 overflow gives +-inf).  The
-// store is NOT Io16::st, which is non-temporal: the next convolution reads y.
-// Cache policy of the loads: the fp32 byte rule (the input streams together above 224 MiB = 112 Mi 16-bit elements); occupancy
-// by elements, as in fq_io16.hip.  Each can be overridden at build time (tools/teacher_fwd_bench.py --dtype bf16 times builds
-// with forced policies next to the product's).
-#ifndef MHAQ_BN_INFER16_NT_ELEMS
-#define MHAQ_BN_INFER16_NT_ELEMS (112ll << 20)
-#endif
-#ifndef MHAQ_BN_INFER16_BIG_ELEMS
-#define MHAQ_BN_INFER16_BIG_ELEMS (20ll << 20)
-#endif
-#ifndef MHAQ_BN_INFER16_ST_NT
-#define MHAQ_BN_INFER16_ST_NT 0
-#endif
-constexpr int64_t kBnInfer16NtElems = MHAQ_BN_INFER16_NT_ELEMS;
-constexpr int64_t kBnInfer16BigElems = MHAQ_BN_INFER16_BIG_ELEMS;
-constexpr bool kBnInfer16StNt = MHAQ_BN_INFER16_ST_NT != 0;
-
-template <bool NT, bool BIG, int MODE, int DT>
-__global__ __attribute__((amdgpu_waves_per_eu(
-    (BIG ? 1 : kBnFwdWaves<Io16<DT>>),
-    (BIG && kBnBigMaxWaves < kBnFwdWaves<Io16<DT>> ? kBnBigMaxWaves : kBnFwdWaves<Io16<DT>>))))
-__launch_bounds__(kBlock) void bn_infer_act16_kernel(
-    const uint16_t* __restrict__ x, const uint16_t* __restrict__ x2, uint16_t* __restrict__ y, int64_t nvec, int cv,
-    const float* __restrict__ k1, const float* __restrict__ k2) {
-  using IO = Io16<DT>;
-  constexpr bool kTwo = MODE != MHAQ_FQ_BN_RELU, kBn2 = MODE == MHAQ_FQ_BN2_ADD_RELU;
-  const int64_t blk0 = (int64_t)blockIdx.x * (kBlock * kBnDxU);
-  const int64_t base = blk0 + threadIdx.x;
-  const bool full = blk0 + kBlock * kBnDxU <= nvec;
-  io16::vu4 a[kBnDxU], b[kBnDxU];
-#pragma unroll
-  for (int u = 0; u < kBnDxU; ++u) {
-    const int64_t idx = base + u * kBlock;
-    const int64_t idc = (full || idx < nvec) ? idx : nvec - 1;
-    a[u] = io16::ld8<NT>(x, idc);
-    if constexpr (kTwo) b[u] = io16::ld8<NT>(x2, idc);
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  const uint32_t ucv = (uint32_t)cv;
-  const uint32_t cb = ((blockIdx.x % ucv) * ((uint32_t)(kBlock * kBnDxU) % ucv)) % ucv;      // wave-uniform
-  const uint32_t step = (uint32_t)kBlock % ucv;                                               // wave-uniform
-  uint32_t col = (cb + threadIdx.x) % ucv;
-  const int64_t c = (int64_t)cv * 8;
-  float k[kBnFwdNConst][2][4], kk[kBnFwdNConst][2][4];
-#pragma unroll
-  for (int u = 0; u < kBnDxU; ++u) {
-    const int64_t idx = base + u * kBlock;
-    if (u > 0) {
-      col += step;
-      if (col >= ucv) col -= ucv;
-    }
-    if (u == 0 || step != 0) {
+    if (u > 0) cw.next();
+    if (u == 0 || cw.step != 0) {
 #pragma unroll
       for (int q = 0; q < kBnFwdNConst; ++q)
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          ldv<4>(k1 + q * c + (int64_t)col * 8 + 4 * h, k[q][h]);
-          if constexpr (kBn2) ldv<4>(k2 + q * c + (int64_t)col * 8 + 4 * h, kk[q][h]);
+        for (int h = 0; h < K / 4; ++h) {
+          ldv<4>(k1 + q * c + (int64_t)cw.col * K + 4 * h, k[q][h]);
+          if constexpr (kBn2) ldv<4>(k2 + q * c + (int64_t)cw.col * K + 4 * h, kk[q][h]);
         }
     }
     if (full || idx < nvec) {
-      float xv[8], bv[8], o[8];
+      float xv[K], bv[K], o[K];
       IO::unpack(a[u], xv);
       if constexpr (kTwo) IO::unpack(b[u], bv);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
+      for (int j = 0; j < K; ++j) {
         const int h = j >> 2, i = j & 3;
         float t = (xv[j] - k[0][h][i]) * k[1][h][i] + k[2][h][i];
         if constexpr (kTwo) t = t + (kBn2 ? (bv[j] - kk[0][h][i]) * kk[1][h][i] + kk[2][h][i] : bv[j]);
         o[j] = bn_relu(t);
       }
-      io16::vu4 v;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) v[w] = io16::down2<DT>(o[2 * w], o[2 * w + 1]);
-      io16::st8<kBnInfer16StNt>(y, idx, v);
+      IO::template stv<kStNt>(y, idx, IO::pack(o));
     }
   }
 }
@@ -1076,144 +1036,55 @@ static int bn_infer_act_status(const void* x, const float* consts, const void* x
 }
 
 // The one launch (arguments checked by bn_infer_act_status); x2: the mode's second stream.
-template <int MODE>
-static int bn_infer_act_launch(const float* x, const float* k1, const float* x2, const float* k2, float* y, int64_t m,
+template <int MODE, class IO>
+static int bn_infer_act_launch(const void* x, const float* k1, const void* x2, const float* k2, void* y, int64_t m,
                                int64_t c, hipStream_t st) {
-  const int64_t nvec = m * (c >> 2);
+  using T = typename IO::T;
+  constexpr bool x16 = IO::kW == 8;
+  const int64_t nvec = m * (c / IO::kW);
   const int64_t grid = (nvec + kBlock * kBnDxU - 1) / (kBlock * kBnDxU);
-  const bool nt = m * c * (MODE == MHAQ_FQ_BN_RELU ? 1 : 2) >= kBnInferNtElems, big = m * c >= kBnBigElems;
-  MHAQ_LAUNCH((big ? (nt ? bn_infer_act_kernel<true, true, MODE> : bn_infer_act_kernel<false, true, MODE>)
-                   : (nt ? bn_infer_act_kernel<true, false, MODE> : bn_infer_act_kernel<false, false, MODE>)),
-              dim3((unsigned)grid), dim3(kBlock), 0, st, x, x2, y, nvec, (int)(c >> 2), k1, k2);
+  const bool nt = m * c * (MODE == MHAQ_FQ_BN_RELU ? 1 : 2) >= (x16 ? kBnInfer16NtElems : kBnInferNtElems);
+  const bool big = m * c >= (x16 ? kBnInfer16BigElems : kBnBigElems);
+  MHAQ_LAUNCH((big ? (nt ? bn_infer_act_kernel<true, true, MODE, IO> : bn_infer_act_kernel<false, true, MODE, IO>)
+                   : (nt ? bn_infer_act_kernel<true, false, MODE, IO> : bn_infer_act_kernel<false, false, MODE, IO>)),
+              dim3((unsigned)grid), dim3(kBlock), 0, st, (const T*)x, (const T*)x2, (T*)y, nvec, (int)(c / IO::kW), k1, k2);
   return launch_status();
 }
-// ... and on 16-bit elements: the cache policy by the bytes of the input streams, the occupancy by elements
-template <int MODE, int DT>
-static int bn_infer_act16_launch(const void* x, const float* k1, const void* x2, const float* k2, void* y, int64_t m,
-                                 int64_t c, hipStream_t st) {
-  const int64_t nvec = m * (c >> 3);
-  const int64_t grid = (nvec + kBlock * kBnDxU - 1) / (kBlock * kBnDxU);
-  const bool nt = m * c * (MODE == MHAQ_FQ_BN_RELU ? 1 : 2) >= kBnInfer16NtElems, big = m * c >= kBnInfer16BigElems;
-  MHAQ_LAUNCH((big ? (nt ? bn_infer_act16_kernel<true, true, MODE, DT> : bn_infer_act16_kernel<false, true, MODE, DT>)
-                   : (nt ? bn_infer_act16_kernel<true, false, MODE, DT> : bn_infer_act16_kernel<false, false, MODE, DT>)),
-              dim3((unsigned)grid), dim3(kBlock), 0, st, (const uint16_t*)x, (const uint16_t*)x2, (uint16_t*)y, nvec,
-              (int)(c >> 3), k1, k2);
-  return launch_status();
+// ... of the mode asked for, with that mode's operands
+template <class IO>
+static int bn_infer_act_mode(const void* x, const float* consts, const void* x2, const float* consts2, const void* residual,
+                             void* y, int64_t m, int64_t c, int mode, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (mode == MHAQ_FQ_BN_RELU) return bn_infer_act_launch<MHAQ_FQ_BN_RELU, IO>(x, consts, nullptr, nullptr, y, m, c, st);
+  if (mode == MHAQ_FQ_BN_ADD_RELU)
+    return bn_infer_act_launch<MHAQ_FQ_BN_ADD_RELU, IO>(x, consts, residual, nullptr, y, m, c, st);
+  return bn_infer_act_launch<MHAQ_FQ_BN2_ADD_RELU, IO>(x, consts, x2, consts2, y, m, c, st);
 }
 
 // ---------------------------------------------------------------- the pool's forward: values and argmax codes
-// max_pool2d(kernel 3, stride 2, padding 1) of a dense fp32 NHWC tensor: one lane per float4 of the output.  The selection
+// max_pool2d(kernel 3, stride 2, padding 1) of a dense NHWC tensor of the element type IO: one lane per 16 bytes of the output
+// (4 fp32 or 8 16-bit channels), nine 16-byte loads, a 16-byte store of p and one byte of code per channel.  The selection
 // is the framework's channels_last kernel's: the window's in-range positions in kh, then kw order, starting at -inf and
 // replacing on  val > max || isnan(val)  (so the LAST NaN of a window wins).  code = kh * 3 + kw of the chosen position.  A
 // window in which nothing replaces the start (all -inf) keeps the framework's initial index, 0 -- element (0, 0) of the plane,
 // which only the window (0, 0) contains (there it is code 4); every other such window gets kPoolNoneChosen, which no input
-// element matches: like the framework's backward, it sends its gradient nowhere.  The nine loads are unconditional on
-// clamped coordinates and take the default cache policy like the stores: every element of t is wanted again by up to three
-// neighbouring windows, p and code by the quantizer behind and by the backward (non-temporal loads of t measured 236 us
-// against 212 us on [250,64,112,112]; docs/NOTEBOOK.md section 6, "Stem pool").
-__global__ __launch_bounds__(kBlock) void maxpool3s2_fwd_kernel(
-    const float* __restrict__ t, float* __restrict__ p, uint8_t* __restrict__ code, uint32_t h, uint32_t w, uint32_t oh,
-    uint32_t ow, uint32_t cv, int64_t nvec) {
-  // pixel and column of the block's first float4, as in bn_bwd_dx_kernel
-  const uint32_t bq = blockIdx.x / cv, br = (blockIdx.x - bq * cv) * (uint32_t)kBlock, brq = br / cv;
-  const uint32_t tt = br - brq * cv + threadIdx.x, tq = tt / cv;
-  const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  const bool ok = idx < nvec;
-  const uint32_t pixel = ok ? bq * (uint32_t)kBlock + brq + tq : 0u, col = tt - tq * cv;
-  const uint32_t q = pixel / ow, n = q / oh, po = q - n * oh, pw = pixel - q * ow;
-  const int ih0 = (int)(po * 2u) - 1, iw0 = (int)(pw * 2u) - 1;
-  vf4 v[9];
-  bool in[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    const int ih = ih0 + k / 3, iw = iw0 + k % 3;
-    in[k] = ih >= 0 && ih < (int)h && iw >= 0 && iw < (int)w;
-    const uint32_t ihc = (uint32_t)(ih < 0 ? 0 : (ih < (int)h ? ih : (int)h - 1));
-    const uint32_t iwc = (uint32_t)(iw < 0 ? 0 : (iw < (int)w ? iw : (int)w - 1));
-    v[k] = bn_ld4<false>(t, (int64_t)((n * h + ihc) * w + iwc) * cv + col);
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  if (!ok) return;
-  const uint32_t start = (po == 0u && pw == 0u) ? 4u : kPoolNoneChosen;     // the framework's initial index 0
-  float mx[4];
-  uint32_t cd[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    mx[j] = -INFINITY;
-    cd[j] = start;
-  }
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    const float e[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const bool take = in[k] && (e[j] > mx[j] || e[j] != e[j]);
-      mx[j] = take ? e[j] : mx[j];
-      cd[j] = take ? (uint32_t)k : cd[j];
-    }
-  }
-  reinterpret_cast<vf4*>(p)[idx] = vf4{mx[0], mx[1], mx[2], mx[3]};
-  reinterpret_cast<uint32_t*>(code)[idx] = cd[0] | (cd[1] << 8) | (cd[2] << 16) | (cd[3] << 24);
-}
-
-// The frozen stem: p = max_pool2d(relu((x - mean) * a + beta), 3, 2, 1) of a dense fp32 NHWC x, the BatchNorm output never
-// stored.  Geometry, the nine clamped loads, their cache policy and the selection are the kernel's above, without the codes
-// (nothing is differentiated); the constants of the lane's four channels arrive under the data loads, and each in-range value
-// takes bn_infer_act_kernel's arithmetic before it is compared.
-__global__ __launch_bounds__(kBlock) void bn_relu_pool3s2_kernel(
-    const float* __restrict__ x, float* __restrict__ p, uint32_t h, uint32_t w, uint32_t oh, uint32_t ow, uint32_t cv,
-    int64_t nvec, const float* __restrict__ consts) {
-  const uint32_t bq = blockIdx.x / cv, br = (blockIdx.x - bq * cv) * (uint32_t)kBlock, brq = br / cv;
-  const uint32_t tt = br - brq * cv + threadIdx.x, tq = tt / cv;
-  const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  const bool ok = idx < nvec;
-  const uint32_t pixel = ok ? bq * (uint32_t)kBlock + brq + tq : 0u, col = tt - tq * cv;
-  const uint32_t q = pixel / ow, n = q / oh, po = q - n * oh, pw = pixel - q * ow;
-  const int ih0 = (int)(po * 2u) - 1, iw0 = (int)(pw * 2u) - 1;
-  vf4 v[9];
-  bool in[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    const int ih = ih0 + k / 3, iw = iw0 + k % 3;
-    in[k] = ih >= 0 && ih < (int)h && iw >= 0 && iw < (int)w;
-    const uint32_t ihc = (uint32_t)(ih < 0 ? 0 : (ih < (int)h ? ih : (int)h - 1));
-    const uint32_t iwc = (uint32_t)(iw < 0 ? 0 : (iw < (int)w ? iw : (int)w - 1));
-    v[k] = bn_ld4<false>(x, (int64_t)((n * h + ihc) * w + iwc) * cv + col);
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  float kc[kBnFwdNConst][4];
-#pragma unroll
-  for (int r = 0; r < kBnFwdNConst; ++r) ldv<4>(consts + ((int64_t)r * cv + col) * 4, kc[r]);
-  if (!ok) return;
-  float mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    const float e[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float r = bn_relu((e[j] - kc[0][j]) * kc[1][j] + kc[2][j]);
-      const bool take = in[k] && (r > mx[j] || r != r);
-      mx[j] = take ? r : mx[j];
-    }
-  }
-  reinterpret_cast<vf4*>(p)[idx] = vf4{mx[0], mx[1], mx[2], mx[3]};
-}
-
-// The same pool on a dense 16-bit NHWC tensor of the element type DT: one lane per 8 output channels, nine 16-byte loads, a
-// 16-byte store of p and an 8-byte store of codes.  Selection and codes as above, compared on the exactly upcast values (the
-// framework's kernel compares in fp32 too); what is stored is the chosen element's ORIGINAL 16 bits, so a NaN keeps its payload.
-// The kernel is written once for two entry points.  `Pre` says what the pool is taken of: the loaded tensor itself (PoolOfTensor,
-// mhaq_fq_maxpool3s2_fwd_x16: no further argument, and nothing is compiled in -- the instruction stream is that of the kernel
-// before `Pre` existed) or the training BatchNorm's output of it, which is never stored (PoolOfNorm,
-// mhaq_fq_bn_norm_pool3s2_fwd_x16: the stem's forward, the BatchNorm's third launch and the pool in one).  A `Pre` is built from
-// the kernel's trailing arguments, fetches what it needs for the lane's eight channels under the data loads and turns each
-// loaded vector into the 16-bit values the selection runs on.
+// element matches: like the framework's backward, it sends its gradient nowhere.  16-bit values are compared exactly upcast
+// (the framework's kernel compares in fp32 too); what is stored is the chosen element's ORIGINAL bits, so a NaN keeps its
+// payload: the maximum itself in fp32, the 16 bits kept beside it (`raw`) for a 16-bit element.  The nine loads are unconditional on clamped coordinates and take the default cache policy like the
+// stores: every element of t is wanted again by up to three neighbouring windows, p and code by the quantizer behind and by
+// the backward (non-temporal loads of t measured 236 us against 212 us on fp32 [250,64,112,112]; docs/NOTEBOOK.md section 6,
+// "Stem pool").
+// `Pre` says what the pool is taken of: the loaded tensor itself (PoolOfTensor, mhaq_fq_maxpool3s2_fwd and its _x16 form: no
+// further argument, and nothing is compiled in) or the training BatchNorm's output of it, which is never stored (PoolOfNorm,
+// mhaq_fq_bn_norm_pool3s2_fwd_x16: the stem's forward, the BatchNorm's third launch and the pool in one).  A `Pre` is built
+// from the kernel's trailing arguments, fetches what it needs for the lane's channels under the data loads and turns each
+// loaded vector into the values the selection runs on.
 struct PoolOfTensor {
   static constexpr bool kTransforms = false;
   struct K {};
 };
 // y = R16(bn_norm_elem(up(x), mean, a, beta)), the 16 bits bn_fwd_norm_kernel stores: a = weight * invstd is
-// bn_fwd_finalize_kernel's fp32 product, the rounding Io16::st's io16::down2.  The selection then runs on THOSE values, not on
+// bn_fwd_finalize_kernel's fp32 product, the rounding Io16::pack's, as in Io16::st.  The selection then runs on THOSE values, not on
 // x: two x that round to one y are a tie that the first in-range position wins, gamma < 0 reverses the order and gamma == 0
 // ties every window, as in the pool of the stored y.  (All nine vectors are converted, the out-of-range ones too: 36 packed
 // converts and no branch.)  The four rows are fp32 [C], 4-byte aligned: scalar indexing, as bn_bwd_reduce_kernel reads the mean.
@@ -1242,21 +1113,22 @@ struct PoolOfNorm {
     }
     return k;
   }
-  template <int DT>
-  static __device__ __forceinline__ void apply(const K& k, io16::vu4& v) {
+  template <class IO>
+  static __device__ __forceinline__ void apply(const K& k, typename IO::Vec& v) {
+    static_assert(IO::kW == 8, "the pooled stem forward exists for 16-bit tensors");
     float e[8];
-    Io16<DT>::unpack(v, e);
+    IO::unpack(v, e);
 #pragma unroll
     for (int j = 0; j < 8; ++j) e[j] = bn_norm_elem(e[j], k.mu[j], k.a[j], k.beta[j]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = io16::down2<DT>(e[2 * i], e[2 * i + 1]);
+    v = IO::pack(e);
   }
 };
-template <int DT, class Pre = PoolOfTensor, class... PreArgs>
-__global__ __launch_bounds__(kBlock) void maxpool3s2_fwd16_kernel(
-    const uint16_t* __restrict__ t, uint16_t* __restrict__ p, uint8_t* __restrict__ code, uint32_t h, uint32_t w, uint32_t oh,
-    uint32_t ow, uint32_t cv, int64_t nvec, PreArgs... pre_args) {
-  typedef uint32_t vu2 __attribute__((ext_vector_type(2)));
+template <class IO, class Pre = PoolOfTensor, class... PreArgs>
+__global__ __launch_bounds__(kBlock) void maxpool3s2_fwd_kernel(
+    const typename IO::T* __restrict__ t, typename IO::T* __restrict__ p, uint8_t* __restrict__ code, uint32_t h, uint32_t w,
+    uint32_t oh, uint32_t ow, uint32_t cv, int64_t nvec, PreArgs... pre_args) {
+  constexpr int K = IO::kW;
+  // pixel and column of the block's first vector, as in bn_bwd_dx_kernel
   const uint32_t bq = blockIdx.x / cv, br = (blockIdx.x - bq * cv) * (uint32_t)kBlock, brq = br / cv;
   const uint32_t tt = br - brq * cv + threadIdx.x, tq = tt / cv;
   const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -1264,7 +1136,7 @@ __global__ __launch_bounds__(kBlock) void maxpool3s2_fwd16_kernel(
   const uint32_t pixel = ok ? bq * (uint32_t)kBlock + brq + tq : 0u, col = tt - tq * cv;
   const uint32_t q = pixel / ow, n = q / oh, po = q - n * oh, pw = pixel - q * ow;
   const int ih0 = (int)(po * 2u) - 1, iw0 = (int)(pw * 2u) - 1;
-  io16::vu4 v[9];
+  typename IO::Vec v[9];
   bool in[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) {
@@ -1272,7 +1144,7 @@ __global__ __launch_bounds__(kBlock) void maxpool3s2_fwd16_kernel(
     in[k] = ih >= 0 && ih < (int)h && iw >= 0 && iw < (int)w;
     const uint32_t ihc = (uint32_t)(ih < 0 ? 0 : (ih < (int)h ? ih : (int)h - 1));
     const uint32_t iwc = (uint32_t)(iw < 0 ? 0 : (iw < (int)w ? iw : (int)w - 1));
-    v[k] = io16::ld8<false>(t, (int64_t)((n * h + ihc) * w + iwc) * cv + col);
+    v[k] = IO::template ld<false>(t, (int64_t)((n * h + ihc) * w + iwc) * cv + col);
   }
   __builtin_amdgcn_sched_barrier(0);
   [[maybe_unused]] typename Pre::K pk;
@@ -1280,47 +1152,48 @@ __global__ __launch_bounds__(kBlock) void maxpool3s2_fwd16_kernel(
   if (!ok) return;
   if constexpr (Pre::kTransforms) {
 #pragma unroll
-    for (int k = 0; k < 9; ++k) Pre::template apply<DT>(pk, v[k]);
+    for (int k = 0; k < 9; ++k) Pre::template apply<IO>(pk, v[k]);
   }
   const uint32_t start = (po == 0u && pw == 0u) ? 4u : kPoolNoneChosen;     // the framework's initial index 0
-  float mx[8];
-  uint32_t raw[8], cd[8];                         // raw: the chosen element's 16 bits (-inf until one is chosen)
+  float mx[K];
+  [[maybe_unused]] uint32_t raw[K];               // K == 8: the chosen element's 16 bits (-inf until one is chosen)
+  uint32_t cd[K];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
+  for (int j = 0; j < K; ++j) {
     mx[j] = -INFINITY;
-    raw[j] = DT == MHAQ_FQ_DT_BF16 ? 0xFF80u : 0xFC00u;
+    if constexpr (K == 8) raw[j] = IO::kNegInfBits;
     cd[j] = start;
   }
 #pragma unroll
   for (int k = 0; k < 9; ++k) {
-    float e[8];
-    Io16<DT>::unpack(v[k], e);
+    float e[K];
+    IO::unpack(v[k], e);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
+    for (int j = 0; j < K; ++j) {
       const bool take = in[k] && (e[j] > mx[j] || e[j] != e[j]);
       mx[j] = take ? e[j] : mx[j];
-      raw[j] = take ? (v[k][j >> 1] >> (16 * (j & 1))) & 0xFFFFu : raw[j];
+      if constexpr (K == 8) raw[j] = take ? IO::bits(v[k], j) : raw[j];
       cd[j] = take ? (uint32_t)k : cd[j];
     }
   }
-  io16::vu4 pv;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) pv[i] = raw[2 * i] | (raw[2 * i + 1] << 16);
-  reinterpret_cast<io16::vu4*>(p)[idx] = pv;
-  reinterpret_cast<vu2*>(code)[idx] = vu2{cd[0] | (cd[1] << 8) | (cd[2] << 16) | (cd[3] << 24),
-                                          cd[4] | (cd[5] << 8) | (cd[6] << 16) | (cd[7] << 24)};
+  // (fp32: the maxima are the bits; the vector is written out because IO::pack(mx), an array handed on by reference, is
+  // lowered otherwise and reorders the instruction stream)
+  if constexpr (K == 8) IO::template stv<false>(p, idx, IO::from_bits(raw));
+  else IO::template stv<false>(p, idx, vf4{mx[0], mx[1], mx[2], mx[3]});
+  reinterpret_cast<typename IO::Code*>(code)[idx] = IO::pack_codes(cd);
 }
 
-
-// The frozen stem on a dense 16-bit NHWC x (mhaq_fq_bn_relu_pool3s2_x16): maxpool3s2_fwd16_kernel without the codes and with the
-// constants of the lane's eight channels under the nine loads, as bn_relu_pool3s2_kernel relates to the fp32 pool forward.
-// Every in-range value is upcast exactly, takes bn_infer_act_kernel's fp32 arithmetic and is compared in fp32; the maximum is
-// rounded to 16 bits ONCE at the end -- rounding is monotone, so this is the value of rounding all nine first, for 4 packed
-// converts instead of 36.  A NaN that wins stays a NaN through the cast.
-template <int DT>
-__global__ __launch_bounds__(kBlock) void bn_relu_pool3s2_16_kernel(
-    const uint16_t* __restrict__ x, uint16_t* __restrict__ p, uint32_t h, uint32_t w, uint32_t oh, uint32_t ow, uint32_t cv,
-    int64_t nvec, const float* __restrict__ consts) {
+// The frozen stem (mhaq_fq_bn_relu_pool3s2 and its _x16 form): p = max_pool2d(relu((x - mean) * a + beta), 3, 2, 1) of a dense
+// NHWC x, the BatchNorm output never stored.  Geometry, the nine clamped loads, their cache policy and the selection are the
+// kernel's above, without the codes (nothing is differentiated); the constants of the lane's channels arrive under the data
+// loads, and each in-range value takes bn_infer_act_kernel's fp32 arithmetic before it is compared in fp32.  A 16-bit maximum
+// is rounded ONCE at the end -- rounding is monotone, so this is the value of rounding all nine first, for 4 packed converts
+// instead of 36.  A NaN that wins stays a NaN through the cast.
+template <class IO>
+__global__ __launch_bounds__(kBlock) void bn_relu_pool3s2_kernel(
+    const typename IO::T* __restrict__ x, typename IO::T* __restrict__ p, uint32_t h, uint32_t w, uint32_t oh, uint32_t ow,
+    uint32_t cv, int64_t nvec, const float* __restrict__ consts) {
+  constexpr int K = IO::kW;
   const uint32_t bq = blockIdx.x / cv, br = (blockIdx.x - bq * cv) * (uint32_t)kBlock, brq = br / cv;
   const uint32_t tt = br - brq * cv + threadIdx.x, tq = tt / cv;
   const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -1328,7 +1201,7 @@ __global__ __launch_bounds__(kBlock) void bn_relu_pool3s2_16_kernel(
   const uint32_t pixel = ok ? bq * (uint32_t)kBlock + brq + tq : 0u, col = tt - tq * cv;
   const uint32_t q = pixel / ow, n = q / oh, po = q - n * oh, pw = pixel - q * ow;
   const int ih0 = (int)(po * 2u) - 1, iw0 = (int)(pw * 2u) - 1;
-  io16::vu4 v[9];
+  typename IO::Vec v[9];
   bool in[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) {
@@ -1336,34 +1209,31 @@ __global__ __launch_bounds__(kBlock) void bn_relu_pool3s2_16_kernel(
     in[k] = ih >= 0 && ih < (int)h && iw >= 0 && iw < (int)w;
     const uint32_t ihc = (uint32_t)(ih < 0 ? 0 : (ih < (int)h ? ih : (int)h - 1));
     const uint32_t iwc = (uint32_t)(iw < 0 ? 0 : (iw < (int)w ? iw : (int)w - 1));
-    v[k] = io16::ld8<false>(x, (int64_t)((n * h + ihc) * w + iwc) * cv + col);
+    v[k] = IO::template ld<false>(x, (int64_t)((n * h + ihc) * w + iwc) * cv + col);
   }
   __builtin_amdgcn_sched_barrier(0);
-  float kc[kBnFwdNConst][2][4];
+  float kc[kBnFwdNConst][K / 4][4];
 #pragma unroll
   for (int r = 0; r < kBnFwdNConst; ++r)
 #pragma unroll
-    for (int hh = 0; hh < 2; ++hh) ldv<4>(consts + ((int64_t)r * cv + col) * 8 + 4 * hh, kc[r][hh]);
+    for (int hh = 0; hh < K / 4; ++hh) ldv<4>(consts + ((int64_t)r * cv + col) * K + 4 * hh, kc[r][hh]);
   if (!ok) return;
-  float mx[8];
+  float mx[K];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) mx[j] = -INFINITY;
+  for (int j = 0; j < K; ++j) mx[j] = -INFINITY;
 #pragma unroll
   for (int k = 0; k < 9; ++k) {
-    float e[8];
-    Io16<DT>::unpack(v[k], e);
+    float e[K];
+    IO::unpack(v[k], e);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
+    for (int j = 0; j < K; ++j) {
       const int hh = j >> 2, i = j & 3;
       const float r = bn_relu((e[j] - kc[0][hh][i]) * kc[1][hh][i] + kc[2][hh][i]);
       const bool take = in[k] && (r > mx[j] || r != r);
       mx[j] = take ? r : mx[j];
     }
   }
-  io16::vu4 pv;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) pv[i] = io16::down2<DT>(mx[2 * i], mx[2 * i + 1]);
-  reinterpret_cast<io16::vu4*>(p)[idx] = pv;
+  IO::template stv<false>(p, idx, IO::pack(mx));
 }
 
 // pooled extent of kernel 3, stride 2, padding 1, dilation 1, ceil_mode = false
@@ -1417,21 +1287,46 @@ static int pool_fwd_status(const void* t, const void* p, const uint8_t* code, in
   if (!bn_aligned(t, 16) || !bn_aligned(p, 16) || !bn_aligned(code, kw)) return MHAQ_FQ_EALIGN;
   return 0;
 }
-// (more: what the kernel takes behind nvec -- the statistics and parameters of PoolOfNorm)
-template <class... More>
-using Pool16Kernel = void (*)(const uint16_t*, uint16_t*, uint8_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int64_t,
-                              More...);
-template <class T, class... More>
-static int pool_fwd_launch(void (*kernel)(const T*, T*, uint8_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int64_t,
-                                          More...),
-                           const void* t, void* p, uint8_t* code, int64_t n, int64_t h, int64_t w, int64_t c, void* stream,
-                           More... more) {
-  constexpr int64_t kw = 16 / sizeof(T);
+// the one launch of a pool forward over [n][h][w][c]: one lane per kw output channels
+struct PoolGrid {
+  int64_t oh, ow, nvec, blocks;
+};
+static inline PoolGrid pool_grid(int64_t n, int64_t h, int64_t w, int64_t c, int64_t kw) {
   const int64_t oh = pool_out(h), ow = pool_out(w), nvec = n * oh * ow * (c / kw);
-  const int64_t grid = (nvec + kBlock - 1) / kBlock;
-  if (grid > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
-  MHAQ_LAUNCH(kernel, dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream, (const T*)t, (T*)p, code, (uint32_t)h,
-              (uint32_t)w, (uint32_t)oh, (uint32_t)ow, (uint32_t)(c / kw), nvec, more...);
+  return PoolGrid{oh, ow, nvec, (nvec + kBlock - 1) / kBlock};
+}
+// (More: what the kernel takes behind nvec -- the statistics and parameters of PoolOfNorm)
+template <class T, class... More>
+using PoolKernel = void (*)(const T*, T*, uint8_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int64_t, More...);
+template <class T, class... More>
+static int pool_fwd_launch(PoolKernel<T, More...> kernel, const void* t, void* p, uint8_t* code, int64_t n, int64_t h,
+                           int64_t w, int64_t c, void* stream, More... more) {
+  constexpr int64_t kw = 16 / sizeof(T);
+  const PoolGrid g = pool_grid(n, h, w, c, kw);
+  if (g.blocks > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
+  MHAQ_LAUNCH(kernel, dim3((unsigned)g.blocks), dim3(kBlock), 0, (hipStream_t)stream, (const T*)t, (T*)p, code, (uint32_t)h,
+              (uint32_t)w, (uint32_t)g.oh, (uint32_t)g.ow, (uint32_t)(c / kw), g.nvec, more...);
+  return launch_status();
+}
+
+// The frozen stem's pool (no codes): required pointers, the dtype (kw == 8), width and range with the size of the grid, the
+// alignment -- the constant rows are read 16 bytes at a time --; then its one launch.
+static int bn_relu_pool_status(const void* x, const float* consts, const void* p, int kw, int dtype, int64_t n, int64_t h,
+                               int64_t w, int64_t c) {
+  if (!x || !consts || !p) return MHAQ_FQ_EINVAL;
+  if (kw == 8 && !io16::known_dtype(dtype)) return MHAQ_FQ_EINVAL;
+  if (const int rc = pool_dims_status(n, h, w, c, kw)) return rc;
+  if (pool_grid(n, h, w, c, kw).blocks > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
+  if (!bn_aligned(x, 16) || !bn_aligned(consts, 16) || !bn_aligned(p, 16)) return MHAQ_FQ_EALIGN;
+  return 0;
+}
+template <class IO>
+static int bn_relu_pool_launch(const void* x, const float* consts, void* p, int64_t n, int64_t h, int64_t w, int64_t c,
+                               void* stream) {
+  using T = typename IO::T;
+  const PoolGrid g = pool_grid(n, h, w, c, IO::kW);
+  MHAQ_LAUNCH(bn_relu_pool3s2_kernel<IO>, dim3((unsigned)g.blocks), dim3(kBlock), 0, (hipStream_t)stream, (const T*)x, (T*)p,
+              (uint32_t)h, (uint32_t)w, (uint32_t)g.oh, (uint32_t)g.ow, (uint32_t)(c / IO::kW), g.nvec, consts);
   return launch_status();
 }
 
@@ -1493,53 +1388,29 @@ int mhaq_fq_bn_infer_consts(const float* running_mean, const float* running_var,
 int mhaq_fq_bn_infer_act(const float* x, const float* consts, const float* x2, const float* consts2, const float* residual,
                          float* y, int64_t m, int64_t c, int mode, void* stream) {
   if (const int rc = bn_infer_act_status(x, consts, x2, consts2, residual, y, m, c, mode, 4, 0)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (mode == MHAQ_FQ_BN_RELU) return bn_infer_act_launch<MHAQ_FQ_BN_RELU>(x, consts, nullptr, nullptr, y, m, c, st);
-  if (mode == MHAQ_FQ_BN_ADD_RELU) return bn_infer_act_launch<MHAQ_FQ_BN_ADD_RELU>(x, consts, residual, nullptr, y, m, c, st);
-  return bn_infer_act_launch<MHAQ_FQ_BN2_ADD_RELU>(x, consts, x2, consts2, y, m, c, st);
+  return bn_infer_act_mode<IoF32>(x, consts, x2, consts2, residual, y, m, c, mode, stream);
 }
 
 int mhaq_fq_bn_infer_act_x16(const void* x, const float* consts, const void* x2, const float* consts2, const void* residual,
                              void* y, int64_t m, int64_t c, int mode, int dtype, void* stream) {
   if (const int rc = bn_infer_act_status(x, consts, x2, consts2, residual, y, m, c, mode, 8, dtype)) return rc;
-  hipStream_t st = (hipStream_t)stream;
   return io16::with_dtype(dtype, [&](auto dt) {
-    constexpr int DT = decltype(dt)::value;
-    if (mode == MHAQ_FQ_BN_RELU) return bn_infer_act16_launch<MHAQ_FQ_BN_RELU, DT>(x, consts, nullptr, nullptr, y, m, c, st);
-    if (mode == MHAQ_FQ_BN_ADD_RELU)
-      return bn_infer_act16_launch<MHAQ_FQ_BN_ADD_RELU, DT>(x, consts, residual, nullptr, y, m, c, st);
-    return bn_infer_act16_launch<MHAQ_FQ_BN2_ADD_RELU, DT>(x, consts, x2, consts2, y, m, c, st);
+    return bn_infer_act_mode<Io16<decltype(dt)::value>>(x, consts, x2, consts2, residual, y, m, c, mode, stream);
   });
 }
 
 int mhaq_fq_bn_relu_pool3s2_x16(const void* x, const float* consts, void* p, int64_t n, int64_t h, int64_t w, int64_t c,
                                 int dtype, void* stream) {
-  if (!x || !consts || !p) return MHAQ_FQ_EINVAL;
-  if (n <= 0 || h <= 0 || w <= 0 || c <= 0 || !io16::known_dtype(dtype)) return MHAQ_FQ_EINVAL;
-  if (const int rc = pool_dims_status(n, h, w, c, 8)) return rc;
-  const int64_t oh = pool_out(h), ow = pool_out(w), nvec = n * oh * ow * (c >> 3);
-  const int64_t grid = (nvec + kBlock - 1) / kBlock;
-  if (grid > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
-  if (!bn_aligned(x, 16) || !bn_aligned(consts, 16) || !bn_aligned(p, 16)) return MHAQ_FQ_EALIGN;
+  if (const int rc = bn_relu_pool_status(x, consts, p, 8, dtype, n, h, w, c)) return rc;
   return io16::with_dtype(dtype, [&](auto dt) {
-    MHAQ_LAUNCH(bn_relu_pool3s2_16_kernel<decltype(dt)::value>, dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream,
-                (const uint16_t*)x, (uint16_t*)p, (uint32_t)h, (uint32_t)w, (uint32_t)oh, (uint32_t)ow, (uint32_t)(c >> 3),
-                nvec, consts);
-    return launch_status();
+    return bn_relu_pool_launch<Io16<decltype(dt)::value>>(x, consts, p, n, h, w, c, stream);
   });
 }
 
 int mhaq_fq_bn_relu_pool3s2(const float* x, const float* consts, float* p, int64_t n, int64_t h, int64_t w, int64_t c,
                             void* stream) {
-  if (!x || !consts || !p) return MHAQ_FQ_EINVAL;
-  if (const int rc = pool_dims_status(n, h, w, c, 4)) return rc;
-  const int64_t oh = pool_out(h), ow = pool_out(w), nvec = n * oh * ow * (c >> 2);
-  const int64_t grid = (nvec + kBlock - 1) / kBlock;
-  if (grid > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
-  if (!bn_aligned(x, 16) || !bn_aligned(consts, 16) || !bn_aligned(p, 16)) return MHAQ_FQ_EALIGN;
-  MHAQ_LAUNCH(bn_relu_pool3s2_kernel, dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream, x, p, (uint32_t)h,
-              (uint32_t)w, (uint32_t)oh, (uint32_t)ow, (uint32_t)(c >> 2), nvec, consts);
-  return launch_status();
+  if (const int rc = bn_relu_pool_status(x, consts, p, 4, 0, n, h, w, c)) return rc;
+  return bn_relu_pool_launch<IoF32>(x, consts, p, n, h, w, c, stream);
 }
 
 int mhaq_fq_bn_bwd_x16(const void* x, const void* dy, const float* mean, const float* invstd, const float* weight, void* dx,
@@ -1556,14 +1427,15 @@ int mhaq_fq_bn_bwd_x16(const void* x, const void* dy, const float* mean, const f
 int mhaq_fq_maxpool3s2_fwd(const float* t, float* p, uint8_t* code, int64_t n, int64_t h, int64_t w, int64_t c,
                            void* stream) {
   if (const int rc = pool_fwd_status(t, p, code, 4, 0, n, h, w, c)) return rc;
-  return pool_fwd_launch<float>(maxpool3s2_fwd_kernel, t, p, code, n, h, w, c, stream);
+  const PoolKernel<float> k = maxpool3s2_fwd_kernel<IoF32>;
+  return pool_fwd_launch(k, t, p, code, n, h, w, c, stream);
 }
 
 int mhaq_fq_maxpool3s2_fwd_x16(const void* t, void* p, uint8_t* code, int64_t n, int64_t h, int64_t w, int64_t c, int dtype,
                                void* stream) {
   if (const int rc = pool_fwd_status(t, p, code, 8, dtype, n, h, w, c)) return rc;
   return io16::with_dtype(dtype, [&](auto dt) {
-    const Pool16Kernel<> k = maxpool3s2_fwd16_kernel<decltype(dt)::value>;
+    const PoolKernel<uint16_t> k = maxpool3s2_fwd_kernel<Io16<decltype(dt)::value>>;
     return pool_fwd_launch(k, t, p, code, n, h, w, c, stream);
   });
 }
@@ -1576,8 +1448,8 @@ int mhaq_fq_bn_norm_pool3s2_fwd_x16(const void* x, const float* mean, const floa
   if (const int rc = pool_fwd_status(x, p, code, 8, dtype, n, h, w, c)) return rc;
   if (!bn_aligned(mean, 4) || !bn_aligned(invstd, 4) || !bn_aligned(weight, 4) || !bn_aligned(bias, 4)) return MHAQ_FQ_EALIGN;
   return io16::with_dtype(dtype, [&](auto dt) {
-    const Pool16Kernel<const float*, const float*, const float*, const float*> k =
-        maxpool3s2_fwd16_kernel<decltype(dt)::value, PoolOfNorm>;
+    const PoolKernel<uint16_t, const float*, const float*, const float*, const float*> k =
+        maxpool3s2_fwd_kernel<Io16<decltype(dt)::value>, PoolOfNorm>;
     return pool_fwd_launch(k, x, p, code, n, h, w, c, stream, mean, invstd, weight, bias);
   });
 }

@@ -341,43 +341,69 @@ def row_minmax(w: torch.Tensor):
     return mn, mx
 
 
-@_on_device
-def bn_forward_train(x, weight=None, bias=None, running_mean=None, running_var=None, factor=0.1, eps=1e-5):
-    """Training-mode BatchNorm forward of a dense float32 channels_last [N, C, H, W] tensor on mhaq_fq_bn_fwd (no autograd:
-    the compiled node bn_train(hip_forward=True) is the differentiable form).  Returns (y, save_mean, save_invstd); the running
-    statistics, both given or both None, are updated in place with `factor`."""
-    x = _require_cuda_f32(x.detach(), "x", any_dense_layout=True)
-    if x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last):
-        raise ValueError("bn_forward_train: x must be a dense channels_last [N, C, H, W] tensor")
+# ----------------------------------------------------------------------------- BatchNorm forwards (no autograd)
+# Each op has a float32 name and an _x16 name (bfloat16 / float16 tensors; per-channel vectors, statistics and constant slabs
+# stay float32).  Both are one body, told apart by the C entry point they pass: `fn` is the public name for the messages.
+def _nhwc(t, name, x16, where=""):
+    """`t` detached, as a dense channels_last [N, C, H, W] device tensor: float32, or with x16 bfloat16 / float16."""
+    t = t.detach()
+    if not x16:
+        t = _require_cuda_f32(t, name, any_dense_layout=True)
+    elif not t.is_cuda:
+        raise _lib.MhaqFqError(f"{name} is on {t.device}: the kernels run only on an MI355X (no CPU fallback by design)")
+    elif t.dtype not in _X16:
+        raise TypeError(f"{name} must be bfloat16 or float16, got {t.dtype}")
+    if t.dim() != 4 or not t.is_contiguous(memory_format=torch.channels_last):
+        raise ValueError(f"{where}{name} must be a dense channels_last [N, C, H, W] tensor")
+    return t
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _bn_forward_train(fn, entry, x, weight, bias, running_mean, running_var, factor, eps):
+    x16 = entry.endswith("_x16")
+    x = _nhwc(x, "x", x16, where="" if x16 else fn + ": ")
     c = x.shape[1]
     m = x.numel() // max(c, 1)
     vecs = [None if t is None else _require_cuda_f32(t.detach(), "a per-channel vector")
             for t in (weight, bias, running_mean, running_var)]
     if any(t is not None and (t.numel() != c or t.device != x.device) for t in vecs):
-        raise ValueError("bn_forward_train: per-channel vectors must have C elements on x's device")
+        raise ValueError(f"{fn}: per-channel vectors must have C elements on x's device")
     if any(t is not None and t.data_ptr() != o.data_ptr() for t, o in zip(vecs[2:], (running_mean, running_var))):
-        raise ValueError("bn_forward_train: the running statistics must be contiguous (they are updated in place)")
+        raise ValueError(f"{fn}: the running statistics must be contiguous (they are updated in place)")
     L = _lib.lib()
     y = torch.empty_like(x)
-    mean, invstd = torch.empty(c, device=x.device), torch.empty(c, device=x.device)
-    nb = L.mhaq_fq_bn_fwd_workspace_bytes(m, c)
+    mean, invstd = (torch.empty(c, dtype=torch.float32, device=x.device) for _ in range(2))
+    nb = getattr(L, entry + "_workspace_bytes")(m, c)
     ws = _workspace(max(nb, 16), x.device)
-    ptr = lambda t: None if t is None else t.data_ptr()
-    _lib.check(L.mhaq_fq_bn_fwd(x.data_ptr(), *map(ptr, vecs[:2]), y.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                                *map(ptr, vecs[2:]), float(factor), float(eps), m, c, ws.data_ptr(), nb, _stream()),
-               "mhaq_fq_bn_fwd")
+    dtype = (_X16[x.dtype],) if x16 else ()
+    _lib.check(getattr(L, entry)(x.data_ptr(), *map(_ptr, vecs[:2]), y.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
+                                 *map(_ptr, vecs[2:]), float(factor), float(eps), m, c, *dtype, ws.data_ptr(), nb, _stream()),
+               entry)
     return y, mean, invstd
+
+
+@_on_device
+def bn_forward_train(x, weight=None, bias=None, running_mean=None, running_var=None, factor=0.1, eps=1e-5):
+    """Training-mode BatchNorm forward of a dense float32 channels_last [N, C, H, W] tensor on mhaq_fq_bn_fwd (no autograd:
+    the compiled node bn_train(hip_forward=True) is the differentiable form).  Returns (y, save_mean, save_invstd); the running
+    statistics, both given or both None, are updated in place with `factor`."""
+    return _bn_forward_train("bn_forward_train", "mhaq_fq_bn_fwd", x, weight, bias, running_mean, running_var, factor, eps)
+
+
+@_on_device
+def bn_forward_train_x16(x, weight=None, bias=None, running_mean=None, running_var=None, factor=0.1, eps=1e-5):
+    """bn_forward_train on a dense channels_last bfloat16 / float16 tensor (mhaq_fq_bn_fwd_x16; no autograd: the compiled node
+    bn_train(x16=True, hip_forward_x16=True) is the differentiable form): the fp32 contract on the upcast input, y rounded
+    once into x's dtype.  The per-channel vectors and the returned statistics are float32."""
+    return _bn_forward_train("bn_forward_train_x16", "mhaq_fq_bn_fwd_x16", x, weight, bias, running_mean, running_var, factor,
+                             eps)
 
 
 # modes of bn_infer_act (include/mhaq_fq.h)
 BN_RELU, BN_ADD_RELU, BN2_ADD_RELU = 0, 1, 2
-
-
-def _nhwc_f32(t, name):
-    t = _require_cuda_f32(t.detach(), name, any_dense_layout=True)
-    if t.dim() != 4 or not t.is_contiguous(memory_format=torch.channels_last):
-        raise ValueError(f"{name} must be a dense channels_last [N, C, H, W] tensor")
-    return t
 
 
 @_on_device
@@ -398,112 +424,62 @@ def bn_infer_consts(running_mean, running_var, weight=None, bias=None, eps=1e-5,
     return out
 
 
-@_on_device
-def bn_infer_act(x, consts, mode=BN_RELU, x2=None, consts2=None, residual=None):
-    """relu(bn(x)), relu(bn(x) + residual) or relu(bn(x) + bn2(x2)) of dense float32 channels_last tensors in one launch
-    (mhaq_fq_bn_infer_act; no autograd), with the slabs of bn_infer_consts."""
-    x = _nhwc_f32(x, "x")
+def _bn_infer_act(fn, entry, x, consts, mode, x2, consts2, residual):
+    x16 = entry.endswith("_x16")
+    x = _nhwc(x, "x", x16)
     c = x.shape[1]
-    others = [None if t is None else _nhwc_f32(t, name) for t, name in ((x2, "x2"), (residual, "residual"))]
-    if any(t is not None and (t.shape != x.shape or t.device != x.device) for t in others):
-        raise ValueError("bn_infer_act: x2 and residual must have x's shape and device")
+    others = [None if t is None else _nhwc(t, name, x16) for t, name in ((x2, "x2"), (residual, "residual"))]
+    if any(t is not None and (t.shape != x.shape or t.device != x.device or t.dtype != x.dtype) for t in others):
+        raise ValueError(f"{fn}: x2 and residual must have x's shape{', dtype' if x16 else ''} and device")
     slabs = [None if k is None else _require_cuda_f32(k.detach(), "a constant slab") for k in (consts, consts2)]
     if any(k is not None and (k.numel() != 3 * c or k.device != x.device) for k in slabs):
-        raise ValueError("bn_infer_act: a constant slab must be [3, C] on x's device")
+        raise ValueError(f"{fn}: a constant slab must be [3, C] on x's device")
     y = torch.empty_like(x)
-    ptr = lambda t: None if t is None else t.data_ptr()
-    _lib.check(_lib.lib().mhaq_fq_bn_infer_act(x.data_ptr(), ptr(slabs[0]), ptr(others[0]), ptr(slabs[1]), ptr(others[1]),
-                                               y.data_ptr(), x.numel() // max(c, 1), c, int(mode), _stream()),
-               "mhaq_fq_bn_infer_act")
+    dtype = (_X16[x.dtype],) if x16 else ()
+    _lib.check(getattr(_lib.lib(), entry)(x.data_ptr(), _ptr(slabs[0]), _ptr(others[0]), _ptr(slabs[1]), _ptr(others[1]),
+                                          y.data_ptr(), x.numel() // max(c, 1), c, int(mode), *dtype, _stream()), entry)
     return y
 
 
 @_on_device
-def bn_relu_pool(x, consts):
-    """max_pool2d(relu(bn(x)), 3, 2, 1) of a dense float32 channels_last tensor in one launch (mhaq_fq_bn_relu_pool3s2; no
-    autograd), the BatchNorm output never stored."""
-    x = _nhwc_f32(x, "x")
-    n, c, h, w = x.shape
-    k = _require_cuda_f32(consts.detach(), "the constant slab")
-    if k.numel() != 3 * c or k.device != x.device:
-        raise ValueError("bn_relu_pool: the constant slab must be [3, C] on x's device")
-    p = torch.empty((n, c, (h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=x.dtype, device=x.device,
-                    memory_format=torch.channels_last)
-    _lib.check(_lib.lib().mhaq_fq_bn_relu_pool3s2(x.data_ptr(), k.data_ptr(), p.data_ptr(), n, h, w, c, _stream()),
-               "mhaq_fq_bn_relu_pool3s2")
-    return p
-
-
-def _nhwc_x16(t, name):
-    t = t.detach()
-    if not t.is_cuda:
-        raise _lib.MhaqFqError(f"{name} is on {t.device}: the kernels run only on an MI355X (no CPU fallback by design)")
-    if t.dtype not in _X16:
-        raise TypeError(f"{name} must be bfloat16 or float16, got {t.dtype}")
-    if t.dim() != 4 or not t.is_contiguous(memory_format=torch.channels_last):
-        raise ValueError(f"{name} must be a dense channels_last [N, C, H, W] tensor")
-    return t
-
-
-@_on_device
-def bn_forward_train_x16(x, weight=None, bias=None, running_mean=None, running_var=None, factor=0.1, eps=1e-5):
-    """bn_forward_train on a dense channels_last bfloat16 / float16 tensor (mhaq_fq_bn_fwd_x16; no autograd: the compiled node
-    bn_train(x16=True, hip_forward_x16=True) is the differentiable form): the fp32 contract on the upcast input, y rounded
-    once into x's dtype.  The per-channel vectors and the returned statistics are float32."""
-    x = _nhwc_x16(x, "x")
-    c = x.shape[1]
-    m = x.numel() // max(c, 1)
-    vecs = [None if t is None else _require_cuda_f32(t.detach(), "a per-channel vector")
-            for t in (weight, bias, running_mean, running_var)]
-    if any(t is not None and (t.numel() != c or t.device != x.device) for t in vecs):
-        raise ValueError("bn_forward_train_x16: per-channel vectors must have C elements on x's device")
-    if any(t is not None and t.data_ptr() != o.data_ptr() for t, o in zip(vecs[2:], (running_mean, running_var))):
-        raise ValueError("bn_forward_train_x16: the running statistics must be contiguous (they are updated in place)")
-    L = _lib.lib()
-    y = torch.empty_like(x)
-    mean, invstd = (torch.empty(c, dtype=torch.float32, device=x.device) for _ in range(2))
-    nb = L.mhaq_fq_bn_fwd_x16_workspace_bytes(m, c)
-    ws = _workspace(max(nb, 16), x.device)
-    ptr = lambda t: None if t is None else t.data_ptr()
-    _lib.check(L.mhaq_fq_bn_fwd_x16(x.data_ptr(), *map(ptr, vecs[:2]), y.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                                    *map(ptr, vecs[2:]), float(factor), float(eps), m, c, _X16[x.dtype], ws.data_ptr(), nb,
-                                    _stream()), "mhaq_fq_bn_fwd_x16")
-    return y, mean, invstd
+def bn_infer_act(x, consts, mode=BN_RELU, x2=None, consts2=None, residual=None):
+    """relu(bn(x)), relu(bn(x) + residual) or relu(bn(x) + bn2(x2)) of dense float32 channels_last tensors in one launch
+    (mhaq_fq_bn_infer_act; no autograd), with the slabs of bn_infer_consts."""
+    return _bn_infer_act("bn_infer_act", "mhaq_fq_bn_infer_act", x, consts, mode, x2, consts2, residual)
 
 
 @_on_device
 def bn_infer_act_x16(x, consts, mode=BN_RELU, x2=None, consts2=None, residual=None):
     """bn_infer_act on dense channels_last bfloat16 / float16 tensors (mhaq_fq_bn_infer_act_x16; no autograd): the fp32
     arithmetic on the upcast inputs with the float32 slabs of bn_infer_consts, rounded once into a y of x's dtype."""
-    x = _nhwc_x16(x, "x")
-    c = x.shape[1]
-    others = [None if t is None else _nhwc_x16(t, name) for t, name in ((x2, "x2"), (residual, "residual"))]
-    if any(t is not None and (t.shape != x.shape or t.device != x.device or t.dtype != x.dtype) for t in others):
-        raise ValueError("bn_infer_act_x16: x2 and residual must have x's shape, dtype and device")
-    slabs = [None if k is None else _require_cuda_f32(k.detach(), "a constant slab") for k in (consts, consts2)]
-    if any(k is not None and (k.numel() != 3 * c or k.device != x.device) for k in slabs):
-        raise ValueError("bn_infer_act_x16: a constant slab must be [3, C] on x's device")
-    y = torch.empty_like(x)
-    ptr = lambda t: None if t is None else t.data_ptr()
-    _lib.check(_lib.lib().mhaq_fq_bn_infer_act_x16(x.data_ptr(), ptr(slabs[0]), ptr(others[0]), ptr(slabs[1]), ptr(others[1]),
-                                                   y.data_ptr(), x.numel() // max(c, 1), c, int(mode), _X16[x.dtype],
-                                                   _stream()), "mhaq_fq_bn_infer_act_x16")
-    return y
+    return _bn_infer_act("bn_infer_act_x16", "mhaq_fq_bn_infer_act_x16", x, consts, mode, x2, consts2, residual)
+
+
+def _bn_relu_pool(fn, entry, x, consts):
+    x16 = entry.endswith("_x16")
+    x = _nhwc(x, "x", x16)
+    n, c, h, w = x.shape
+    k = _require_cuda_f32(consts.detach(), "the constant slab")
+    if k.numel() != 3 * c or k.device != x.device:
+        raise ValueError(f"{fn}: the constant slab must be [3, C] on x's device")
+    p = torch.empty((n, c, (h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=x.dtype, device=x.device,
+                    memory_format=torch.channels_last)
+    dtype = (_X16[x.dtype],) if x16 else ()
+    _lib.check(getattr(_lib.lib(), entry)(x.data_ptr(), k.data_ptr(), p.data_ptr(), n, h, w, c, *dtype, _stream()), entry)
+    return p
+
+
+@_on_device
+def bn_relu_pool(x, consts):
+    """max_pool2d(relu(bn(x)), 3, 2, 1) of a dense float32 channels_last tensor in one launch (mhaq_fq_bn_relu_pool3s2; no
+    autograd), the BatchNorm output never stored."""
+    return _bn_relu_pool("bn_relu_pool", "mhaq_fq_bn_relu_pool3s2", x, consts)
 
 
 @_on_device
 def bn_relu_pool_x16(x, consts):
     """bn_relu_pool on a dense channels_last bfloat16 / float16 tensor (mhaq_fq_bn_relu_pool3s2_x16; no autograd)."""
-    x = _nhwc_x16(x, "x")
-    n, c, h, w = x.shape
-    k = _require_cuda_f32(consts.detach(), "the constant slab")
-    if k.numel() != 3 * c or k.device != x.device:
-        raise ValueError("bn_relu_pool_x16: the constant slab must be [3, C] on x's device")
-    p = torch.empty((n, c, (h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=x.dtype, device=x.device,
-                    memory_format=torch.channels_last)
-    _lib.check(_lib.lib().mhaq_fq_bn_relu_pool3s2_x16(x.data_ptr(), k.data_ptr(), p.data_ptr(), n, h, w, c, _X16[x.dtype],
-                                                      _stream()), "mhaq_fq_bn_relu_pool3s2_x16")
-    return p
+    return _bn_relu_pool("bn_relu_pool_x16", "mhaq_fq_bn_relu_pool3s2_x16", x, consts)
 
 
 # ----------------------------------------------------------------------------- per-tensor op
