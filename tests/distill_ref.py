@@ -18,8 +18,11 @@ NAMES = {CE: "Cross-Entropy", SCE: "Symmetrical Cross-Entropy", KL: "KL", SKL: "
          HELLINGER: "Hellinger"}
 ZERO_AT_EQUAL = [KL, SKL, JSD, HELLINGER]         # loss and gradient vanish where target == input
 
-# the shapes of the GPU tests: register path (1001: unaligned row bases), its edge at 4096 / 4097, a re-walked row
-SHAPES = [(3, 1), (1, 2), (5, 37), (16, 1001), (250, 1000), (2, 4096), (4, 4097), (2, 10007)]
+# the shapes of the GPU tests: register path (1001: unaligned row bases), its edge at 4096 / 4097, a re-walked row; more row
+# partials than the finalize has threads (257: one of them, 600: a third trip); 1028 and 4092 columns: the first 4-element group
+# of a thread's second trip over the row and the last group of its fourth
+SHAPES = [(3, 1), (1, 2), (5, 37), (16, 1001), (250, 1000), (2, 4096), (4, 4097), (2, 10007), (257, 4), (600, 3), (3, 1028),
+          (2, 4092)]
 CPU_SHAPES = [(1, 2), (5, 37), (16, 1001)]
 MARGIN = 4.0                                     # the issue's factor on the framework chain's own error
 

@@ -3,7 +3,8 @@ through mhaq_amd.loss.FusedDistillLoss, against float64 autograd on the CPU thro
 (tests/distill_ref.py).  The bar is the framework's own float32 chain on the device, never the kernel:
     |L - L64| <= 4 |L_torch - L64| + 8 ulp32(L64),   max|gx - g64| <= 4 max|g_torch - g64| + 8 2^-24 max|g64|.
 Shapes: 3x1, 1x2, 5x37, 16x1001 (odd: unaligned row bases) and 250x1000 in registers, 2x4096 / 4x4097 at the edge of the
-register path, 2x10007 re-walked."""
+register path, 2x10007 re-walked; 257x4 and 600x3 give the finalize more row partials than it has threads, 3x1028 and 2x4092
+end in the first group of a thread's second trip over the row and in the last group of its fourth."""
 import ctypes
 import functools
 
@@ -18,7 +19,7 @@ BAND = 64                                  # elements of ones planted before and
 G_UP = 0.375                               # a non-trivial upstream gradient
 DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 SCALES = {(3, 1): 2.0, (1, 2): 1.0, (5, 37): 8.0, (16, 1001): 4.0, (250, 1000): 4.0, (2, 4096): 2.0, (4, 4097): 8.0,
-          (2, 10007): 1.0}
+          (2, 10007): 1.0, (257, 4): 4.0, (600, 3): 2.0, (3, 1028): 4.0, (2, 4092): 2.0}
 ids_shape = lambda s: "%dx%d" % s          # noqa: E731
 ids_kind = lambda k: R.NAMES[k]            # noqa: E731
 

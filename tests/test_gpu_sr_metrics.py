@@ -53,19 +53,35 @@ class Banded:
         return bool((self.buf[:BAND] == 1).all()) and bool((self.buf[BAND + self.n:] == 1).all())
 
 
-def capi(sr, hr, sr_div=1.0, luminance=True, pool=None):
-    """-> (psnr[N], ssim[N], l1[1], mean[2], flags int); asserts that nothing around the outputs and the workspace was written."""
+def placed(t, off):
+    """The values of t, `off` elements into a larger 256-byte-aligned allocation whose other elements are NaN."""
+    if not off:
+        return t
+    buf = torch.full((off + t.numel() + BAND,), float("nan"), dtype=t.dtype, device=t.device)
+    assert buf.data_ptr() % 256 == 0
+    view = buf[off:off + t.numel()].view(t.shape)
+    view.copy_(t)
+    assert view.is_contiguous() and view.data_ptr() == buf.data_ptr() + off * t.element_size()
+    return view
+
+
+def capi(sr, hr, sr_div=1.0, luminance=True, pool=None, ws_fill=-7, flags_init=0, sr_off=0, hr_off=0):
+    """-> (psnr[N], ssim[N], l1[1], mean[2], flags int); asserts that nothing around the outputs and the workspace was written.
+    ws_fill: what the workspace holds before the call; flags_init: the flag word before it; sr_off / hr_off: the input starts
+    that many elements past a 256-byte boundary."""
     from mhaq_amd import _lib
     lib = _lib.lib()
     assert sr.is_contiguous() and hr.is_contiguous()
     n, c, h, w = sr.shape
+    sr, hr = placed(sr, sr_off), placed(hr, hr_off)
     pool = R.pool_factor(h, w) if pool is None else pool
     wsb = lib.mhaq_fq_sr_metrics_workspace_bytes(n, c, h, w, int(luminance), pool)
     assert wsb > 0 and wsb % 8 == 0
-    ws = Banded(wsb // 8, torch.float64)
+    ws = Banded(wsb // 8, torch.float64, fill=ws_fill)
     psnr, ssim = Banded(n + (n & 1), torch.float32), Banded(n + (n & 1), torch.float32)
     l1, mean = Banded(2, torch.float32), Banded(2, torch.float32)
     flags = Banded(2, torch.int32, fill=0)
+    flags.view[0] = flags_init
     _lib.check(lib.mhaq_fq_sr_metrics(_ptr(sr), DT[sr.dtype], _ptr(hr), DT[hr.dtype], n, c, h, w, float(sr_div),
                                       int(luminance), pool, _ptr(psnr.view), _ptr(ssim.view), _ptr(l1.view), _ptr(mean.view),
                                       _ptr(flags.view), _ptr(ws.view), wsb, _stream()), "mhaq_fq_sr_metrics")

@@ -1,6 +1,7 @@
 """CPU: everything about the fused super-resolution metrics (mhaq_fq_sr_metrics, mhaq_amd/sr_metrics.py) that needs no GPU --
 the symbols, every argument error (returned before any launch: the pointers here are fake), the workspace query, the pool
-factor, the float64 restatement of tests/sr_metrics_ref.py against values derived independently, the validation meter
+factor, the float64 restatement of tests/sr_metrics_ref.py against values derived independently and against direct64 (the
+definition written out a second time), the geometry that the shapes of the GPU edge suite reach, the validation meter
 and the QATConfig defaults.  The kernels are held to the restatement on the device by tests/test_gpu_sr_metrics.py."""
 import ctypes
 import dataclasses
@@ -104,6 +105,48 @@ def test_workspace_covers_the_pooled_planes_and_the_partials_and_grows_with_ever
     assert ws(2, 3, 96, 96, 0, 1) > ws(2, 3, 96, 96, 1, 1)                        # three planes against one
 
 
+def sr_geometry_replica(n, c, h, w, lum, f):
+    """sr_geometry of csrc/sr_metrics.hip in Python: what a shape of the GPU edge suite reaches, and the workspace it needs."""
+    p = 1 if lum else c
+    unit = 8 * f // math.gcd(8, f)
+    cap = 2048 if f == 1 else min(2048, 12288 // (2 * p * f))
+    chunk = min(cap // unit, -(-w // unit)) * unit
+    nchunk = -(-w // chunk)
+    groups = -(-h // f)
+    band = max(1, min(groups, -(-2048 // (f * min(chunk, w)))))
+    nband = -(-groups // band)
+    hp, wp = h // f, w // f
+    tx, ty = -(-(wp - 10) // 32), -(-(hp - 10) // 32)
+    nblk1, nblk2 = nband * nchunk, p * tx * ty
+    plane = (n * p * hp * wp * 4 + 15) & ~15
+    total = 2 * plane + n * nblk1 * 16 + n * nblk2 * 8 + n * 24 + ((n * nblk1 * 4 + 7) & ~7)
+    return dict(unit=unit, chunk=chunk, nchunk=nchunk, last=w - (nchunk - 1) * chunk, band=band, nband=nband,
+                lds=0 if f == 1 else 2 * p * f * chunk * 4, tx=tx, ty=ty, total=total)
+
+
+def test_the_edge_suites_shapes_reach_the_geometry_they_are_there_for():
+    """(unit, chunk, chunks, width of the last chunk, band, bands, bytes of LDS) per shape of tests/test_gpu_sr_metrics_edges.py,
+    and the library's workspace query agrees with the replica (it counts the workgroups of both launches)."""
+    from tests.test_gpu_sr_metrics_edges import POOLED
+    want = {(57, 1257): (40, 1200, 2, 57, 1, 12, 48000), (22, 2071): (8, 2048, 2, 23, 1, 11, 32768),
+            (22, 2072): (8, 2048, 2, 24, 1, 11, 32768), (22, 2049): (8, 2048, 2, 1, 1, 11, 32768),
+            (22, 2050): (8, 2048, 2, 2, 1, 11, 32768), (35, 707): (24, 672, 2, 35, 2, 6, 48384),
+            (44, 556): (8, 512, 2, 44, 1, 11, 49152), (55, 57): (40, 80, 1, 57, 8, 2, 3200),
+            (77, 83): (56, 112, 1, 83, 4, 3, 6272), (33, 34): (24, 48, 1, 34, 11, 1, 1152),
+            (300, 11): (8, 16, 1, 11, 187, 2, 0)}
+    ws = _lib.lib().mhaq_fq_sr_metrics_workspace_bytes
+    assert len(POOLED) == len(want)
+    for (n, c, h, w, lum, f) in POOLED:
+        g = sr_geometry_replica(n, c, h, w, lum, f)
+        assert (g["unit"], g["chunk"], g["nchunk"], g["last"], g["band"], g["nband"], g["lds"]) == want[(h, w)], (h, w, g)
+        assert ws(n, c, h, w, int(lum), f) == g["total"], (h, w)
+        assert g["lds"] <= 49152
+    assert sr_geometry_replica(1, 3, 300, 11, True, 1)["ty"] == 10 and sr_geometry_replica(1, 3, 300, 11, True, 1)["tx"] == 1
+    # the workload this stands for: a DIV2K validation image on luminance
+    g = sr_geometry_replica(1, 3, 1356, 2040, True, 5)
+    assert (g["chunk"], g["nchunk"], g["last"]) == (1200, 2, 840) and ws(1, 3, 1356, 2040, 1, 5) == g["total"]
+
+
 def test_pool_factor_rounds_halves_to_even():
     from mhaq_amd.sr_metrics import ssim_pool_factor
     want = {128: 1, 383: 1, 384: 2, 639: 2, 640: 2, 641: 3, 1356: 5}
@@ -140,6 +183,54 @@ def test_restatement_identical_images_and_constant_planes():
     p1, s1, _ = R.restate64(sr, hr)
     p2, s2, _ = R.restate64(sr2, hr)
     assert float(s1) == float(s2) and float(p2) < float(p1)
+
+
+# (n, c, h, w, luminance, pool, noise, flat, sr_div)
+DIRECT_CASES = [(1, 3, 11, 11, True, None, 0.05, None, 1.0), (2, 3, 24, 37, False, None, 0.05, None, 1.0),
+                (2, 1, 24, 37, False, None, 0.05, None, 1.0), (1, 3, 57, 61, True, 5, 0.05, None, 1.0),
+                (1, 3, 35, 38, False, 3, 0.05, None, 1.0), (1, 3, 64, 64, True, None, 0.01, 0.5, 1.0),
+                (2, 3, 24, 37, True, None, 0.05, None, 255.0)]
+
+
+@pytest.mark.parametrize("case", DIRECT_CASES, ids=lambda c: "%dx%dx%dx%d-%s-pool%s-div%g%s" % (
+    c[0], c[1], c[2], c[3], "lum" if c[4] else "planes", c[5], c[8], "-flat" if c[7] is not None else ""))
+def test_direct64_written_from_the_header_agrees_with_the_restatement(case):
+    """Two float64 statements of include/mhaq_fq.h that share no code (conv2d / avg_pool2d in torch against sliding windows,
+    block means and an einsum in numpy).  Both are fp64 sums of at most 121 terms of magnitude at most 1, so they differ near
+    1e-14; the bounds leave four orders above that and stay three orders below the smallest term of the fp32 bar,
+    8 ulp32(1) = 9.5e-7."""
+    n, c, h, w, lum, pool, noise, flat, div = case
+    sr, hr = R.images(n, c, h, w, noise=noise, seed=7 * h + w + c, flat=flat)
+    if div != 1.0:                                        # a de-normalised prediction with values the clamp meets
+        sr = sr * div
+        sr[0, :, 3, 5] = -0.3 * div
+        sr[1, :, 7, 30] = 1.7 * div
+        sr[1, 1, 20, 2] = 1.0001 * div
+    psnr, ssim, l1 = R.restate64(sr, hr, sr_div=div, luminance=lum, pool=pool)
+    dp, ds, dl = R.direct64(sr, hr, sr_div=div, luminance=lum, pool=pool)
+    assert dp.shape == (n,) and ds.shape == (n,) and dp.dtype == ds.dtype == "float64"
+    print("direct64 - restate64:", [float(abs(dp[i] - float(psnr[i]))) for i in range(n)],
+          [float(abs(ds[i] - float(ssim[i]))) for i in range(n)], abs(float(dl) - float(l1)))
+    for i in range(n):
+        assert abs(dp[i] - float(psnr[i])) <= 1e-9, (i, dp[i], float(psnr[i]))
+        assert abs(ds[i] - float(ssim[i])) <= 1e-10, (i, ds[i], float(ssim[i]))
+    assert abs(float(dl) - float(l1)) <= 1e-10
+    assert 0.0 < float(ds.min()) < 1.0 and float(dp.max()) < 80.0                 # not the degenerate equal-images values
+
+
+def test_direct64_keeps_a_nan_through_the_clamp_and_takes_the_reference_pool_by_default():
+    sr, hr = R.images(2, 3, 24, 37, seed=2)
+    bad = sr.clone()
+    bad[1, 0, 4, 4] = float("nan")
+    dp, ds, dl = R.direct64(bad, hr)
+    assert math.isnan(dp[1]) and math.isnan(ds[1]) and math.isnan(dl) and math.isfinite(dp[0]) and math.isfinite(ds[0])
+    clean = R.direct64(sr, hr)
+    assert dp[0] == clean[0][0] and ds[0] == clean[1][0]
+    # pool = None is the factor of the image size; an explicit factor is taken as given
+    sr, hr = R.images(1, 3, 384, 390, seed=4)
+    assert R.direct64(sr, hr)[1][0] == R.direct64(sr, hr, pool=2)[1][0] != R.direct64(sr, hr, pool=1)[1][0]
+    assert float(R.restate64(sr, hr)[1]) == float(R.restate64(sr, hr, pool=2)[1]) != float(R.restate64(sr, hr, pool=1)[1])
+    assert float(R.chain32(sr, hr)[1]) == float(R.chain32(sr, hr, pool=2)[1])
 
 
 def test_chain32_is_the_restatement_in_float32():
