@@ -616,6 +616,52 @@ int mhaq_fq_distill_loss_bwd(const float* gunit, const float* g /* [1], device *
                              void* gx, int gx_dtype, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Classification head over one logit tensor and hard labels: the mean cross-entropy, the per-row nll, the rank of the
+ * label's logit with the top-1 / top-k counts, and optionally the gradient, from one read of the logits in two launches.
+ * The backward is mhaq_fq_distill_loss_bwd above (gx = RNE(gunit * g[0])).  Additive to ABI v4 -- MHAQ_FQ_ABI_VERSION stays
+ * 4; a caller discovers these entry points by symbol.
+ *   x             logits, dense row-major [rows][cols]; MHAQ_FQ_DT_F32, MHAQ_FQ_DT_BF16 or MHAQ_FQ_DT_F16, aligned to its
+ *                 element size.  16-bit elements are converted up exactly; everything else is fp32 arithmetic (no
+ *                 contraction, no approximate transcendentals), reduced in fp64.
+ *   target        [rows] int64.  A row is VALID when target != ignore_index and 0 <= target < cols; V = number of valid rows.
+ *                 A target that is neither ignore_index nor in range sets bit 2 of `flags` and its row is treated as ignored:
+ *                 no address is ever formed from it (the framework's loss aborts the process with a device-side assert there).
+ *   topk          >= 1; with topk >= cols every valid row counts
+ *   loss          [1] fp32: (sum of nll over the valid rows) / V, summed in fp64 in a fixed order and rounded once; NaN for V = 0
+ *   acc           [2] fp32: float(counts[1]) / float(V) and float(counts[2]) / float(V), one IEEE division each; 0 for V = 0
+ *   counts        [3] int64: V, #{valid rows with rank == 0}, #{valid rows with rank < topk}
+ *   nll           NULL, or [rows] fp32 (0 on rows that are not valid)
+ *   rank          NULL, or [rows] int32 (cols on rows that are not valid)
+ *   gunit         NULL, or [rows][cols] fp32: d loss / d x for an upstream gradient of 1; every element is written
+ *   flags         [1] device word, WRITTEN by the call (not OR-ed into): bit 1 (value 2) = the nll of a valid row is not
+ *                 finite, bit 2 (value 4) = a target out of range
+ *   workspace     mhaq_fq_cls_head_workspace_bytes(rows) bytes, 8-byte aligned: per row an fp64 partial, the rank, a status
+ * Per valid row with label y:  m = max_c x_c,  S = sum_c exp(x_c - m) (fp64 sum, rounded to fp32),
+ *   nll = log S - (x_y - m)   (= lse - x_y with lse = m + log S, in the framework's order of operations),
+ *   gunit_j = (exp(x_j - m) / S - [j == y]) / V;  gunit is 0 on every other row.
+ * rank = the label's position in torch.sort(x, descending=True, stable=True):
+ *   rank = #{c : x_c > x_y} + #{c < y : x_c == x_y},  where a NaN sorts above +inf and equals a NaN, and +0 == -0.
+ * Hence argmax(x) == y exactly when rank == 0, ties and NaN rows included.
+ * There is no other screening: a NaN or infinite logit spoils its own row's nll (and the loss) by plain IEEE arithmetic and
+ * leaves the other rows' nll, rank and gunit bits alone.  The same inputs give the same bits at every call: no atomics,
+ * fixed summation orders, no host synchronisation, no data-dependent host scalar; stream-ordered, capture-safe, stateless.
+ * Launch one, one workgroup per row (rows of up to 4096 columns are held in registers, longer ones are walked once per
+ * pass; with a gunit, each valid row's workgroup also counts V over `target` itself, rows * 8 bytes out of L2); launch two,
+ * one workgroup, adds the rows up.
+ * Argument errors are returned before any launch, in this order: NULL x / target / loss / acc / counts / flags / workspace,
+ * rows or cols < 1, topk < 1, an unknown dtype (MHAQ_FQ_EINVAL); a short workspace (MHAQ_FQ_EWORKSPACE); x not aligned to
+ * its element size, target / counts / workspace not 8-byte or another pointer not 4-byte aligned (MHAQ_FQ_EALIGN); rows or
+ * cols > 2^31 - 1 (MHAQ_FQ_EUNSUPPORTED).
+ * ---------------------------------------------------------------------- */
+size_t mhaq_fq_cls_head_workspace_bytes(int64_t rows);
+int mhaq_fq_cls_head_fwd(const void* x, int x_dtype, const int64_t* target, int64_t rows, int64_t cols,
+                         int64_t ignore_index, int topk,
+                         float* loss /* [1] */, float* acc /* [2] */, int64_t* counts /* [3] */,
+                         float* nll /* [rows], nullable */, int32_t* rank /* [rows], nullable */,
+                         float* gunit /* [rows*cols], nullable */, uint32_t* flags /* [1] */,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Super-resolution validation metrics: per-image PSNR and SSIM of the clamped prediction against the target and the L1
  * criterion on the unclamped one, in three launches.  Additive to ABI v4 -- MHAQ_FQ_ABI_VERSION stays 4; a caller discovers
  * these entry points by symbol.

@@ -91,6 +91,10 @@ SIGNATURES = {
     "mhaq_fq_distill_loss_workspace_bytes": (_sz, [_i64]),
     "mhaq_fq_distill_loss_fwd": (_int, [_p, _int, _p, _int, _i64, _i64, _int, _p, _p, _p, _sz, _p]),
     "mhaq_fq_distill_loss_bwd": (_int, [_p, _p, _p, _int, _i64, _p]),
+    # classification head: x, x_dtype, target, rows, cols, ignore_index, topk, loss, acc, counts, nll, rank, gunit, flags,
+    # workspace (additive, ABI v4 kept)
+    "mhaq_fq_cls_head_workspace_bytes": (_sz, [_i64]),
+    "mhaq_fq_cls_head_fwd": (_int, [_p, _int, _p, _i64, _i64, _i64, _int, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     # super-resolution validation metrics: sr, sr_dtype, hr, hr_dtype, n, c, h, w, sr_div, to_luminance, pool, psnr, ssim,
     # l1, mean, flags, workspace (additive, ABI v4 kept)
     "mhaq_fq_sr_metrics_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _int, _int]),

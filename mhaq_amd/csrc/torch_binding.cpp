@@ -63,7 +63,8 @@ namespace {
   X(mhaq_fq_bn_infer_consts) X(mhaq_fq_bn_infer_act) X(mhaq_fq_bn_relu_pool3s2)                                     \
   X(mhaq_fq_bn_infer_act_x16) X(mhaq_fq_bn_relu_pool3s2_x16)                                                        \
   X(mhaq_fq_radam_chunk_elements) X(mhaq_fq_radam_step)                                                          \
-  X(mhaq_fq_distill_loss_workspace_bytes) X(mhaq_fq_distill_loss_fwd) X(mhaq_fq_distill_loss_bwd)
+  X(mhaq_fq_distill_loss_workspace_bytes) X(mhaq_fq_distill_loss_fwd) X(mhaq_fq_distill_loss_bwd)             \
+  X(mhaq_fq_cls_head_workspace_bytes) X(mhaq_fq_cls_head_fwd)
 
 struct Api {
 #define X(n) decltype(&::n) n = nullptr;
@@ -1828,6 +1829,65 @@ Tensor distill_loss(const Tensor& x, const Tensor& t, int64_t kind) {
   return DistillLossFn::apply(x, t, kind, x.requires_grad() && at::GradMode::is_enabled());
 }
 
+// ------------------------------------------------------------------------------------------------ classification head
+// The hard-label cross-entropy of a training step (mhaq_amd/loss.py: FusedCrossEntropy): mhaq_fq_cls_head_fwd -- two launches
+// -- forward, mhaq_fq_distill_loss_bwd -- one -- backward.  Returns {loss, flags}: the flag word (bit 2 = a label out of
+// range) stays on the device for whoever wants to read it; gunit is allocated only where x takes a gradient.
+std::atomic<int64_t> g_cls_head_launches{0};   // kernel launches of this node so far: 2 forward, 1 backward
+
+class ClsHeadFn : public torch::autograd::Function<ClsHeadFn> {
+ public:
+  static variable_list forward(AutogradContext* ctx, const Tensor& x, const Tensor& target, int64_t ignore_index,
+                               bool need_grad) {
+    const int64_t rows = x.size(0), cols = x.size(1);
+    Tensor loss = at::empty({}, x.options().dtype(at::kFloat));
+    Tensor flags = at::empty({1}, x.options().dtype(at::kInt));
+    Tensor aux = at::empty({4}, x.options().dtype(at::kLong));        // counts [3], then acc [2] in the fourth word
+    Tensor ws = at::empty({(int64_t)A.mhaq_fq_cls_head_workspace_bytes(rows)}, x.options().dtype(at::kByte));
+    Tensor gunit;
+    if (need_grad) gunit = at::empty({rows, cols}, x.options().dtype(at::kFloat));
+    int64_t* counts = static_cast<int64_t*>(aux.mutable_data_ptr());
+    check(A.mhaq_fq_cls_head_fwd(x.const_data_ptr(), distill_dtype(x), static_cast<const int64_t*>(target.const_data_ptr()),
+                                 rows, cols, ignore_index, 1, fptr_mut(loss), reinterpret_cast<float*>(counts + 3), counts,
+                                 nullptr, nullptr, need_grad ? fptr_mut(gunit) : nullptr,
+                                 static_cast<uint32_t*>(flags.mutable_data_ptr()), ws.mutable_data_ptr(), (size_t)ws.numel(),
+                                 cur_stream(x)),
+          "mhaq_fq_cls_head_fwd");
+    g_cls_head_launches.fetch_add(2, std::memory_order_relaxed);
+    if (need_grad) ctx->save_for_backward({gunit});
+    ctx->saved_data["dtype"] = (int64_t)distill_dtype(x);
+    ctx->mark_non_differentiable({flags});
+    return {loss, flags};
+  }
+
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    auto saved = ctx->get_saved_variables();
+    TORCH_CHECK(!saved.empty(), "cls_head_loss: the forward ran without a gradient to keep");
+    const Tensor& gunit = saved[0];
+    Tensor g = grads[0].reshape({1}).to(at::kFloat).contiguous();
+    const int dt = (int)ctx->saved_data["dtype"].toInt();
+    Tensor gx = at::empty(gunit.sizes(), gunit.options().dtype(dt == MHAQ_FQ_DT_F32    ? at::kFloat
+                                                               : dt == MHAQ_FQ_DT_BF16 ? at::kBFloat16
+                                                                                       : at::kHalf));
+    check(A.mhaq_fq_distill_loss_bwd(fptr(gunit), fptr(g), gx.mutable_data_ptr(), dt, gunit.numel(), cur_stream(gunit)),
+          "mhaq_fq_distill_loss_bwd");
+    g_cls_head_launches.fetch_add(1, std::memory_order_relaxed);
+    return {gx, Tensor(), Tensor(), Tensor()};
+  }
+};
+
+std::vector<Tensor> cls_head_loss(const Tensor& x, const Tensor& target, int64_t ignore_index) {
+  need_lib();
+  if (!x.is_cuda() || !target.is_cuda()) throw MhaqError("cls_head_loss: device tensors are required (there is no CPU path)");
+  MHAQ_ON_DEVICE_OF(x);
+  TORCH_CHECK(x.dim() == 2 && x.is_contiguous() && x.numel() > 0 && (x.scalar_type() == at::kFloat || act_dtype(x) != 0),
+              "cls_head_loss: the logits must be a non-empty contiguous [rows, cols] float32, bfloat16 or float16 tensor");
+  TORCH_CHECK(target.dim() == 1 && target.is_contiguous() && target.scalar_type() == at::kLong &&
+                  target.size(0) == x.size(0) && target.device() == x.device(),
+              "cls_head_loss: the target must be a contiguous int64 [rows] tensor on the logits' device");
+  return ClsHeadFn::apply(x, target, ignore_index, x.requires_grad() && at::GradMode::is_enabled());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1992,6 +2052,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("distill_loss", &distill_loss, py::arg("input"), py::arg("target"), py::arg("kind"));
   m.def("distill_fused_launches", []() { return g_distill_fused_launches.load(); },
         "kernel launches of mhaq_fq_distill_loss_fwd (2) / _bwd (1) so far in this process");
-  m.def("fused_radam_steps", []() { return g_fused_radam_steps.load(); },
+  m.def("cls_head_loss", &cls_head_loss, py::arg("input"), py::arg("target"), py::arg("ignore_index"));
+  m.def("cls_head_launches", []() { return g_cls_head_launches.load(); },
+        "kernel launches of the compiled classification-head node so far in this process: mhaq_fq_cls_head_fwd (2), backward (1)");
+  m.def("fused_radam_steps",[]() { return g_fused_radam_steps.load(); },
         "launches of mhaq_fq_radam_step so far (tests: the optimizer step took the HIP kernel)");
 }

@@ -7,6 +7,7 @@
   SymmetricalKL             distillation loss of the ResNet-18 configs (src/aux/loss/symm_kl_loss.py)
   FusedDistillLoss          the six softmax-family distillation losses of src/aux/loss in the HIP library
                             (mhaq_fq_distill_loss_fwd / _bwd: 2 + 1 launches)
+  FusedCrossEntropy         nn.CrossEntropyLoss() on hard labels in the HIP library (mhaq_fq_cls_head_fwd: 2 + 1 launches)
   distillation_criterion    a config's `distillation_loss` string -> module (gdnsq_quant.py: get_loss)
 
 (The torch restatement of the two PotentialLoss modules is checker code and lives in oracle/loss.py.)
@@ -119,7 +120,11 @@ ENV_SWITCH_DISTILL = "MHAQ_DISTILL_FUSED"
 def distill_fused_enabled(configured: bool = False) -> bool:
     """The trainer's switch: `configured` (QATConfig.fused_distill_loss) unless MHAQ_DISTILL_FUSED is set, which then
     decides: "1" / "true" / "on" / "yes" enable the fused loss, anything else disables it."""
-    v = os.environ.get(ENV_SWITCH_DISTILL)
+    return _env_switch(ENV_SWITCH_DISTILL, configured)
+
+
+def _env_switch(name: str, configured: bool) -> bool:
+    v = os.environ.get(name)
     if v is None or not v.strip():
         return bool(configured)
     return v.strip().lower() in ("1", "true", "on", "yes")
@@ -169,6 +174,76 @@ class FusedDistillLoss(nn.Module):
         c = input.shape[-1]
         return _ext.ext().distill_loss(input.reshape(-1, c).contiguous(), target.detach().reshape(-1, c).contiguous(),
                                        self.kind)
+
+
+# ----------------------------------------------------------------------------- fused hard-label cross-entropy
+ENV_SWITCH_CE = "MHAQ_CE_FUSED"
+ENV_SWITCH_CLS_METRICS = "MHAQ_CLS_METRICS"
+
+
+def ce_fused_enabled(configured: bool = False) -> bool:
+    """The trainer's switch: `configured` (QATConfig.fused_cross_entropy) unless MHAQ_CE_FUSED is set, which then decides
+    (as distill_fused_enabled)."""
+    return _env_switch(ENV_SWITCH_CE, configured)
+
+
+def cls_metrics_enabled(configured: bool = False) -> bool:
+    """`configured` (QATConfig.cls_metrics) unless MHAQ_CLS_METRICS is set, which then decides."""
+    return _env_switch(ENV_SWITCH_CLS_METRICS, configured)
+
+
+def is_default_cross_entropy(criterion) -> bool:
+    """True for an nn.CrossEntropyLoss -- the class itself, not a subclass -- without class weights or label smoothing
+    and with the mean reduction: what FusedCrossEntropy computes (its ignore_index may be any)."""
+    return (type(criterion) is nn.CrossEntropyLoss and criterion.weight is None and criterion.label_smoothing == 0.0
+            and criterion.reduction == "mean")
+
+
+def cls_head_launches() -> int:
+    """Kernel launches of the compiled classification-head node so far in this process: two per forward, one per backward."""
+    from . import _ext
+    return int(_ext.ext().cls_head_launches())
+
+
+class FusedCrossEntropy(nn.Module):
+    """nn.CrossEntropyLoss() with its default arguments on int64 class labels, in the HIP library: two launches forward
+    (mhaq_fq_cls_head_fwd: one workgroup per row of logits, then a one-workgroup sum), one backward
+    (mhaq_fq_distill_loss_bwd), where the framework runs log_softmax / nll_loss and their autograd mirror.  Only
+    `ignore_index` can be set: class weights, label smoothing and the other reductions are refused.
+
+    forward(input, target) takes device logits of any shape seen as [-1, C] over the last dimension (float32, bfloat16 or
+    float16) and the int64 labels of its rows, and returns a 0-dim float32 loss; the gradient has the logits' dtype.  A
+    label that is neither ignore_index nor in [0, C) does not abort the process as the framework's device assert does: its
+    row is ignored and bit 2 of `last_flags` (a device word; cls_metrics.check_cls_flags reads it) is set.  There is no CPU
+    arithmetic: a CPU tensor raises MhaqFqError."""
+
+    def __init__(self, weight=None, ignore_index: int = -100, reduction: str = "mean", label_smoothing: float = 0.0):
+        super().__init__()
+        if weight is not None:
+            raise NotImplementedError("FusedCrossEntropy: class weights are not supported")
+        if label_smoothing != 0.0:
+            raise NotImplementedError("FusedCrossEntropy: label smoothing is not supported")
+        if reduction != "mean":
+            raise NotImplementedError(f"FusedCrossEntropy: reduction {reduction!r} is not supported, only 'mean'")
+        self.ignore_index = int(ignore_index)
+        self.last_flags = None
+
+    def extra_repr(self):
+        return f"ignore_index={self.ignore_index}"
+
+    def forward(self, input, target):
+        from . import _ext
+        from ._lib import MhaqFqError
+        if not (input.is_cuda and target.is_cuda):
+            raise MhaqFqError("FusedCrossEntropy runs only as HIP kernels: input and target must be device tensors "
+                              "(no CPU fallback by design)")
+        if input.dim() < 1 or target.dtype != torch.int64 or target.numel() * input.shape[-1] != input.numel():
+            raise ValueError(f"FusedCrossEntropy: input {tuple(input.shape)} needs one int64 class label per row of its "
+                             f"last dimension, got a {target.dtype} target of shape {tuple(target.shape)}")
+        c = input.shape[-1]
+        loss, self.last_flags = _ext.ext().cls_head_loss(input.reshape(-1, c).contiguous(),
+                                                         target.detach().reshape(-1).contiguous(), self.ignore_index)
+        return loss
 
 
 def distillation_criterion(name: str, fused: bool = False) -> nn.Module:

@@ -939,3 +939,43 @@ def sr_metrics(sr, hr, sr_div, to_luminance, pool):
                                     mean.data_ptr(), flags.data_ptr(), ws.data_ptr(), nb, _stream()),
                "mhaq_fq_sr_metrics")
     return psnr, ssim, l1, mean, flags[:1]
+
+
+# ------------------------------------------------------------------ classification head (validation: no gradient, plain ctypes)
+@_on_device
+def cls_head(x, target, topk=5, ignore_index=-100, want_nll_rank=True):
+    """mhaq_fq_cls_head_fwd on dense [rows, cols] device logits (float32 / bfloat16 / float16) and int64 [rows] labels: two
+    launches, no host synchronisation, no gradient.  Returns (loss[1], acc[2], counts[3] int64, nll[rows] or None,
+    rank[rows] int32 or None, flags[1] int32); outputs and workspace come from the caching allocator.  cls_metrics.py is
+    the public face; the training loss is the compiled node (loss.FusedCrossEntropy)."""
+    for t, name in ((x, "logits"), (target, "target")):
+        if not t.is_cuda:
+            raise _lib.MhaqFqError(f"{name} is on {t.device}: the classification head runs only as HIP kernels on an "
+                                   "MI355X (no CPU fallback by design)")
+    if x.dtype not in _SR_DT:
+        raise TypeError(f"logits must be float32, bfloat16 or float16, got {x.dtype}")
+    if x.dim() != 2 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError("logits must be a non-empty contiguous [rows, cols] tensor")
+    if target.dtype != torch.int64 or target.dim() != 1 or not target.is_contiguous() or target.shape[0] != x.shape[0] \
+            or target.device != x.device:
+        raise ValueError(f"target must be a contiguous int64 [{x.shape[0]}] tensor on {x.device}")
+    if int(topk) < 1:
+        raise ValueError(f"topk must be at least 1, got {topk}")
+    rows, cols = x.shape
+    L = _lib.lib()
+    nb = L.mhaq_fq_cls_head_workspace_bytes(rows)
+    ws = _workspace(nb, x.device)
+    counts = torch.empty(3, dtype=torch.int64, device=x.device)
+    out = torch.empty(4 + (rows if want_nll_rank else 0), dtype=torch.float32, device=x.device)    # loss, acc[2], pad, nll
+    words = torch.empty(1 + (rows if want_nll_rank else 0), dtype=torch.int32, device=x.device)    # flags, rank
+    loss, acc = out[:1], out[1:3]
+    nll = out[4:] if want_nll_rank else None
+    flags = words[:1]
+    rank = words[1:] if want_nll_rank else None
+    _lib.check(L.mhaq_fq_cls_head_fwd(x.data_ptr(), _SR_DT[x.dtype], target.data_ptr(), rows, cols, int(ignore_index),
+                                      int(topk), loss.data_ptr(), acc.data_ptr(), counts.data_ptr(),
+                                      nll.data_ptr() if want_nll_rank else None,
+                                      rank.data_ptr() if want_nll_rank else None, None, flags.data_ptr(), ws.data_ptr(), nb,
+                                      _stream()),
+               "mhaq_fq_cls_head_fwd")
+    return loss, acc, counts, nll, rank, flags

@@ -26,7 +26,8 @@ from torch import nn
 from . import ops
 from ._lib import MhaqFqError
 from .enums import QNMethod, QScheme
-from .loss import FusedPotentialLoss, FusedPotentialLossNoPred, distill_fused_enabled, distillation_criterion
+from .loss import (FusedCrossEntropy, FusedPotentialLoss, FusedPotentialLossNoPred, ce_fused_enabled, cls_metrics_enabled,
+                   distill_fused_enabled, distillation_criterion, is_default_cross_entropy)
 from .wrap import get_model_values, quantize_model
 
 
@@ -101,6 +102,17 @@ class QATConfig:
     # overrides it.  (The five other softmax-family names are FusedDistillLoss either way.)
     fused_distill_loss: bool = False
     criterion: nn.Module = field(default_factory=nn.CrossEntropyLoss)
+    # the criterion of the non-distillation training step as loss.FusedCrossEntropy -- 2 + 1 HIP launches instead of the
+    # framework's log_softmax / nll_loss chain -- where the trainer builds the HIP-backed loss itself, on a GPU, and `criterion`
+    # is an nn.CrossEntropyLoss with default arguments (any other criterion is left alone; `criterion` itself is never
+    # replaced).  Off by default: the loss and its gradient are then the same quantity through other roundings, not the
+    # framework's bits.  MHAQ_CE_FUSED=1 / 0 in the environment overrides it.
+    fused_cross_entropy: bool = False
+    # validate_step's "cls" record from the classification head (cls_metrics.py: two HIP launches on the logits): val_loss (for a
+    # default nn.CrossEntropyLoss criterion) and top1 come from the kernel, and Accuracy_top1, Accuracy_top5, their ns_* products
+    # with `converged`, `correct` (the [3] counts) and `metric_flags` are appended.  Off by default: the record and its launches
+    # are then unchanged.  MHAQ_CLS_METRICS=1 / 0 in the environment overrides it.
+    cls_metrics: bool = False
     # mixed precision (the reference trainer's `precision = "bf16-mixed"`, training/trainer.py:126): torch.bfloat16 runs
     # the teacher and student forwards, the loss and validate_step's forward under torch.autocast; the activation
     # quantizers then take the 16-bit kernels (mhaq_fq_act_*_x16), weights and quantizer parameters stay float32.
@@ -352,8 +364,11 @@ class QATTrainer:
                                   "its PotentialLoss run only as HIP kernels (no CPU fallback by design)")
             loss_classes = (FusedPotentialLoss, FusedPotentialLossNoPred)
             fused_distill = distill_fused_enabled(cfg.fused_distill_loss)
+            fused_ce = ce_fused_enabled(cfg.fused_cross_entropy) and is_default_cross_entropy(cfg.criterion)
         else:
-            fused_distill = False       # a caller's loss classes keep the framework's Symmetrical KL
+            fused_distill = fused_ce = False    # a caller's loss classes keep the framework's Symmetrical KL and criterion
+        # the criterion of the non-distillation training step; validate_step keeps cfg.criterion (or takes the head's loss)
+        self._train_criterion = FusedCrossEntropy(ignore_index=cfg.criterion.ignore_index) if fused_ce else cfg.criterion
         if cfg.distillation:
             self.loss = loss_classes[0](distillation_criterion(cfg.distillation_loss, fused_distill), p=1,
                                         a=cfg.act_bit, w=cfg.weight_bit)
@@ -670,7 +685,7 @@ class QATTrainer:
                         fp.record_stream(main)
                 loss = self.loss(out, fp)
             else:
-                loss = self.loss((self.cfg.criterion(out[0], y), *out[1:]))
+                loss = self.loss((self._train_criterion(out[0], y), *out[1:]))
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         return loss
@@ -690,6 +705,10 @@ class QATTrainer:
                 out = self.net(x * 255 if sr and self.cfg.sr_denormalize else x)
             if sr:                       # enqueued ahead of the integrity check's host sync: the step keeps its one sync
                 head = self._sr_record_head(out, y)
+            elif cls_metrics_enabled(self.cfg.cls_metrics):
+                head = self._cls_record_head(out, y)
+            else:
+                head = None
             out = out.float()            # the statistics below in float32, as without autocast
             check_model_integrity(self.net)
         finally:
@@ -697,7 +716,15 @@ class QATTrainer:
         with stats.memoised():          # one HIP sweep per weight layer for the six statistics + is_converged
             if sr:
                 return {**head, **self._bit_width_record(stats)}
-            return self._validation_record(out, y, stats)
+            return self._validation_record(out, y, stats, head)
+
+    def _cls_record_head(self, out, y):
+        """LVisionCls' validation step (vision_cls_module.py:17-26, 67-77): the criterion and torchmetrics' Accuracy_top1 /
+        Accuracy_top5 from the classification head -- cls_metrics.py, two launches on the logits (16-bit ones under
+        autocast are converted up exactly), no host sync.  `flags` is the device word check_cls_flags reads."""
+        from .cls_metrics import cls_metrics
+        crit = self.cfg.criterion
+        return cls_metrics(out, y, topk=5, ignore_index=crit.ignore_index if is_default_cross_entropy(crit) else -100)
 
     def _sr_record_head(self, out, y):
         """LVisionSR.validation_step (vision_sr_module.py:151-167): the criterion on the scaled, unclamped prediction, PSNR and
@@ -725,15 +752,17 @@ class QATTrainer:
             "converged": stats.is_converged(self.net, self.loss),
         }
 
-    def _validation_record(self, out, y, stats):
-        return {
-            "val_loss": self.cfg.criterion(out, y),
-            "top1": (out.argmax(1) == y).float().mean(),
-            "mean_weights_bit_width": stats.get_weights_bit_width_mean(self.net),
-            "actual_weights_bit_width": stats.get_true_weights_width(self.net, max=False),
-            "actual_weights_max_bit_width": stats.get_true_weights_width(self.net),
-            "mean_activations_bit_width": stats.get_activations_bit_width_mean(self.net),
-            "actual_activations_bit_width": stats.get_true_activations_width(self.net, max=False),
-            "actual_activations_max_bit_width": stats.get_true_activations_width(self.net),
-            "converged": stats.is_converged(self.net, self.loss),
+    def _validation_record(self, out, y, stats, head=None):
+        """`head`: what _cls_record_head enqueued (cfg.cls_metrics), or None for the framework's ops."""
+        crit = self.cfg.criterion
+        rec = {
+            "val_loss": head["loss"] if head is not None and is_default_cross_entropy(crit) else crit(out, y),
+            "top1": head["Accuracy_top1"] if head is not None else (out.argmax(1) == y).float().mean(),
+            **self._bit_width_record(stats),
         }
+        if head is not None:         # the reference's val decorator logs Metric/ns_<name> = metric * is_converged
+            conv = float(rec["converged"])
+            rec.update({"Accuracy_top1": head["Accuracy_top1"], "Accuracy_top5": head["Accuracy_top5"],
+                        "ns_Accuracy_top1": head["Accuracy_top1"] * conv, "ns_Accuracy_top5": head["Accuracy_top5"] * conv,
+                        "correct": head["counts"], "metric_flags": head["flags"]})
+        return rec
