@@ -907,6 +907,10 @@ int mhaq_fq_noise_bwd(const float* v, const float* g, float* gv, float* gs /* [g
  *   fwd: out[12] = {ploss, wloss, aloss, rloss, cw, ca, cb, -mean lws, mean lwq, -mean las, mean laq,
  *        max(lwq-lws)};  update_state != 0 also does loss_sum += base^p, cnt += 1 (training mode).
  *   bwd: given g = dL/dploss [1] and `out` from fwd: g_base [1], g_las/g_laq [na], g_lws/g_lwq [nw].
+ *   No NaN screening, plain IEEE as the reference (torch.max(0, h), .mean(), (lwq-lws).max()): a NaN in lws or lwq
+ *   makes ploss, wloss, that vector's mean and max(lwq-lws) NaN, one in las or laq makes ploss, aloss and that
+ *   vector's mean NaN; a NaN hinge counts as inactive (NaN > 0 is false).  The other side's outputs are untouched.
+ *   The gradients under a NaN input are finite or NaN, not specified (the reference's own come from max's backward).
  * ---------------------------------------------------------------------- */
 int mhaq_fq_potential_loss_fwd(const float* base, const float* las, const float* laq, int64_t na,
                                const float* lws, const float* lwq, int64_t nw,

@@ -1450,7 +1450,13 @@ __global__ __launch_bounds__(kSmallThreads) void wt_small_bwd_kernel(
 //   out[0] ploss  [1] wloss  [2] aloss  [3] rloss  [4] cw  [5] ca  [6] cb     (cw/ca: d ploss / d hinge_i,
 //   cb: d ploss / d base)   [7] -mean lws  [8] mean lwq  [9] -mean las  [10] mean laq  [11] max(lwq - lws)
 
-__device__ inline float hinge_pow(float h, float p) { return (h > 0.f) ? ((p == 1.f) ? h : powf(h, p)) : 0.f; }
+// No NaN screening, plain IEEE as the reference: torch.max(0, h) and (lwq - lws).max() hand a NaN on, so a NaN hinge is
+// NaN (and counts as inactive: NaN > 0 is false there too) and the running maximum keeps a NaN once it has met one.
+__device__ inline float hinge_pow(float h, float p) {
+  if (h != h) return h;
+  return (h > 0.f) ? ((p == 1.f) ? h : powf(h, p)) : 0.f;
+}
+__device__ inline float nanmax(float a, float b) { return (a != a || b != b) ? NAN : fmaxf(a, b); }
 // d/dh of max(0, h)^p; torch.max(0, h) splits the gradient at the tie h == 0
 __device__ inline float hinge_grad(float h, float p) {
   if (h < 0.f) return 0.f;
@@ -1488,7 +1494,7 @@ __global__ __launch_bounds__(kBlock) void potential_loss_fwd_kernel(
         acc[1] += (h > 0.f) ? 1.0 : 0.0;
         acc[4] += (double)sv[k];
         acc[5] += (double)q[k];
-        mx = fmaxf(mx, d);
+        mx = nanmax(mx, d);
       }
     }
   }
@@ -1511,11 +1517,12 @@ __global__ __launch_bounds__(kBlock) void potential_loss_fwd_kernel(
       }
     }
   }
-  mx = wave_max(mx);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = nanmax(mx, __shfl_down(mx, o, 64));     // wave_max with the NaN kept
   if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = mx;
   block_sum<8>(acc, sm);          // contains the barriers that also publish smax
   if (threadIdx.x == 0) {
-    for (int w = 1; w < kBlock / 64; ++w) mx = fmaxf(mx, smax[w]);
+    for (int w = 1; w < kBlock / 64; ++w) mx = nanmax(mx, smax[w]);
     const float wloss = (float)acc[0] / (float)nw, aloss = (float)acc[2] / (float)na;
     const float wact = (float)acc[1], aact = (float)acc[3];
     const float b = *base;
