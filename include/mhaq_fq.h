@@ -662,6 +662,95 @@ int mhaq_fq_cls_head_fwd(const void* x, int x_dtype, const int64_t* target, int6
                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Object-detection validation: the YOLO head's non-maximum suppression and COCO's greedy matching of its output against
+ * the ground truth, in three entry points with the caller's sort between the first two.  Additive to ABI v4 --
+ * MHAQ_FQ_ABI_VERSION stays 4; a caller discovers these entry points by symbol.
+ *   pred          what the head returns in eval mode, dense [B][4 + nc][A]; MHAQ_FQ_DT_F32, MHAQ_FQ_DT_BF16 or MHAQ_FQ_DT_F16,
+ *                 aligned to its element size.  Rows 0-3 are cx, cy, w, h in pixels, rows 4.. the class scores (already
+ *                 sigmoided).  16-bit elements are converted up exactly; everything after that is fp32 arithmetic with no
+ *                 contraction and IEEE division.
+ * The contract restates the reference's non_max_suppression with its NMS call written out; it is not a recording.
+ * Candidates.  Pair (a, c) is a candidate iff score[a][c] > conf_thr; a NaN score is never one.  conf_thr is finite and
+ *   >= 0, so the bit pattern of every candidate's score is a non-negative int32.
+ * Order.  Descending score, ties by (a, c) ascending (a stable descending sort of the reference's candidate list; the
+ *   reference's own argsort leaves the order of ties undefined, so this is one of its valid results), realised as
+ *   key = (int64(0x7FFFFFFF - bits(score)) << 32) | (a * nc + c);  a pair that is no candidate carries INT64_MAX.  Keys are
+ *   unique, so ascending key order is the order.  Only the first max_nms candidates (reference: 30000) go on.
+ * Boxes.  x1 = cx - w / 2, y1 = cy - h / 2, x2 = cx + w / 2, y2 = cy + h / 2.  The class offset is o = float(c) * max_wh
+ *   (reference: 7680), the offset box b = box + o, each coordinate rounded once, and area = (b.x2 - b.x1) * (b.y2 - b.y1)
+ *   is taken on the OFFSET box.  At class 79 the offset coordinates sit on a grid of 1/16 px: that is part of the contract.
+ * Suppression.  Walk the candidates in order: candidate j is kept iff no earlier KEPT candidate i has
+ *   inter / ((area_i + area_j) - inter) > iou_thr,  inter = max(0, min(i.x2, j.x2) - max(i.x1, j.x1)) * (the same in y),
+ *   where min(p, q) = q < p ? q : p and max(p, q) = p < q ? q : p with p the kept box's operand (0 in the outer max): a NaN
+ *   compares false.  The comparison is strict and in fp32; 0 / 0 is NaN and does not suppress.  The first max_det kept
+ *   candidates (reference: 100) are the output, and the walk ends there.
+ *
+ * mhaq_fq_od_keys: one launch, one read of the score rows, coalesced along A.
+ *   keys          [B][A * nc] int64, 8-byte aligned.  Every element is written; the POSITION of a key inside its image's row
+ *                 is unspecified (the order lives in the key's value).  The caller sorts each row ascending (any sort of
+ *                 int64 rows) before mhaq_fq_od_nms.
+ *   Errors, before the launch: NULL pred / keys, an unknown dtype, B, nc or A < 1, conf_thr negative, NaN or infinite
+ *   (MHAQ_FQ_EINVAL); pred not aligned to its element size, keys not 8-byte aligned (MHAQ_FQ_EALIGN); A * nc > 2^31 - 1,
+ *   B or nc > 65535 (MHAQ_FQ_EUNSUPPORTED).
+ *
+ * mhaq_fq_od_nms: two launches (one workgroup per image; one workgroup for the flag word).
+ *   keys          the rows of mhaq_fq_od_keys, each sorted ascending.  A key inside the candidate range whose low word is
+ *                 not below A * nc is skipped; no address is formed from it.
+ *   det           [B][max_det][6] fp32: x1, y1, x2, y2 of the UN-offset box, score, float(class), in kept order; rows at and
+ *                 beyond count[b] are written as zeros
+ *   count         [B] int32, kept boxes of the image (<= max_det)
+ *   n_cand        [B] int32, candidates of the image before the truncation to max_nms: the position of the first INT64_MAX
+ *                 of its sorted row (a binary search; no count kernel, no atomics)
+ *   flags         [1] device word, WRITTEN by the call: bit 0 (value 1) = a NaN or infinite coordinate x1, y1, x2 or y2 of
+ *                 the un-offset box among the candidates that were walked, i.e. those at sorted positions up to and including
+ *                 the one that filled the list, or all of the first max_nms when the list did not fill; bit 1 (value 2) = an
+ *                 image had more than max_nms candidates
+ *   workspace     mhaq_fq_od_nms_workspace_bytes(B) bytes, 4-byte aligned: one flag word per image
+ *   Workspace and LDS grow with B and max_det only, never with the square of the candidate count: mhaq_fq_od_nms_chunk()
+ *   candidates at a time are tested against the kept boxes (LDS) and then resolved among themselves in order, a box being
+ *   tested only against boxes that are kept.  Ending the walk at max_det is exact: whether a candidate is kept depends on
+ *   earlier candidates only.  There is no wall-clock limit: every image of the batch is processed.
+ *   Errors, before any launch: a NULL pointer, an unknown dtype, B, nc, A, max_nms or max_det < 1, iou_thr NaN, max_wh NaN or
+ *   infinite (MHAQ_FQ_EINVAL); a short workspace (MHAQ_FQ_EWORKSPACE); pred not aligned to its element size, keys not 8-byte
+ *   or another pointer not 4-byte aligned (MHAQ_FQ_EALIGN); A * nc > 2^31 - 1, B or nc > 65535, max_det > 1024
+ *   (MHAQ_FQ_EUNSUPPORTED).
+ *
+ * mhaq_fq_od_match: COCO's greedy matching (pycocotools' evaluateImg for area = all, no crowd boxes, maxDets = max_det) of a
+ * batch's detections against its ground truth, one launch, one workgroup of ten wavefronts per image.
+ *   det, count    as written by mhaq_fq_od_nms (count is clamped to [0, max_det])
+ *   nc            classes: a ground-truth label outside [0, nc) sets bit 2 (value 4) of flags; that box is ignored and no
+ *                 address is formed from its label
+ *   gt_box        [G][4] fp32 x1, y1, x2, y2;  gt_label [G] int64;  gt_off [B + 1] int64, CSR offsets of the images into
+ *                 them (device memory; clamped to [0, G]).  G == 0: gt_box, gt_label and workspace may be NULL.
+ *   tp            [B][max_det] int32: bit k = detection d is matched at threshold T_k; 0 at and beyond count[b]
+ *   flags         [1] device word, OR-ed into (mhaq_fq_od_nms wrote it)
+ *   workspace     mhaq_fq_od_match_workspace_bytes(G) bytes: one mark per ground-truth box and threshold
+ *   Per image and k = 0..9, T_k = the fp64 values of numpy.linspace(0.5, 0.95, 10): detections are walked in output order;
+ *   detection d of class c takes, among the image's ground truth with label c that is still unmatched at k and has
+ *   double(iou32(d, g)) >= T_k, the one with the largest IoU, ties to the highest index (pycocotools' >= update rule);
+ *   both are then marked.  iou32 is the formula above on the un-offset boxes (p the detection's operand), areas
+ *   (x2 - x1) * (y2 - y1); a NaN never matches.
+ *   Errors, before the launch: NULL det / count / gt_off / tp / flags, B, max_det or nc < 1, G < 0, with G > 0 a NULL gt_box /
+ *   gt_label / workspace (MHAQ_FQ_EINVAL); a short workspace (MHAQ_FQ_EWORKSPACE); gt_label / gt_off not 8-byte or another
+ *   pointer not 4-byte aligned (MHAQ_FQ_EALIGN); max_det > 1024 (MHAQ_FQ_EUNSUPPORTED).
+ * All three: stream-ordered, capture-safe, stateless, no host synchronisation, no atomics (every word has one writer); the
+ * same inputs give the same bits at every call.
+ * ---------------------------------------------------------------------- */
+int mhaq_fq_od_nms_chunk(void);
+int mhaq_fq_od_keys(const void* pred, int pred_dtype, int64_t B, int64_t nc, int64_t A, float conf_thr,
+                    int64_t* keys /* [B][A*nc] */, void* stream);
+size_t mhaq_fq_od_nms_workspace_bytes(int64_t B);
+int mhaq_fq_od_nms(const void* pred, int pred_dtype, const int64_t* keys /* sorted rows */,
+                   int64_t B, int64_t nc, int64_t A, float iou_thr, float max_wh, int max_nms, int max_det,
+                   float* det /* [B][max_det][6] */, int32_t* count /* [B] */, int32_t* n_cand /* [B] */,
+                   uint32_t* flags /* [1] */, void* workspace, size_t workspace_bytes, void* stream);
+size_t mhaq_fq_od_match_workspace_bytes(int64_t G);
+int mhaq_fq_od_match(const float* det, const int32_t* count, int64_t B, int max_det, int64_t nc,
+                     const float* gt_box /* [G][4] */, const int64_t* gt_label /* [G] */,
+                     const int64_t* gt_off /* [B+1] */, int64_t G, int32_t* tp /* [B][max_det] */,
+                     uint32_t* flags /* [1] */, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Super-resolution validation metrics: per-image PSNR and SSIM of the clamped prediction against the target and the L1
  * criterion on the unclamped one, in three launches.  Additive to ABI v4 -- MHAQ_FQ_ABI_VERSION stays 4; a caller discovers
  * these entry points by symbol.

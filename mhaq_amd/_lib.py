@@ -95,6 +95,15 @@ SIGNATURES = {
     # workspace (additive, ABI v4 kept)
     "mhaq_fq_cls_head_workspace_bytes": (_sz, [_i64]),
     "mhaq_fq_cls_head_fwd": (_int, [_p, _int, _p, _i64, _i64, _i64, _int, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    # object-detection validation (additive, ABI v4 kept).  keys: pred, dtype, B, nc, A, conf_thr, keys.  nms: pred, dtype,
+    # sorted keys, B, nc, A, iou_thr, max_wh, max_nms, max_det, det, count, n_cand, flags, workspace.  match: det, count, B,
+    # max_det, nc, gt_box, gt_label, gt_off, G, tp, flags, workspace
+    "mhaq_fq_od_nms_chunk": (_int, []),
+    "mhaq_fq_od_keys": (_int, [_p, _int, _i64, _i64, _i64, C.c_float, _p, _p]),
+    "mhaq_fq_od_nms_workspace_bytes": (_sz, [_i64]),
+    "mhaq_fq_od_nms": (_int, [_p, _int, _p, _i64, _i64, _i64, C.c_float, C.c_float, _int, _int, _p, _p, _p, _p, _p, _sz, _p]),
+    "mhaq_fq_od_match_workspace_bytes": (_sz, [_i64]),
+    "mhaq_fq_od_match": (_int, [_p, _p, _i64, _int, _i64, _p, _p, _p, _i64, _p, _p, _p, _sz, _p]),
     # super-resolution validation metrics: sr, sr_dtype, hr, hr_dtype, n, c, h, w, sr_div, to_luminance, pool, psnr, ssim,
     # l1, mean, flags, workspace (additive, ABI v4 kept)
     "mhaq_fq_sr_metrics_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _int, _int]),

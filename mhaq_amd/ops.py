@@ -979,3 +979,85 @@ def cls_head(x, target, topk=5, ignore_index=-100, want_nll_rank=True):
                                       _stream()),
                "mhaq_fq_cls_head_fwd")
     return loss, acc, counts, nll, rank, flags
+
+
+# ------------------------------------------------------------------ object-detection validation (no gradient, plain ctypes)
+def _od_pred(pred):
+    if not pred.is_cuda:
+        raise _lib.MhaqFqError(f"pred is on {pred.device}: the detection head's NMS runs only as HIP kernels on an MI355X "
+                               "(no CPU fallback by design)")
+    if pred.dtype not in _SR_DT:
+        raise TypeError(f"pred must be float32, bfloat16 or float16, got {pred.dtype}")
+    if pred.dim() != 3 or pred.shape[1] < 5 or pred.numel() == 0 or not pred.is_contiguous():
+        raise ValueError("pred must be a non-empty contiguous [B, 4 + nc, A] tensor")
+    b, rows, a = pred.shape
+    return b, rows - 4, a
+
+
+def od_nms_chunk() -> int:
+    """Candidates per sweep of the NMS workgroup (mhaq_fq_od_nms_chunk)."""
+    return int(_lib.lib().mhaq_fq_od_nms_chunk())
+
+
+@_on_device
+def od_keys(pred, conf_thr):
+    """mhaq_fq_od_keys on a dense [B, 4 + nc, A] device tensor (float32 / bfloat16 / float16): one launch.  Returns the
+    unsorted int64 keys [B, A * nc]."""
+    b, nc, a = _od_pred(pred)
+    keys = torch.empty((b, a * nc), dtype=torch.int64, device=pred.device)
+    _lib.check(_lib.lib().mhaq_fq_od_keys(pred.data_ptr(), _SR_DT[pred.dtype], b, nc, a, float(conf_thr), keys.data_ptr(),
+                                          _stream()), "mhaq_fq_od_keys")
+    return keys
+
+
+@_on_device
+def od_nms_sorted(pred, keys, iou_thr, max_wh, max_nms, max_det):
+    """mhaq_fq_od_nms on `pred` and the rows of od_keys sorted ascending: two launches, no host synchronisation.  Returns
+    (det[B, max_det, 6], count[B] int32, n_cand[B] int32, flags[1] int32)."""
+    b, nc, a = _od_pred(pred)
+    if keys.dtype != torch.int64 or keys.shape != (b, a * nc) or not keys.is_contiguous() or keys.device != pred.device:
+        raise ValueError(f"keys must be a contiguous int64 [{b}, {a * nc}] tensor on {pred.device}")
+    L = _lib.lib()
+    nb = L.mhaq_fq_od_nms_workspace_bytes(b)
+    ws = _workspace(nb, pred.device)
+    det = torch.empty((b, int(max_det), 6), dtype=torch.float32, device=pred.device)
+    words = torch.empty(2 * b + 1, dtype=torch.int32, device=pred.device)           # count, n_cand, flags
+    count, n_cand, flags = words[:b], words[b:2 * b], words[2 * b:]
+    _lib.check(L.mhaq_fq_od_nms(pred.data_ptr(), _SR_DT[pred.dtype], keys.data_ptr(), b, nc, a, float(iou_thr), float(max_wh),
+                                int(max_nms), int(max_det), det.data_ptr(), count.data_ptr(), n_cand.data_ptr(),
+                                flags.data_ptr(), ws.data_ptr(), nb, _stream()), "mhaq_fq_od_nms")
+    return det, count, n_cand, flags
+
+
+def od_nms(pred, conf_thr, iou_thr, max_wh, max_nms, max_det):
+    """The three stages on one prediction: od_keys, torch.sort of the key rows (plumbing: the library brings no segmented
+    sort, a C caller its own), od_nms_sorted."""
+    keys = od_keys(pred, conf_thr)
+    return od_nms_sorted(pred, torch.sort(keys, dim=1).values, iou_thr, max_wh, max_nms, max_det)
+
+
+@_on_device
+def od_match(det, count, gt_box, gt_label, gt_off, nc, flags):
+    """mhaq_fq_od_match: one launch, no host synchronisation.  `det` [B, max_det, 6] and `count` [B] as od_nms returns them,
+    `gt_box` [G, 4] float32 xyxy, `gt_label` [G] int64 and the CSR offsets `gt_off` [B + 1] int64 on det's device; bit 2 is
+    OR-ed into `flags` in place.  Returns tp [B, max_det] int32."""
+    if not det.is_cuda:
+        raise _lib.MhaqFqError(f"det is on {det.device}: the detection matching runs only as HIP kernels on an MI355X "
+                               "(no CPU fallback by design)")
+    if det.dtype != torch.float32 or det.dim() != 3 or det.shape[2] != 6 or det.numel() == 0 or not det.is_contiguous():
+        raise ValueError("det must be a non-empty contiguous float32 [B, max_det, 6] tensor")
+    b, max_det, _ = det.shape
+    g = gt_label.shape[0]
+    for t, name, dt, shape in ((count, "count", torch.int32, (b,)), (gt_box, "gt_box", torch.float32, (g, 4)),
+                               (gt_label, "gt_label", torch.int64, (g,)), (gt_off, "gt_off", torch.int64, (b + 1,)),
+                               (flags, "flags", torch.int32, (1,))):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != det.device:
+            raise ValueError(f"{name} must be a contiguous {dt} {list(shape)} tensor on {det.device}")
+    L = _lib.lib()
+    nb = L.mhaq_fq_od_match_workspace_bytes(g)
+    ws = _workspace(max(nb, 8), det.device)
+    tp = torch.empty((b, max_det), dtype=torch.int32, device=det.device)
+    _lib.check(L.mhaq_fq_od_match(det.data_ptr(), count.data_ptr(), b, max_det, int(nc), gt_box.data_ptr() if g else None,
+                                  gt_label.data_ptr() if g else None, gt_off.data_ptr(), g, tp.data_ptr(), flags.data_ptr(),
+                                  ws.data_ptr(), nb, _stream()), "mhaq_fq_od_match")
+    return tp

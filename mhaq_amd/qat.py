@@ -118,10 +118,17 @@ class QATConfig:
     # quantizers then take the 16-bit kernels (mhaq_fq_act_*_x16), weights and quantizer parameters stay float32.
     # None = float32 throughout.  torch.float16 would need loss scaling and is refused.
     autocast_dtype: Optional[torch.dtype] = None
+    # task "od" (below): the confidence and IoU thresholds and the detections kept per image of the reference's
+    # non_max_suppression (yolo_nms.py:15-19), handed to od_metrics.od_nms
+    od_conf_thr: float = 0.001
+    od_iou_thr: float = 0.65
+    od_max_det: int = 100
     # what validate_step records: "cls" = the classification record (val_loss, top1, ...), "sr" = the super-resolution record of
     # the reference's LVisionSR.validation_step (PSNR, SSIM and the criterion, sr_metrics.py: three HIP launches).  For "sr":
     # sr_to_luminance = the config's `to_luminance` (PSNR / SSIM on the luminance plane), sr_denormalize = its `denormalize`
-    # (the model sees x * 255 and its output is divided by 255, LVisionSR.forward).
+    # (the model sees x * 255 and its output is divided by 255, LVisionSR.forward).  "od" = the object-detection record of
+    # LVisionOD.validation_step (od_metrics.py: NMS of the YOLO head's [B, 4 + nc, A] output and COCO matching against the
+    # target list, for OdValidationMeter); y is then the list of {"boxes", "labels"} dicts of the images.
     task: str = "cls"
     sr_to_luminance: bool = True
     sr_denormalize: bool = False
@@ -255,11 +262,11 @@ class QATTrainer:
         (mhaq_amd/loss.py).  A CPU trainer is checker territory (tests, bench.py's cpu_baseline): it must bring its
         layers AND its loss (oracle/ref_layers.py, oracle/loss.py) -- the product has no CPU arithmetic."""
         self.cfg, self.device = cfg, torch.device(device)
-        if cfg.task not in ("cls", "sr"):
-            raise ValueError(f"QATConfig.task: {cfg.task!r} is not supported (\"cls\" or \"sr\")")
-        if cfg.task == "sr" and self.device.type != "cuda":
-            raise MhaqFqError("QATConfig.task = \"sr\" on a CPU device: the validation metrics run only as HIP kernels "
-                              "(no CPU fallback by design)")
+        if cfg.task not in ("cls", "sr", "od"):
+            raise ValueError(f"QATConfig.task: {cfg.task!r} is not supported (\"cls\", \"sr\" or \"od\")")
+        if cfg.task in ("sr", "od") and self.device.type != "cuda":
+            raise MhaqFqError(f"QATConfig.task = \"{cfg.task}\" on a CPU device: the validation metrics run only as HIP "
+                              "kernels (no CPU fallback by design)")
         if cfg.autocast_dtype is not None and cfg.autocast_dtype != torch.bfloat16:
             raise ValueError(f"QATConfig.autocast_dtype: {cfg.autocast_dtype} is not supported (None or torch.bfloat16; "
                              "float16 training needs loss scaling, which this trainer does not do)")
@@ -698,13 +705,15 @@ class QATTrainer:
         their integrity flags (gdnsq.py:211-217), checked here with ONE host sync for the whole model."""
         from . import stats
         from .gdnsq import check_model_integrity
-        sr = self.cfg.task == "sr"
+        sr, od = self.cfg.task == "sr", self.cfg.task == "od"
         self.module.eval()
         try:
             with self._autocast():
                 out = self.net(x * 255 if sr and self.cfg.sr_denormalize else x)
             if sr:                       # enqueued ahead of the integrity check's host sync: the step keeps its one sync
                 head = self._sr_record_head(out, y)
+            elif od:
+                head = self._od_record_head(out, y)
             elif cls_metrics_enabled(self.cfg.cls_metrics):
                 head = self._cls_record_head(out, y)
             else:
@@ -714,7 +723,7 @@ class QATTrainer:
         finally:
             self.module.train()
         with stats.memoised():          # one HIP sweep per weight layer for the six statistics + is_converged
-            if sr:
+            if sr or od:
                 return {**head, **self._bit_width_record(stats)}
             return self._validation_record(out, y, stats, head)
 
@@ -740,6 +749,18 @@ class QATTrainer:
             val_loss = crit(out.float().div(div) if self.cfg.sr_denormalize else out.float(), y)
         return {"PSNR": m["PSNR"], "SSIM": m["SSIM"], "psnr": m["psnr"], "ssim": m["ssim"], "metric_flags": m["flags"],
                 "val_loss": val_loss}
+
+    def _od_record_head(self, out, target):
+        """LVisionOD.validation_step (MeanAveragePrecisionYolo.update on the head's eval output): non-maximum suppression and
+        COCO matching against the target list -- od_metrics.py, keys / sort / NMS / match, no host sync.  The reference's
+        step applies no criterion and returns 0: `val_loss` is a 0-dim zero.  `metric_flags` is the device word
+        check_od_flags reads; OdValidationMeter takes the record as it is."""
+        from .od_metrics import od_match, od_nms
+        m = od_match(od_nms(out.contiguous(), conf_thr=self.cfg.od_conf_thr, iou_thr=self.cfg.od_iou_thr,
+                            max_det=self.cfg.od_max_det), target)
+        return {"det": m["det"], "det_count": m["count"], "tp": m["tp"], "gt_labels": m["gt_labels"],
+                "gt_offsets": m["gt_offsets"], "metric_flags": m["flags"],
+                "val_loss": torch.zeros((), dtype=torch.float32, device=out.device)}
 
     def _bit_width_record(self, stats):
         return {
