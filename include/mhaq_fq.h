@@ -792,6 +792,26 @@ int mhaq_fq_sr_metrics(const void* sr, int sr_dtype, const void* hr, int hr_dtyp
                        float* psnr /* [n] */, float* ssim /* [n] */, float* l1 /* [1] */, float* mean /* [2] */,
                        uint32_t* flags /* [1] */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Captured steps: every memset node of a hipGraph becomes a kernel node that stores the same bytes.  Additive to ABI v4 --
+ * MHAQ_FQ_ABI_VERSION stays 4; a caller discovers this entry point by symbol.
+ * A captured training step holds memset nodes that no launch of this library made (under torch.autocast MIOpen's 16-bit
+ * backward-data convolutions clear their output with hipMemsetAsync), and replays of a graph with memset nodes do not repeat
+ * the eager step on every MI355X host.  Call this between the end of the capture and hipGraphInstantiate.
+ *   graph         a hipGraph_t that is not being captured into; an executable graph instantiated from it earlier does not
+ *                 change
+ *   replaced_out  optional host word: the number of memset nodes replaced
+ *   left_out      optional host word: the number of memset nodes left as they are (see below)
+ * Each memset node (1-, 2- or 4-byte elements, one row or `height` rows `pitch` bytes apart) is replaced by one launch of a
+ * fill kernel with the node's dependencies and dependents, a memset of no bytes by an empty node; every other node and edge
+ * stays.  The kernel writes exactly the bytes the memset would have written.  A memset node the kernel does not serve
+ * (another element size, a NULL destination, a pitch shorter than a row, a destination or pitch that is no multiple of the
+ * element size) is left in the graph and counted in *left_out: the graph is still the captured one.
+ * Returns 0, MHAQ_FQ_EINVAL (a NULL graph), or the hipError_t of a graph call that failed (> 0); both words are written in
+ * every case, and after a failed graph call the nodes replaced so far stay replaced.  Host code only: no launch, no stream.
+ * ---------------------------------------------------------------------- */
+int mhaq_fq_graph_memsets_to_kernels(void* graph, int32_t* replaced_out, int32_t* left_out);
+
 /* Whole-tensor min / max (zero point of a PER_TENSOR weight quantizer,
  * gdnsq_conv2d.py:82-83; min/max observer, calib/minmaxobserver.py:19-36).
  * out[0] = min, out[1] = max. */

@@ -109,6 +109,8 @@ SIGNATURES = {
     "mhaq_fq_sr_metrics_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _int, _int]),
     "mhaq_fq_sr_metrics": (_int, [_p, _int, _p, _int, _i64, _i64, _i64, _i64, C.c_float, _int, _int, _p, _p, _p, _p, _p,
                                   _p, _sz, _p]),
+    # a captured hipGraph's memset nodes -> fill-kernel nodes: graph, replaced_out, left_out (additive, ABI v4 kept)
+    "mhaq_fq_graph_memsets_to_kernels": (_int, [_p, _p, _p]),
     "mhaq_fq_minmax_workspace_bytes": (_sz, [_i64]),
     "mhaq_fq_minmax": (_int, [_p, _i64, _p, _p, _sz, _p]),
     "mhaq_fq_row_minmax": (_int, [_p, _i64, _i64, _p, _p, _p]),

@@ -315,6 +315,18 @@ def fill_r(n: int, seed: int, offset: int, device) -> torch.Tensor:
     return out
 
 
+def graph_memsets_to_kernels(graph: "torch.cuda.CUDAGraph"):
+    """mhaq_fq_graph_memsets_to_kernels on a captured torch.cuda.CUDAGraph(keep_graph=True) that has not been instantiated
+    yet: every memset node (MIOpen's 16-bit backward-data convolutions clear their output with hipMemsetAsync) becomes a
+    launch of the library's fill kernel with the same edges.  Call it on the device the graph was captured on, then
+    graph.instantiate().  Returns (replaced, left): the nodes replaced, and the memset nodes the kernel does not serve,
+    which stay in the graph."""
+    n, left = _i32(0), _i32(0)
+    _lib.check(_lib.lib().mhaq_fq_graph_memsets_to_kernels(graph.raw_cuda_graph(), _byref(n), _byref(left)),
+               "mhaq_fq_graph_memsets_to_kernels")
+    return int(n.value), int(left.value)
+
+
 @_on_device
 def minmax(x: torch.Tensor) -> torch.Tensor:
     """[min, max] of a tensor in one fused sweep (weight zero point; min/max observer)."""

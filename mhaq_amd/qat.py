@@ -573,7 +573,7 @@ class QATTrainer:
         self._static = (x.clone(), y.clone())
         self.optimizer.zero_grad(set_to_none=True)
         torch.cuda.synchronize(self.device)
-        graph = torch.cuda.CUDAGraph()
+        graph = None
         drawn = ops.rng.drawn()
         # Under data parallelism another thread of this process talks to the GPU while we capture: the process group's
         # watchdog polls its work events.  In the default ("global") error mode such a call from ANY thread invalidates
@@ -581,6 +581,8 @@ class QATTrainer:
         mode = "thread_local" if self.distributed else "global"
         err = None
         try:
+            # keep_graph: the hipGraph stays ours to edit between the capture and its instantiation (below)
+            graph = torch.cuda.CUDAGraph(keep_graph=True)
             with torch.cuda.graph(graph, stream=self._gstream, capture_error_mode=mode), \
                     ops.rng.device_offset(self._rng_base):
                 self._static_loss = self._forward_backward(*self._static)
@@ -588,6 +590,14 @@ class QATTrainer:
                 # device word K further, so replay k runs at the offsets eager step k would have used
                 self._rng_stride = ops.rng.drawn() - drawn
                 self._rng_base.add_(self._rng_stride)
+            # Under autocast the capture holds memset nodes: MIOpen's 16-bit backward-data convolutions clear their output
+            # with hipMemsetAsync.  Replays of such a graph left the eager trajectory after one or two steps on some hosts
+            # (wrong input gradients in a few channels, NaN soon after); as launches of the library's fill kernel the clears
+            # are launches like everything else in the step.  (A workaround for the replay of memset nodes, not a change of
+            # what the step computes; a memset node the fill kernel does not serve stays, and the capture with it.)
+            with torch.cuda.device(self.device):
+                ops.graph_memsets_to_kernels(graph)
+                graph.instantiate()
         except Exception as e:      # noqa: BLE001 -- whatever made the capture fail, training goes on eagerly
             err = e
         # every rank reaches this point in the same step; a capture that failed on ONE rank takes all of them to the
