@@ -688,7 +688,8 @@ int mhaq_fq_cls_head_fwd(const void* x, int x_dtype, const int64_t* target, int6
  * mhaq_fq_od_keys: one launch, one read of the score rows, coalesced along A.
  *   keys          [B][A * nc] int64, 8-byte aligned.  Every element is written; the POSITION of a key inside its image's row
  *                 is unspecified (the order lives in the key's value).  The caller sorts each row ascending (any sort of
- *                 int64 rows) before mhaq_fq_od_nms.
+ *                 int64 rows) before mhaq_fq_od_nms -- or calls mhaq_fq_od_sorted_keys and mhaq_fq_od_nms_rows (below)
+ *                 instead of this entry point, its own sort and mhaq_fq_od_nms.
  *   Errors, before the launch: NULL pred / keys, an unknown dtype, B, nc or A < 1, conf_thr negative, NaN or infinite
  *   (MHAQ_FQ_EINVAL); pred not aligned to its element size, keys not 8-byte aligned (MHAQ_FQ_EALIGN); A * nc > 2^31 - 1,
  *   B or nc > 65535 (MHAQ_FQ_EUNSUPPORTED).
@@ -749,6 +750,48 @@ int mhaq_fq_od_match(const float* det, const int32_t* count, int64_t B, int max_
                      const float* gt_box /* [G][4] */, const int64_t* gt_label /* [G] */,
                      const int64_t* gt_off /* [B+1] */, int64_t G, int32_t* tp /* [B][max_det] */,
                      uint32_t* flags /* [1] */, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Object-detection validation, the library's own sort: the candidates of every image are compacted out of the score rows and
+ * only they are sorted (a segmented radix sort), in place of mhaq_fq_od_keys and the caller's sort of its rows.  Additive to
+ * ABI v4 -- MHAQ_FQ_ABI_VERSION stays 4; a caller discovers these entry points by symbol.
+ *
+ * mhaq_fq_od_sorted_keys: 15 launches (count, offsets, emit; per 8-bit digit of the score word: histogram, scan, scatter).
+ *   pred, conf_thr  as for mhaq_fq_od_keys: the same candidate rule, the same 64-bit key
+ *   max_nms         K = min(A * nc, max_nms) keys are kept per image
+ *   skeys           [B][K] int64, 8-byte aligned.  Row b holds the first min(n_cand[b], K) keys of image b in ascending order,
+ *                   every slot behind them INT64_MAX: bit for bit the first K elements of the sorted row b of
+ *                   mhaq_fq_od_keys.
+ *   n_cand          [B] int32, the image's candidates; may exceed max_nms
+ *   workspace       mhaq_fq_od_sorted_keys_workspace_bytes(B, nc, A, max_nms) bytes, 8-byte aligned.  The counts are known on
+ *                   the device only, so it is sized for every pair a candidate in every image:
+ *                     2 * B * A * nc * 8                               two key rows per image, written in turn
+ *                   + round8(B * A * 4) + round8(B * ceil(A / 256) * 4)  candidates per anchor and per tile of 256 anchors
+ *                   + B * ceil(A * nc / T) * 256 * 4                   digit counts per sort tile, T = mhaq_fq_od_sort_tile()
+ *                   (0 for arguments the call would refuse).
+ *   The compacted row is ascending in the key's low word (a * nc + c), so a stable sort by the 31 bits of the score word is
+ *   the 64-bit order: four passes.  Work and traffic of the passes follow n_cand, not A * nc; the grids are launched for the
+ *   worst case and a tile beyond an image's candidates leaves at once.
+ *   Errors, before any launch: those of mhaq_fq_od_keys; also NULL n_cand / workspace, max_nms < 1 (MHAQ_FQ_EINVAL); n_cand
+ *   not 4-byte or workspace not 8-byte aligned (MHAQ_FQ_EALIGN); a short workspace (MHAQ_FQ_EWORKSPACE).
+ *
+ * mhaq_fq_od_nms_rows: mhaq_fq_od_nms on compact rows.  Identical to it except that row b starts at skeys + b * key_stride,
+ *   the image's candidate count is n_cand_in[b] (no binary search; a negative one counts as 0), the walk is limited to
+ *   min(n_cand_in[b], max_nms, key_stride) keys, bit 1 of flags is set when n_cand_in[b] > max_nms, and n_cand is a copy of
+ *   n_cand_in (two different arrays).  key_stride >= 1; n_cand_in [B] int32, 4-byte aligned, not NULL.
+ * Both: stream-ordered, capture-safe, stateless, no host synchronisation, no global atomics, no workgroup waits for another;
+ * the same inputs give the same bits at every call.
+ * ---------------------------------------------------------------------- */
+int mhaq_fq_od_sort_tile(void);
+size_t mhaq_fq_od_sorted_keys_workspace_bytes(int64_t B, int64_t nc, int64_t A, int max_nms);
+int mhaq_fq_od_sorted_keys(const void* pred, int pred_dtype, int64_t B, int64_t nc, int64_t A, float conf_thr, int max_nms,
+                           int64_t* skeys /* [B][min(A*nc, max_nms)] */, int32_t* n_cand /* [B] */,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int mhaq_fq_od_nms_rows(const void* pred, int pred_dtype, const int64_t* skeys, int64_t key_stride,
+                        const int32_t* n_cand_in /* [B] */, int64_t B, int64_t nc, int64_t A, float iou_thr, float max_wh,
+                        int max_nms, int max_det, float* det /* [B][max_det][6] */, int32_t* count /* [B] */,
+                        int32_t* n_cand /* [B] */, uint32_t* flags /* [1] */, void* workspace, size_t workspace_bytes,
+                        void* stream);
 
 /* ------------------------------------------------------------------------
  * Super-resolution validation metrics: per-image PSNR and SSIM of the clamped prediction against the target and the L1

@@ -102,6 +102,13 @@ SIGNATURES = {
     "mhaq_fq_od_keys": (_int, [_p, _int, _i64, _i64, _i64, C.c_float, _p, _p]),
     "mhaq_fq_od_nms_workspace_bytes": (_sz, [_i64]),
     "mhaq_fq_od_nms": (_int, [_p, _int, _p, _i64, _i64, _i64, C.c_float, C.c_float, _int, _int, _p, _p, _p, _p, _p, _sz, _p]),
+    # the library's own sort.  sorted_keys: pred, dtype, B, nc, A, conf_thr, max_nms, skeys, n_cand, workspace.  nms_rows: as
+    # nms with key_stride and n_cand_in after the keys
+    "mhaq_fq_od_sort_tile": (_int, []),
+    "mhaq_fq_od_sorted_keys_workspace_bytes": (_sz, [_i64, _i64, _i64, _int]),
+    "mhaq_fq_od_sorted_keys": (_int, [_p, _int, _i64, _i64, _i64, C.c_float, _int, _p, _p, _p, _sz, _p]),
+    "mhaq_fq_od_nms_rows": (_int, [_p, _int, _p, _i64, _p, _i64, _i64, _i64, C.c_float, C.c_float, _int, _int, _p, _p, _p, _p,
+                                   _p, _sz, _p]),
     "mhaq_fq_od_match_workspace_bytes": (_sz, [_i64]),
     "mhaq_fq_od_match": (_int, [_p, _p, _i64, _int, _i64, _p, _p, _p, _i64, _p, _p, _p, _sz, _p]),
     # super-resolution validation metrics: sr, sr_dtype, hr, hr_dtype, n, c, h, w, sr_div, to_luminance, pool, psnr, ssim,

@@ -16,13 +16,7 @@
 //   match  one workgroup of ten wavefronts per image, wavefront k = IoU threshold T_k, lanes over the image's ground truth;
 //          per detection one arg-max reduction over the lanes.
 // No atomics: every word has one writer.  The same inputs give the same bits at every call.
-#include <hip/hip_runtime.h>
-
-#include <type_traits>
-
-#include "../../include/mhaq_fq.h"
-#include "fq_common.hpp"
-#include "fq_io16.hpp"
+#include "od_common.hpp"
 
 namespace mhaq {
 
@@ -30,13 +24,6 @@ constexpr int kOdChunk = kBlock;          // candidates per sweep of the NMS wor
 constexpr int kOdMaxDet = 1024;           // kept boxes held in LDS: 20 KiB
 constexpr int kOdThr = 10;                // COCO's IoU thresholds
 constexpr int kOdMatchBlock = kOdThr * kWave;
-constexpr int64_t kOdNoKey = 0x7fffffffffffffffLL;
-
-template <int DT>
-__device__ __forceinline__ float od_ld(const void* p, int64_t i) {
-  if constexpr (DT == MHAQ_FQ_DT_F32) return ldg(static_cast<const float*>(p) + i);
-  else return io16::up1<DT>(*gptr(static_cast<const uint16_t*>(p) + i));
-}
 
 // min / max of the contract: a comparison and a select, so that a NaN (which compares false) has one defined outcome.
 // `a` is the kept box's (the detection's) value, `b` the candidate's (the ground truth's).
@@ -51,7 +38,6 @@ __device__ __forceinline__ float od_iou(od_f4 a, float area_a, od_f4 b, float ar
   const float inter = iw * ih;
   return inter / ((area_a + area_b) - inter);                 // 0 / 0 = NaN: compares false everywhere
 }
-__host__ __device__ __forceinline__ bool od_finite(float v) { return fabsf(v) <= 3.4028234663852886e38f; }      // false for a NaN
 
 // ---------------------------------------------------------------- keys
 template <int DT>
@@ -63,7 +49,7 @@ __global__ __launch_bounds__(kBlock) void od_keys_kernel(const void* __restrict_
   const float s = od_ld<DT>(pred, (b * (4 + nc) + 4 + c) * A + a);
   int64_t key = kOdNoKey;
   if (s > conf_thr)                                           // false for a NaN; conf_thr >= 0, so the bits are a positive int32
-    key = (int64_t)(((uint64_t)(uint32_t)(0x7fffffff - (int32_t)__float_as_uint(s)) << 32) | (uint32_t)(a * nc + c));
+    key = od_key(s, a, nc, c);
   *gptr(keys + (b * nc + c) * A + a) = key;
 }
 
@@ -99,26 +85,36 @@ __device__ __forceinline__ OdCand od_gather(const void* __restrict__ img, const 
   return k;
 }
 
-template <int DT>
+// ROWS = false: the rows of mhaq_fq_od_keys sorted whole (stride A * nc, the count from a binary search).  ROWS = true
+// (mhaq_fq_od_nms_rows): compact rows of `key_stride` keys whose candidate counts the caller hands in.
+template <int DT, bool ROWS>
 __global__ __launch_bounds__(kOdChunk) void od_nms_kernel(const void* __restrict__ pred, const int64_t* __restrict__ keys,
                                                           int A, int nc, float iou_thr, float max_wh, int max_nms,
                                                           int max_det, float* __restrict__ det, int32_t* __restrict__ count,
-                                                          int32_t* __restrict__ n_cand, uint32_t* __restrict__ img_flags) {
+                                                          int32_t* __restrict__ n_cand, uint32_t* __restrict__ img_flags,
+                                                          int64_t key_stride, const int32_t* __restrict__ n_cand_in) {
   __shared__ od_f4 s_box[kOdMaxDet];
   __shared__ float s_area[kOdMaxDet];
   __shared__ uint64_t s_alive[kOdChunk / kWave];
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t b = blockIdx.x, N = (int64_t)A * nc;
-  const int64_t* krow = keys + b * N;
+  const int64_t* krow = keys + b * (ROWS ? key_stride : N);
   const void* img = static_cast<const char*>(pred) + b * (4 + nc) * (int64_t)A * (DT == MHAQ_FQ_DT_F32 ? 4 : 2);
   float* drow = det + b * max_det * 6;
   // candidates of the image = position of the first INT64_MAX of its sorted row (uniform: every thread walks the same path)
   int64_t lo = 0, hi = N;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (*gptr(krow + mid) == kOdNoKey) hi = mid; else lo = mid + 1;
+  if constexpr (ROWS) {
+    const int32_t n = *gptr(n_cand_in + b);
+    lo = n < 0 ? 0 : n;
+  } else {
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (*gptr(krow + mid) == kOdNoKey) hi = mid; else lo = mid + 1;
+    }
   }
-  const int64_t ncand = lo, limit = ncand < max_nms ? ncand : (int64_t)max_nms;
+  const int64_t ncand = lo;
+  int64_t limit = ncand < max_nms ? ncand : (int64_t)max_nms;
+  if (ROWS && limit > key_stride) limit = key_stride;
   int cnt = 0;
   bool nonfinite = false;
   OdCand nxt = od_gather<DT>(img, krow, tid, limit, A, nc, max_wh);
@@ -241,17 +237,6 @@ __global__ __launch_bounds__(kOdMatchBlock) void od_match_kernel(const float* __
   }
 }
 
-template <class F>
-void od_with_dtype(int dtype, F f) {
-  if (dtype == MHAQ_FQ_DT_F32) f(std::integral_constant<int, MHAQ_FQ_DT_F32>{});
-  else if (dtype == MHAQ_FQ_DT_BF16) f(std::integral_constant<int, MHAQ_FQ_DT_BF16>{});
-  else f(std::integral_constant<int, MHAQ_FQ_DT_F16>{});
-}
-inline bool od_dtype_known(int dt) { return dt == MHAQ_FQ_DT_F32 || dt == MHAQ_FQ_DT_BF16 || dt == MHAQ_FQ_DT_F16; }
-inline bool od_shape_supported(int64_t B, int64_t nc, int64_t A) {
-  return B <= 65535 && nc <= 65535 && A <= 0x7fffffff && A * nc <= 0x7fffffff;
-}
-
 }  // namespace mhaq
 
 using namespace mhaq;
@@ -276,27 +261,50 @@ int mhaq_fq_od_keys(const void* pred, int pred_dtype, int64_t B, int64_t nc, int
 
 size_t mhaq_fq_od_nms_workspace_bytes(int64_t B) { return B > 0 ? (((size_t)B * 4 + 7) & ~(size_t)7) : 0; }
 
-int mhaq_fq_od_nms(const void* pred, int pred_dtype, const int64_t* keys, int64_t B, int64_t nc, int64_t A, float iou_thr,
-                   float max_wh, int max_nms, int max_det, float* det, int32_t* count, int32_t* n_cand, uint32_t* flags,
-                   void* workspace, size_t workspace_bytes, void* stream) {
+// the body of mhaq_fq_od_nms (n_cand_in == NULL, key_stride = A * nc) and of mhaq_fq_od_nms_rows
+static int od_nms_launch(const void* pred, int pred_dtype, const int64_t* keys, int64_t key_stride, const int32_t* n_cand_in,
+                         bool rows, int64_t B, int64_t nc, int64_t A, float iou_thr, float max_wh, int max_nms, int max_det,
+                         float* det, int32_t* count, int32_t* n_cand, uint32_t* flags, void* workspace,
+                         size_t workspace_bytes, void* stream) {
   if (!pred || !keys || !det || !count || !n_cand || !flags || !workspace || !od_dtype_known(pred_dtype) || B < 1 ||
-      nc < 1 || A < 1 || max_nms < 1 || max_det < 1)
+      nc < 1 || A < 1 || max_nms < 1 || max_det < 1 || (rows && (!n_cand_in || key_stride < 1)))
     return MHAQ_FQ_EINVAL;
   if (iou_thr != iou_thr || !od_finite(max_wh)) return MHAQ_FQ_EINVAL;
   if (workspace_bytes < mhaq_fq_od_nms_workspace_bytes(B)) return MHAQ_FQ_EWORKSPACE;
   if (((uintptr_t)pred & (pred_dtype == MHAQ_FQ_DT_F32 ? 3 : 1)) || ((uintptr_t)keys & 7) || ((uintptr_t)det & 3) ||
-      ((uintptr_t)count & 3) || ((uintptr_t)n_cand & 3) || ((uintptr_t)flags & 3) || ((uintptr_t)workspace & 3))
+      ((uintptr_t)count & 3) || ((uintptr_t)n_cand & 3) || ((uintptr_t)flags & 3) || ((uintptr_t)workspace & 3) ||
+      ((uintptr_t)n_cand_in & 3))
     return MHAQ_FQ_EALIGN;
   if (!od_shape_supported(B, nc, A) || max_det > kOdMaxDet) return MHAQ_FQ_EUNSUPPORTED;
   uint32_t* img_flags = static_cast<uint32_t*>(workspace);
   const hipStream_t st = (hipStream_t)stream;
   od_with_dtype(pred_dtype, [&](auto dt) {
-    MHAQ_LAUNCH(od_nms_kernel<decltype(dt)::value>, dim3((unsigned)B), dim3(kOdChunk), 0, st, pred, keys, (int)A, (int)nc,
-                iou_thr, max_wh, max_nms, max_det, det, count, n_cand, img_flags);
+    constexpr int DT = decltype(dt)::value;
+    if (rows)
+      MHAQ_LAUNCH((od_nms_kernel<DT, true>), dim3((unsigned)B), dim3(kOdChunk), 0, st, pred, keys, (int)A, (int)nc, iou_thr,
+                  max_wh, max_nms, max_det, det, count, n_cand, img_flags, key_stride, n_cand_in);
+    else
+      MHAQ_LAUNCH((od_nms_kernel<DT, false>), dim3((unsigned)B), dim3(kOdChunk), 0, st, pred, keys, (int)A, (int)nc, iou_thr,
+                  max_wh, max_nms, max_det, det, count, n_cand, img_flags, key_stride, n_cand_in);
   });
   if (launch_status() != 0) return launch_status();
   MHAQ_LAUNCH(od_flags_kernel, dim3(1), dim3(kBlock), 0, st, (const uint32_t*)img_flags, B, flags);
   return launch_status();
+}
+
+int mhaq_fq_od_nms(const void* pred, int pred_dtype, const int64_t* keys, int64_t B, int64_t nc, int64_t A, float iou_thr,
+                   float max_wh, int max_nms, int max_det, float* det, int32_t* count, int32_t* n_cand, uint32_t* flags,
+                   void* workspace, size_t workspace_bytes, void* stream) {
+  return od_nms_launch(pred, pred_dtype, keys, A * nc, nullptr, false, B, nc, A, iou_thr, max_wh, max_nms, max_det, det,
+                       count, n_cand, flags, workspace, workspace_bytes, stream);
+}
+
+int mhaq_fq_od_nms_rows(const void* pred, int pred_dtype, const int64_t* skeys, int64_t key_stride, const int32_t* n_cand_in,
+                        int64_t B, int64_t nc, int64_t A, float iou_thr, float max_wh, int max_nms, int max_det, float* det,
+                        int32_t* count, int32_t* n_cand, uint32_t* flags, void* workspace, size_t workspace_bytes,
+                        void* stream) {
+  return od_nms_launch(pred, pred_dtype, skeys, key_stride, n_cand_in, true, B, nc, A, iou_thr, max_wh, max_nms, max_det, det,
+                       count, n_cand, flags, workspace, workspace_bytes, stream);
 }
 
 size_t mhaq_fq_od_match_workspace_bytes(int64_t G) { return G > 0 ? (((size_t)G * kOdThr + 7) & ~(size_t)7) : 0; }

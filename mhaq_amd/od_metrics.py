@@ -22,15 +22,18 @@ IOU_THRESHOLDS = np.linspace(0.5, 0.95, 10)      # T_k of od_match's bit k
 
 
 def od_nms(pred: torch.Tensor, conf_thr: float = 0.001, iou_thr: float = 0.65, max_det: int = 100, max_nms: int = 30000,
-           max_wh: float = 7680.0) -> dict:
+           max_wh: float = 7680.0, sort: str | None = None) -> dict:
     """Non-maximum suppression of a batch.  `pred` is what the YOLO head returns in eval mode: a contiguous [B, 4 + nc, A]
     tensor on the GPU (float32, bfloat16 or float16), rows 0-3 cx, cy, w, h in pixels, rows 4.. the sigmoided class scores.
     Returns device tensors: `det` ([B, max_det, 6] float32: x1, y1, x2, y2, score, class in kept order, zero rows beyond the
     count), `count` and `n_candidates` ([B] int32) and `flags` (one int32 word for check_od_flags), and `num_classes` (the
-    host integer od_match needs).  The defaults are the reference's.  Nothing here waits for the device."""
+    host integer od_match needs).  The defaults are the reference's.  `sort` chooses how the candidates are ordered: "lib"
+    (the library's compaction and segmented radix sort, csrc/od_sort.hip), "torch" (torch.sort of the whole key rows) or None
+    (the environment variable MHAQ_OD_SORT, else ops' default); the record is the same bits either way.  Nothing here waits
+    for the device."""
     if not isinstance(pred, torch.Tensor):
         raise TypeError("pred must be a tensor")
-    det, count, n_cand, flags = ops.od_nms(pred.detach(), conf_thr, iou_thr, max_wh, max_nms, max_det)
+    det, count, n_cand, flags = ops.od_nms(pred.detach(), conf_thr, iou_thr, max_wh, max_nms, max_det, sort=sort)
     return {"det": det, "count": count, "n_candidates": n_cand, "flags": flags, "num_classes": pred.shape[1] - 4}
 
 

@@ -1029,21 +1029,81 @@ def od_nms_sorted(pred, keys, iou_thr, max_wh, max_nms, max_det):
     b, nc, a = _od_pred(pred)
     if keys.dtype != torch.int64 or keys.shape != (b, a * nc) or not keys.is_contiguous() or keys.device != pred.device:
         raise ValueError(f"keys must be a contiguous int64 [{b}, {a * nc}] tensor on {pred.device}")
+    return _od_nms_launch(pred, keys, None, iou_thr, max_wh, max_nms, max_det)
+
+
+def _od_nms_launch(pred, keys, n_cand_in, iou_thr, max_wh, max_nms, max_det):
+    """mhaq_fq_od_nms (n_cand_in None: whole sorted rows) or mhaq_fq_od_nms_rows (compact rows and their counts)."""
+    b, nc, a = _od_pred(pred)
     L = _lib.lib()
     nb = L.mhaq_fq_od_nms_workspace_bytes(b)
     ws = _workspace(nb, pred.device)
     det = torch.empty((b, int(max_det), 6), dtype=torch.float32, device=pred.device)
     words = torch.empty(2 * b + 1, dtype=torch.int32, device=pred.device)           # count, n_cand, flags
     count, n_cand, flags = words[:b], words[b:2 * b], words[2 * b:]
-    _lib.check(L.mhaq_fq_od_nms(pred.data_ptr(), _SR_DT[pred.dtype], keys.data_ptr(), b, nc, a, float(iou_thr), float(max_wh),
-                                int(max_nms), int(max_det), det.data_ptr(), count.data_ptr(), n_cand.data_ptr(),
-                                flags.data_ptr(), ws.data_ptr(), nb, _stream()), "mhaq_fq_od_nms")
+    tail = (b, nc, a, float(iou_thr), float(max_wh), int(max_nms), int(max_det), det.data_ptr(), count.data_ptr(),
+            n_cand.data_ptr(), flags.data_ptr(), ws.data_ptr(), nb, _stream())
+    if n_cand_in is None:
+        _lib.check(L.mhaq_fq_od_nms(pred.data_ptr(), _SR_DT[pred.dtype], keys.data_ptr(), *tail), "mhaq_fq_od_nms")
+    else:
+        _lib.check(L.mhaq_fq_od_nms_rows(pred.data_ptr(), _SR_DT[pred.dtype], keys.data_ptr(), keys.shape[1],
+                                         n_cand_in.data_ptr(), *tail), "mhaq_fq_od_nms_rows")
     return det, count, n_cand, flags
 
 
-def od_nms(pred, conf_thr, iou_thr, max_wh, max_nms, max_det):
-    """The three stages on one prediction: od_keys, torch.sort of the key rows (plumbing: the library brings no segmented
-    sort, a C caller its own), od_nms_sorted."""
+def od_sort_tile() -> int:
+    """Keys per tile of the segmented radix sort (mhaq_fq_od_sort_tile)."""
+    return int(_lib.lib().mhaq_fq_od_sort_tile())
+
+
+@_on_device
+def od_sorted_keys(pred, conf_thr, max_nms):
+    """mhaq_fq_od_sorted_keys: the candidates of every image compacted and sorted by the library's segmented radix sort, no
+    host synchronisation.  Returns (skeys [B, min(A * nc, max_nms)] int64 -- the head of each sorted row of od_keys, on bits --,
+    n_cand [B] int32)."""
+    b, nc, a = _od_pred(pred)
+    max_nms = min(int(max_nms), 0x7fffffff)
+    L = _lib.lib()
+    skeys = torch.empty((b, max(min(a * nc, max_nms), 1)), dtype=torch.int64, device=pred.device)
+    n_cand = torch.empty(b, dtype=torch.int32, device=pred.device)
+    nb = L.mhaq_fq_od_sorted_keys_workspace_bytes(b, nc, a, max_nms)
+    ws = _workspace(max(nb, 8), pred.device)
+    _lib.check(L.mhaq_fq_od_sorted_keys(pred.data_ptr(), _SR_DT[pred.dtype], b, nc, a, float(conf_thr), max_nms,
+                                        skeys.data_ptr(), n_cand.data_ptr(), ws.data_ptr(), nb, _stream()),
+               "mhaq_fq_od_sorted_keys")
+    return skeys, n_cand
+
+
+@_on_device
+def od_nms_rows(pred, skeys, n_cand, iou_thr, max_wh, max_nms, max_det):
+    """mhaq_fq_od_nms_rows on `pred` and what od_sorted_keys returns: two launches, no host synchronisation.  Returns what
+    od_nms_sorted returns."""
+    b, _, _ = _od_pred(pred)
+    if skeys.dtype != torch.int64 or skeys.dim() != 2 or skeys.shape[0] != b or skeys.shape[1] < 1 or \
+            not skeys.is_contiguous() or skeys.device != pred.device:
+        raise ValueError(f"skeys must be a contiguous int64 [{b}, K] tensor on {pred.device}")
+    if n_cand.dtype != torch.int32 or tuple(n_cand.shape) != (b,) or not n_cand.is_contiguous() or \
+            n_cand.device != pred.device:
+        raise ValueError(f"n_cand must be a contiguous int32 [{b}] tensor on {pred.device}")
+    return _od_nms_launch(pred, skeys, n_cand, iou_thr, max_wh, max_nms, max_det)
+
+
+# Which sort od_nms runs when neither its argument nor MHAQ_OD_SORT says: "lib" (od_sorted_keys, od_nms_rows) or "torch"
+# (od_keys, torch.sort of the whole key rows, od_nms_sorted).  Both give the same bits; the library sort's median lies below
+# torch.sort's minimum on both recorded shapes, sparse and dense (profiles/r27_od_sort_micro.txt, DESIGN section 18a).
+_OD_SORT_DEFAULT = "lib"
+
+
+def od_nms(pred, conf_thr, iou_thr, max_wh, max_nms, max_det, sort=None):
+    """The stages on one prediction.  sort="lib": the library's compaction and segmented sort of the candidates, then the NMS
+    on the compact rows.  sort="torch": od_keys, torch.sort of the key rows, od_nms_sorted.  None: the environment variable
+    MHAQ_OD_SORT, else the default.  The outputs are the same bits either way."""
+    sort = sort or os.environ.get("MHAQ_OD_SORT") or _OD_SORT_DEFAULT
+    if sort == "lib":
+        skeys, n_cand = od_sorted_keys(pred, conf_thr, max_nms)
+        return od_nms_rows(pred, skeys, n_cand, iou_thr, max_wh, max_nms, max_det)
+    if sort != "torch":
+        raise ValueError(f"sort must be 'lib' or 'torch', got {sort!r}")
     keys = od_keys(pred, conf_thr)
     return od_nms_sorted(pred, torch.sort(keys, dim=1).values, iou_thr, max_wh, max_nms, max_det)
 

@@ -8,6 +8,11 @@ The NMS stage's time depends on the data, so each shape is timed in two regimes 
 20-200 px at random places of the image):
   sparse   scores = sigmoid(1.5 * z - 10), z normal: about 2 % of the (anchor, class) pairs are candidates, below max_nms
   dense    scores uniform in (0, 1): every pair is a candidate, every image is cut to max_nms = 30000 (the worst case)
+The library's own sort stage (mhaq_fq_od_sorted_keys: compaction of the candidates and a segmented radix sort of only them,
+csrc/od_sort.hip) is timed beside the key launch and torch.sort that it replaces, in the same loop, the two sides alternating,
+and so is the NMS on its compact rows (mhaq_fq_od_nms_rows) beside the NMS on whole rows; a second table has the median and
+the min-max of each side and the peak extra memory of both, counted from the shapes.  The library sort is called "faster" on
+a line only where its median lies below the minimum of the torch.sort stage ALONE (it also does the key launch's work).
 Times: HIP events around one call of a stage, --reps timed calls after --warmup, the stages in turn, over --buffers different
 predictions in rotation (no call finds its own input warm in a cache); median and minimum in microseconds.  A stage is
 enqueued by the host one call at a time, so a figure is the larger of its device work and its enqueue time.
@@ -68,7 +73,7 @@ def bench(shape, regime, reps, warmup, nbuf):
     preds = [prediction(shape, regime, 100 + i) for i in range(nbuf)]
     gt_box, gt_label, gt_off = ground_truth(shape, 7)
     nc = shape[1] - 4
-    t = {k: [] for k in ("keys", "sort", "nms", "match")}
+    t = {k: [] for k in ("keys", "sort", "nms", "match", "libsort", "nmsrows")}
     info = None
     for i in range(warmup + reps):
         pred = preds[i % nbuf]
@@ -76,12 +81,25 @@ def bench(shape, regime, reps, warmup, nbuf):
         skeys, t_sort = timed(lambda: torch.sort(keys, dim=1).values)
         (det, count, n_cand, flags), t_nms = timed(lambda: ops.od_nms_sorted(pred, skeys, IOU, MAX_WH, MAX_NMS, MAX_DET))
         _, t_match = timed(lambda: ops.od_match(det, count, gt_box, gt_label, gt_off, nc, flags))
+        (lkeys, lcand), t_lib = timed(lambda: ops.od_sorted_keys(pred, CONF, MAX_NMS))
+        lib, t_rows = timed(lambda: ops.od_nms_rows(pred, lkeys, lcand, IOU, MAX_WH, MAX_NMS, MAX_DET))
+        if i == 0 and not all(torch.equal(x, y) for x, y in zip(lib, (det, count, n_cand, flags))):
+            raise SystemExit("the two sort paths differ on %s %s" % (shape, regime))
         if i >= warmup:
-            for k, v in zip(t, (t_keys, t_sort, t_nms, t_match)):
+            for k, v in zip(t, (t_keys, t_sort, t_nms, t_match, t_lib, t_rows)):
                 t[k].append(v)
         if info is None:
             info = (float(n_cand.float().mean()), float(count.float().mean()), int(flags.item()))
-    return {k: (statistics.median(v), min(v)) for k, v in t.items()}, info
+    return {k: (statistics.median(v), min(v), max(v)) for k, v in t.items()}, info
+
+
+def extra_mib(shape):
+    """Peak extra device memory of the two sort stages in MiB, from the shapes: torch.sort holds the key rows, its values and
+    indices and about one row-sized temporary more (4 int64 rows of A * nc); the library sort its workspace and compact rows."""
+    B, rows, A, _ = shape
+    n = B * A * (rows - 4)
+    return 4 * n * 8 / 2 ** 20, (ops._lib.lib().mhaq_fq_od_sorted_keys_workspace_bytes(B, rows - 4, A, MAX_NMS)
+                                 + B * min(A * (rows - 4), MAX_NMS) * 8) / 2 ** 20
 
 
 def main():
@@ -99,9 +117,18 @@ def main():
              "# %-14s %-7s %10s %8s %5s | %9s %9s | %9s %9s | %9s %9s | %9s %9s | %10s"
              % ("shape", "regime", "candidates", "kept", "flags", "keys med", "keys min", "sort med", "sort min", "nms med",
                 "nms min", "match med", "match min", "sort share")]
+    sort_lines = ["# the sort stage, both sides in one loop in turn: median (min-max) in microseconds; extra memory in MiB",
+                  "# %-14s %-7s | %-28s | %-28s | %-28s | %-7s | %-24s | %s"
+                  % ("shape", "regime", "torch.sort", "keys + torch.sort (medians)", "lib sorted_keys", "verdict",
+                     "nms whole / compact rows", "extra MiB torch / lib")]
     for shape in SHAPES:
         for regime in REGIMES:
             r, (cand, kept, flags) = bench(shape, regime, a.reps, a.warmup, a.buffers)
+            r, full = {k: v[:2] for k, v in r.items()}, r
+            verdict = "faster" if full["libsort"][0] < full["sort"][1] else "not faster"
+            sort_lines.append("  %-14s %-7s | %8.1f (%8.1f-%8.1f) | %28.1f | %8.1f (%8.1f-%8.1f) | %-7s | %10.1f / %10.1f | %.1f / %.1f"
+                              % ("%dx%dx%d" % shape[:3], regime, *full["sort"], full["keys"][0] + full["sort"][0],
+                                 *full["libsort"], verdict, full["nms"][0], full["nmsrows"][0], *extra_mib(shape)))
             three = r["keys"][0] + r["sort"][0] + r["nms"][0]
             lines.append("  %-14s %-7s %10.0f %8.1f %5d | %9.1f %9.1f | %9.1f %9.1f | %9.1f %9.1f | %9.1f %9.1f | %9.0f%%"
                          % ("%dx%dx%d" % shape[:3], regime, cand, kept, flags, *r["keys"], *r["sort"], *r["nms"], *r["match"],
@@ -109,6 +136,8 @@ def main():
             print(lines[-1], flush=True)
     lines.append("# candidates / kept: means per image of the first prediction; sort share: the sort's median over the sum of "
                  "the three stages' medians")
+    lines += sort_lines
+    print("\n".join(sort_lines), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
