@@ -794,6 +794,71 @@ int mhaq_fq_od_nms_rows(const void* pred, int pred_dtype, const int64_t* skeys, 
                         void* stream);
 
 /* ------------------------------------------------------------------------
+ * Object-detection training: the YOLO task-aligned target assignment (the reference's Assigner.forward,
+ * src/models/od/loss/yolo_loss.py:140-232) in three launches.  Additive to ABI v4 -- MHAQ_FQ_ABI_VERSION stays 4; a caller
+ * discovers these entry points by symbol.
+ *   pd_scores     [b][a][nc] sigmoided class scores and
+ *   pd_bboxes     [b][a][4] predicted boxes, xyxy in pixels; both of the type named by pd_dtype (MHAQ_FQ_DT_F32,
+ *                 MHAQ_FQ_DT_BF16 or MHAQ_FQ_DT_F16), aligned to its element size, converted up exactly
+ *   anc_points    [a][2] fp32 anchor centres in pixels
+ *   gt_labels     [b][g] fp32, integer-valued;  gt_bboxes [b][g][4] fp32 xyxy;  mask_gt [b][g] fp32, 0 = a padding row
+ * All arithmetic is fp32 with no contraction and IEEE division and square root.  The contract restates yolo_loss.py:150-232;
+ * it is not a recording.  Per image, ground truth g and anchor a = (ax, ay), with k = top_k:
+ *  1. in(g,a) = ax - x1g > eps and ay - y1g > eps and x2g - ax > eps and y2g - ay > eps (:162-164: amin(...).gt_(eps), false for
+ *     a NaN).  valid(g) = mask_gt[g] != 0 and 0 <= gt_labels[g] < nc (:166).
+ *  2. Where in and valid (:167-179): ov(g,a) = max(CIoU(gt_g, pd_a), 0) by compute_iou's formula (:20-46) in its order of
+ *     operations, box1 = the ground truth, box2 = the prediction, eps = 1e-7;  sc(g,a) = pd_scores[a][label_g];
+ *     m(g,a) = sc^alpha * ov^beta (a metric that is not > 0 counts as 0).  Elsewhere all three are 0.  An exponent of 0.5 is
+ *     sqrtf, an integer one in [1, 64] a chain of multiplications, any other powf.
+ *  3. Per valid g the k best anchors over ALL a by (m descending, anchor index ascending) (:182; torch.topk leaves ties
+ *     unspecified, this library fixes them).  A chosen anchor counts only if in(g,a): that is mask_pos (:187-193).
+ *  4. cnt(a) = sum over g of mask_pos (:195).  Where cnt(a) > 1 the anchor goes to argmax over ALL g of ov(g,a), the lowest g on
+ *     a tie (:196-204) -- the reference's rule, with its quirk that the winner need not have had the anchor in its top-k, nor,
+ *     when every overlap is 0, hold it at all.  fg(a) = cnt(a) > 0, gt_idx(a) = the ground truth of a foreground anchor, else 0
+ *     (:205).
+ *  5. target_bboxes[a] = gt_bboxes[gt_idx(a)] for EVERY anchor: a background anchor receives ground truth 0's box (:212).
+ *  6. label(a) = max(gt_labels[gt_idx(a)], 0) (:210, :215).
+ *  7. Per g: pam(g) = max over a of m * mask_pos, pov(g) = max over a of ov * mask_pos on the final mask_pos (:226-228).
+ *  8. norm(a) = (m(gt_idx, a) * pov) / (pam + eps) for a foreground anchor whose m is > 0, else 0 (:229; with eps == 0 the
+ *     reference has 0 / 0 where m is 0).
+ *  9. target_scores[a][:] = 0 except target_scores[a][label(a)] = norm(a) where fg(a) (:217-230); no address is formed from a
+ *     label: one outside [0, nc) leaves its row zero.
+ * 10. scores_sum = sum over all images and anchors of norm(a) (what the caller's target_scores.sum() is, :322): accumulated in
+ *     fp64 in a fixed order, rounded once to fp32.
+ * Deviations from the reference: the tie orders of 3 and 4 are fixed; fg_mask is 0 / 1 bytes also when g == 0 (the reference
+ * returns float zeros there); there is no host read -- the multi-assignment step (4) always runs and is the identity where no
+ * cnt(a) > 1 (:196 reads the device); a NaN or infinite coordinate or score in an in-box pair of a valid ground truth gives
+ * that pair ov = m = 0 and sets bit 0 (value 1) of flags; a label outside [0, nc) on a row whose mask is set makes that ground
+ * truth invalid and sets bit 2 (value 4).  The bits are those of mhaq_fq_od_nms / mhaq_fq_od_match.
+ *   target_bboxes [b][a][4] fp32;  target_scores [b][a][nc] fp32, every element written (no fill precedes the call)
+ *   fg_mask       [b][a] bytes 0 / 1;  target_gt_idx [b][a] int32
+ *   scores_sum    [1] fp32;  flags [1] device word, WRITTEN by the call
+ *   workspace     mhaq_fq_od_assign_workspace_bytes(b, g, a, top_k) bytes, 8-byte aligned: per image one fp64 partial sum and
+ *                 one flag word, per ground truth its k chosen anchors (int32, -1 = none) and one flag word, per anchor its label
+ *                 and norm -- O(b * g * k + b * a); no [b][g][a] array exists anywhere.  0 for arguments the call would refuse
+ *                 and for b * a == 0.
+ * Launches: one workgroup per (image, ground truth) selects the k anchors (metrics in 4 * a bytes of LDS, k rounds of a
+ * workgroup-wide maximum of 64-bit keys metric bits << 32 | ~anchor); one workgroup per image resolves multi-assignment and
+ * writes compact rows (4 * a + 28 * g bytes of dynamic LDS; each kernel has under 512 bytes of static LDS besides); an elementwise launch writes the dense outputs.  g == 0: no ground truth,
+ * the first launch is left out, outputs are zero and gt_* may be NULL.  b * a == 0: only scores_sum = 0 and flags = 0 are
+ * written and every other pointer may be NULL.
+ * Errors, before any launch: NULL scores_sum / flags, b, a or g < 0, nc or top_k < 1, an unknown dtype, alpha, beta or eps
+ * negative, NaN or infinite; with b * a > 0 a NULL input (gt_* only if g > 0), output or workspace, or a < top_k (the
+ * reference's topk raises there) (MHAQ_FQ_EINVAL); b or nc > 65535, a > 24576, g > 1024, top_k > 32 (MHAQ_FQ_EUNSUPPORTED); a
+ * short workspace (MHAQ_FQ_EWORKSPACE); a prediction not aligned to its element size, workspace not 8-byte or another pointer
+ * not 4-byte aligned (MHAQ_FQ_EALIGN).
+ * Stream-ordered, capture-safe, stateless, no host synchronisation, no global atomics, no workgroup waits for another; the
+ * same inputs give the same bits at every call.
+ * ---------------------------------------------------------------------- */
+size_t mhaq_fq_od_assign_workspace_bytes(int64_t b, int64_t g, int64_t a, int top_k);
+int mhaq_fq_od_assign(const void* pd_scores, const void* pd_bboxes, int pd_dtype, const float* anc_points /* [a][2] */,
+                      const float* gt_labels /* [b][g] */, const float* gt_bboxes /* [b][g][4] */,
+                      const float* mask_gt /* [b][g] */, int64_t b, int64_t a, int64_t nc, int64_t g, int top_k, float alpha,
+                      float beta, float eps, float* target_bboxes /* [b][a][4] */, float* target_scores /* [b][a][nc] */,
+                      uint8_t* fg_mask /* [b][a] */, int32_t* target_gt_idx /* [b][a] */, float* scores_sum /* [1] */,
+                      uint32_t* flags /* [1] */, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Super-resolution validation metrics: per-image PSNR and SSIM of the clamped prediction against the target and the L1
  * criterion on the unclamped one, in three launches.  Additive to ABI v4 -- MHAQ_FQ_ABI_VERSION stays 4; a caller discovers
  * these entry points by symbol.

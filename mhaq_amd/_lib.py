@@ -111,6 +111,12 @@ SIGNATURES = {
                                    _p, _sz, _p]),
     "mhaq_fq_od_match_workspace_bytes": (_sz, [_i64]),
     "mhaq_fq_od_match": (_int, [_p, _p, _i64, _int, _i64, _p, _p, _p, _i64, _p, _p, _p, _sz, _p]),
+    # object-detection training, the task-aligned assignment (additive, ABI v4 kept): pd_scores, pd_bboxes, dtype, anc_points,
+    # gt_labels, gt_bboxes, mask_gt, b, a, nc, g, top_k, alpha, beta, eps, target_bboxes, target_scores, fg_mask,
+    # target_gt_idx, scores_sum, flags, workspace
+    "mhaq_fq_od_assign_workspace_bytes": (_sz, [_i64, _i64, _i64, _int]),
+    "mhaq_fq_od_assign": (_int, [_p, _p, _int, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _int, C.c_float, C.c_float, C.c_float,
+                                 _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     # super-resolution validation metrics: sr, sr_dtype, hr, hr_dtype, n, c, h, w, sr_div, to_luminance, pool, psnr, ssim,
     # l1, mean, flags, workspace (additive, ABI v4 kept)
     "mhaq_fq_sr_metrics_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _int, _int]),

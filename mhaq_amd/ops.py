@@ -1133,3 +1133,57 @@ def od_match(det, count, gt_box, gt_label, gt_off, nc, flags):
                                   gt_label.data_ptr() if g else None, gt_off.data_ptr(), g, tp.data_ptr(), flags.data_ptr(),
                                   ws.data_ptr(), nb, _stream()), "mhaq_fq_od_match")
     return tp
+
+
+# ------------------------------------------------------------------ object-detection training (no gradient, plain ctypes)
+@_on_device
+def od_assign(pd_scores, pd_bboxes, anc_points, gt_labels, gt_bboxes, mask_gt, top_k, alpha, beta, eps, out=None):
+    """mhaq_fq_od_assign: three launches, no host synchronisation.  `pd_scores` [B, A, nc] and `pd_bboxes` [B, A, 4] (one of
+    float32 / bfloat16 / float16 for both), `anc_points` [A, 2], `gt_labels` [B, G], `gt_bboxes` [B, G, 4] and `mask_gt` [B, G]
+    float32, all contiguous on one device.  Returns (target_bboxes [B, A, 4], target_scores [B, A, nc], fg_mask [B, A] bool,
+    target_gt_idx [B, A] int32, scores_sum [1], flags [1] int32); `out`, if given, is a tuple of the first four to write into
+    (fg_mask as uint8).  Shapes outside the library's ranges raise ValueError; there is no other path."""
+    if not pd_scores.is_cuda:
+        raise _lib.MhaqFqError(f"pd_scores is on {pd_scores.device}: the target assignment runs only as HIP kernels on an "
+                               "MI355X (no CPU fallback by design)")
+    if pd_scores.dtype not in _SR_DT or pd_bboxes.dtype != pd_scores.dtype:
+        raise TypeError(f"pd_scores and pd_bboxes must both be float32, bfloat16 or float16, got {pd_scores.dtype} and "
+                        f"{pd_bboxes.dtype}")
+    if pd_scores.dim() != 3 or pd_scores.shape[2] < 1:
+        raise ValueError("pd_scores must be [B, A, nc] with nc >= 1")
+    b, a, nc = pd_scores.shape
+    if gt_bboxes.dim() != 3 or gt_bboxes.shape[0] != b or gt_bboxes.shape[2] != 4:
+        raise ValueError(f"gt_bboxes must be [{b}, G, 4]")
+    g = gt_bboxes.shape[1]
+    dev = pd_scores.device
+    for t, name, dt, shape in ((pd_bboxes, "pd_bboxes", pd_scores.dtype, (b, a, 4)), (pd_scores, "pd_scores", pd_scores.dtype,
+                                                                                     (b, a, nc)),
+                               (anc_points, "anc_points", torch.float32, (a, 2)), (gt_labels, "gt_labels", torch.float32, (b, g)),
+                               (gt_bboxes, "gt_bboxes", torch.float32, (b, g, 4)), (mask_gt, "mask_gt", torch.float32, (b, g))):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{name} must be a contiguous {dt} {list(shape)} tensor on {dev}")
+    top_k = int(top_k)
+    if b * a and a < top_k:
+        raise ValueError(f"top_k = {top_k} exceeds the {a} anchors")
+    if out is None:
+        out = (torch.empty((b, a, 4), dtype=torch.float32, device=dev), torch.empty((b, a, nc), dtype=torch.float32, device=dev),
+               torch.empty((b, a), dtype=torch.uint8, device=dev), torch.empty((b, a), dtype=torch.int32, device=dev))
+    tb, ts, fg, gi = out
+    for t, name, dt, shape in ((tb, "target_bboxes", torch.float32, (b, a, 4)), (ts, "target_scores", torch.float32, (b, a, nc)),
+                               (fg, "fg_mask", torch.uint8, (b, a)), (gi, "target_gt_idx", torch.int32, (b, a))):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"out's {name} must be a contiguous {dt} {list(shape)} tensor on {dev}")
+    words = torch.empty(2, dtype=torch.int32, device=dev)            # scores_sum (fp32 bits), flags
+    ssum, flags = words[:1].view(torch.float32), words[1:]
+    L = _lib.lib()
+    nb = L.mhaq_fq_od_assign_workspace_bytes(b, g, a, top_k)
+    ws = _workspace(max(nb, 8), dev)
+    ptr = lambda t: t.data_ptr() if t.numel() else None
+    rc = L.mhaq_fq_od_assign(ptr(pd_scores), ptr(pd_bboxes), _SR_DT[pd_scores.dtype], ptr(anc_points), ptr(gt_labels),
+                             ptr(gt_bboxes), ptr(mask_gt), b, a, nc, g, top_k, float(alpha), float(beta), float(eps), ptr(tb),
+                             ptr(ts), ptr(fg), ptr(gi), ssum.data_ptr(), flags.data_ptr(), ws.data_ptr(), nb, _stream())
+    if rc == -4:                                                     # MHAQ_FQ_EUNSUPPORTED
+        raise ValueError(f"mhaq_fq_od_assign does not serve B = {b}, A = {a}, nc = {nc}, G = {g}, top_k = {top_k} "
+                         "(include/mhaq_fq.h has the ranges)")
+    _lib.check(rc, "mhaq_fq_od_assign")
+    return tb, ts, fg.view(torch.bool), gi, ssum, flags
