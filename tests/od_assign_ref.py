@@ -21,6 +21,37 @@ CASES = {
     "a21504-lds-above-64k-b3": (10, 1024, (4, 0, 1), 4, 80, 13, 1.0, 6.0, F32),
     "g300-packed-count-word-b3": (72, 160, (300, 0, 5), 300, 80, 10, 0.5, 6.0, F32),
 }
+# The edges of the exponents, of top_k and of the expand kernel's row length (tests/test_gpu_od_assign_edges.py): the fields of
+# CASES and a tweak that edge_case() applies -- "zero": every third anchor's scores are exactly 0; "tie": no tweak, but the
+# outcome rests on the library's tie rule, so the row has no margin and the reference's Assigner cannot be compared (with
+# alpha == beta == 0 every in-box metric is 1, and torch.topk's choice among equals is unspecified).
+EDGE_CASES = {
+    "exp-powf-0.75-2.5": (21, 160, (7, 3, 0), 7, 80, 10, 0.75, 2.5, F32, None),
+    "exp-odd-3-identity-1": (22, 160, (7, 3, 0), 7, 80, 10, 3.0, 1.0, F32, None),
+    "exp-odd-7-5": (21, 160, (7, 3, 0), 7, 80, 10, 7.0, 5.0, F32, None),
+    "exp-2-last-integer-64": (22, 160, (7, 3, 0), 7, 80, 10, 2.0, 64.0, F32, None),
+    "exp-2-powf-65": (22, 160, (7, 3, 0), 7, 80, 10, 2.0, 65.0, F32, None),
+    "exp-alpha0-zero-scores": (23, 160, (7, 3, 0), 7, 80, 10, 0.0, 6.0, F32, "zero"),
+    "exp-beta0": (163, 160, (7, 3, 0), 7, 80, 10, 0.5, 0.0, F32, None),
+    "exp-6-sqrt-beta": (21, 160, (7, 3, 0), 7, 80, 10, 6.0, 0.5, F32, None),
+    "exp-both-0": (21, 160, (7, 3, 0), 7, 80, 10, 0.0, 0.0, F32, "tie"),
+    "exp-bf16-powf-0.75-2.5": (21, 160, (7, 3, 0), 7, 80, 10, 0.75, 2.5, BF16, None),
+    "k32-full-selection": (21, 160, (7, 3, 0), 7, 80, 32, 0.5, 6.0, F32, None),
+    "nc2-scalar-rows-shorter-than-a-store": (21, 160, (7, 3, 0), 7, 2, 10, 0.5, 6.0, F32, None),
+    "nc4-one-store-per-row": (21, 160, (7, 3, 0), 7, 4, 10, 0.5, 6.0, F32, None),
+    "nc5-scalar-odd-rows": (21, 160, (7, 3, 0), 7, 5, 10, 0.5, 6.0, F32, None),
+    "nc8-two-stores-per-row": (21, 160, (7, 3, 0), 7, 8, 10, 0.5, 6.0, F32, None),
+}
+
+
+def edge_case(name):
+    """-> (case, nc, top_k, alpha, beta, needs a margin) of a row of EDGE_CASES."""
+    seed, size, counts, g, nc, k, alpha, beta, dtype, tweak = EDGE_CASES[name]
+    c = make_case(seed, size, counts, g, nc)
+    if tweak == "zero":
+        c["pd_scores"][:, ::3] = 0.0
+    c["pd_scores"], c["pd_bboxes"] = c["pd_scores"].to(dtype), c["pd_bboxes"].to(dtype)
+    return c, nc, k, alpha, beta, tweak != "tie"
 
 
 def anchors(size):
@@ -107,9 +138,11 @@ def assign_ref(case, nc, top_k, alpha, beta, eps=1e-9, dtype=torch.float64):
     pos = torch.where(multi[:, None], first, pos)
     fg, gi = pos.any(1), pos.int().argmax(1)
     bi = torch.arange(b, device=dev)[:, None]
-    label = lab[bi, gi].clamp(0).long()
-    pam, pov = (m * pos).amax(-1, keepdim=True), (ov * pos).amax(-1, keepdim=True)
-    norm = (m * pos * pov / (pam + eps)).amax(1)
+    # step 6; a NaN label is class 0 and one beyond int32 its largest value (both lie outside [0, nc) or on an invalid row)
+    label = torch.nan_to_num(lab[bi, gi], nan=0.0, posinf=2.0 ** 31, neginf=0.0).clamp(0, 2.0 ** 31).long()
+    mp = m * pos
+    pam, pov = mp.amax(-1, keepdim=True), (ov * pos).amax(-1, keepdim=True)
+    norm = torch.where(mp > 0, mp * pov / (pam + eps), zero).amax(1)          # step 8: 0 where m is 0, also with eps == 0
     hit = fg & (label < nc)
     out["target_scores"][hit.nonzero(as_tuple=True) + (label[hit],)] = norm[hit]
     out.update(target_bboxes=gb32[bi, gi], fg_mask=fg, target_gt_idx=gi, scores_sum=norm.sum(),
@@ -125,3 +158,61 @@ def assign_ref(case, nc, top_k, alpha, beta, eps=1e-9, dtype=torch.float64):
         if bool(sel.any()):
             out["margin"] = min(out["margin"], float(((top2[:, 0] - top2[:, 1]) / top2[:, 0])[sel].min()))
     return out
+
+
+def predictions(anc, b, nc, seed, extent):
+    """pd_scores [b, A, nc] and pd_bboxes [b, A, 4] jittered around the anchors `anc`, as make_case draws them."""
+    gen = torch.Generator().manual_seed(seed)
+    a = anc.shape[0]
+    half = extent * (0.08 + 0.25 * torch.rand(b, a, 4, generator=gen))
+    pd_bboxes = torch.cat((anc - half[..., :2], anc + half[..., 2:]), -1) + extent * 0.03 * (torch.rand(b, a, 4, generator=gen) - 0.5)
+    return torch.sigmoid(2.0 * torch.randn(b, a, nc, generator=gen)), pd_bboxes
+
+
+def hand_case(anc, nc, rows, g, seed=0, extent=160.0, far=False):
+    """One image on the anchors `anc` with the ground truth `rows` = {row index: (box, label, mask)} among `g` rows, every
+    other row zeros with mask 0.  `far`: every prediction lies far from every box (all overlaps are 0)."""
+    sc, pb = predictions(anc, 1, nc, seed, extent)
+    if far:
+        pb = torch.tensor([9000.0, 9000.0, 9010.0, 9010.0]).expand(1, anc.shape[0], 4).clone()
+    gt_bboxes, gt_labels, mask = torch.zeros(1, g, 4), torch.zeros(1, g, 1), torch.zeros(1, g, 1)
+    for j, (box, label, m) in rows.items():
+        gt_bboxes[0, j], gt_labels[0, j], mask[0, j] = torch.tensor(box, dtype=torch.float32), label, m
+    return {"pd_scores": sc, "pd_bboxes": pb, "anc_points": anc.clone(), "gt_labels": gt_labels, "gt_bboxes": gt_bboxes,
+            "mask_gt": mask}
+
+
+def grid(nx, ny, stride=8.0):
+    """A hand-made anchor grid: nx * ny cell centres at one stride, row by row."""
+    yy, xx = torch.meshgrid((torch.arange(ny, dtype=torch.float32) + 0.5) * stride,
+                            (torch.arange(nx, dtype=torch.float32) + 0.5) * stride, indexing="ij")
+    return torch.stack((xx, yy), -1).view(-1, 2)
+
+
+def run(case, nc, k, alpha, beta, eps=1e-9):
+    """The kernels on `case`: -> (the case on the device, the record of mhaq_amd.od_assign)."""
+    from mhaq_amd import od_assign as OA
+    dev = {n: t.cuda() for n, t in case.items()}
+    return dev, OA.od_assign(dev["pd_scores"], dev["pd_bboxes"], dev["anc_points"], dev["gt_labels"], dev["gt_bboxes"],
+                             dev["mask_gt"], nc, k, alpha, beta, eps)
+
+
+def check(rec, dev, nc, k, alpha, beta, need_margin, eps=1e-9, label=""):
+    """Discrete outputs equal the fp64 restatement; continuous ones lie within twice the error of the framework's own fp32
+    chain (the restatement in fp32 on the same device) against fp64."""
+    from tests.sr_metrics_ref import within_bar
+    r64 = assign_ref(dev, nc, k, alpha, beta, eps)
+    r32 = assign_ref(dev, nc, k, alpha, beta, eps, dtype=torch.float32)
+    if need_margin:
+        assert r64["margin"] >= 1e-3                     # a condition on the inputs, not a tolerance on the kernel
+    for name in ("fg_mask", "target_gt_idx", "target_bboxes"):
+        assert torch.equal(rec[name].to(r64[name].dtype), r64[name]), name
+    assert torch.equal(rec["target_scores"] != 0, r64["target_scores"] != 0)
+    assert int(rec["flags"].item()) == r64["flags"]
+    ts, ts32, ts64 = (r["target_scores"].double() for r in (rec, r32, r64))
+    err, bar = float((ts - ts64).abs().max()) if ts.numel() else 0.0, float((ts32 - ts64).abs().max()) if ts.numel() else 0.0
+    ok, frac = within_bar(rec["scores_sum"], r32["scores_sum"], r64["scores_sum"], 1.0)  # its own bar + 8 ulp32, as for
+    print(f"bars {label}: target_scores kernel {err:.3e} fp32 chain {bar:.3e} fraction of 2x {err / (2 * bar) if bar else 0.0:.3f}; "
+          f"scores_sum fraction {frac:.3f}")                                             # every scalar of this suite
+    assert err <= 2 * bar and ok
+    return r64

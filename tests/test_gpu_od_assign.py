@@ -8,37 +8,12 @@ import torch
 from mhaq_amd import od_assign as OA
 from mhaq_amd import ops
 from tests import od_assign_ref as R
-from tests.sr_metrics_ref import within_bar
 
 pytestmark = pytest.mark.gpu
 CASES, F32 = R.CASES, torch.float32
-DISCRETE = ("fg_mask", "target_gt_idx", "target_bboxes")
 
 
-def run(case, nc, k, alpha, beta):
-    dev = {n: t.cuda() for n, t in case.items()}
-    return dev, OA.od_assign(dev["pd_scores"], dev["pd_bboxes"], dev["anc_points"], dev["gt_labels"], dev["gt_bboxes"],
-                             dev["mask_gt"], nc, k, alpha, beta)
-
-
-def check(rec, dev, nc, k, alpha, beta, need_margin):
-    """Discrete outputs equal the fp64 restatement; continuous ones lie within twice the error of the framework's own fp32
-    chain (the restatement in fp32 on the same device) against fp64."""
-    r64 = R.assign_ref(dev, nc, k, alpha, beta)
-    r32 = R.assign_ref(dev, nc, k, alpha, beta, dtype=torch.float32)
-    if need_margin:
-        assert r64["margin"] >= 1e-3                     # a condition on the inputs, not a tolerance on the kernel
-    for name in DISCRETE:
-        assert torch.equal(rec[name].to(r64[name].dtype), r64[name]), name
-    assert torch.equal(rec["target_scores"] != 0, r64["target_scores"] != 0)
-    assert int(rec["flags"].item()) == r64["flags"]
-    ts, ts32, ts64 = (r["target_scores"].double() for r in (rec, r32, r64))
-    err, bar = float((ts - ts64).abs().max()) if ts.numel() else 0.0, float((ts32 - ts64).abs().max()) if ts.numel() else 0.0
-    print(f"target_scores: kernel {err:.3e} fp32 chain {bar:.3e}")
-    ok, frac = within_bar(rec["scores_sum"], r32["scores_sum"], r64["scores_sum"], 1.0)  # its own bar + 8 ulp32, as for
-    print(f"scores_sum: fraction of its bar {frac:.3f}")                             # every scalar of this suite
-    assert err <= 2 * bar and ok
-    return r64
+run, check = R.run, R.check                  # shared with tests/test_gpu_od_assign_edges.py
 
 
 @pytest.mark.parametrize("name", CASES)
