@@ -859,6 +859,82 @@ int mhaq_fq_od_assign(const void* pd_scores, const void* pd_bboxes, int pd_dtype
                       uint32_t* flags /* [1] */, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Object-detection training: the YOLO criterion around the assignment above (the reference's ComputeYoloLoss.__call__,
+ * src/models/od/loss/yolo_loss.py:271-344, with box_decode :261-269, BoxLoss :108-138 and compute_iou :20-46) on the head's raw
+ * outputs where they are.  Additive to ABI v4 -- MHAQ_FQ_ABI_VERSION stays 4; a caller discovers these entry points by symbol.
+ *   level_ptr     HOST array [levels] of device pointers: level l is a dense [b][no][H_l][W_l] tensor, no = 4 * reg_max + nc,
+ *                 the 4 * reg_max box-distribution channels first (side l, t, r, b; reg_max bins each), then the nc class
+ *                 logits (Head.forward's cat, :272-273).  Elements of the type named by dtype (MHAQ_FQ_DT_F32, MHAQ_FQ_DT_BF16
+ *                 or MHAQ_FQ_DT_F16), aligned to its size, converted up exactly.  Never copied, concatenated or permuted.
+ *   level_h, level_w, level_stride   HOST arrays [levels]: H_l, W_l (>= 0) and the level's stride in pixels (> 0, finite).
+ *                 The arrays are read during the call and travel by value in the kernel arguments (capture-safe).
+ *                 a = sum of H_l * W_l; anchor index = the level's first index + y * W_l + x (make_anchors, :7-18).
+ *   reg_max       16 is the only compiled bin count.
+ * All element arithmetic is fp32 with no contraction, IEEE division and square root and no approximate transcendentals; sums
+ * are accumulated in fp64 in a fixed order.  The contract restates the reference; it is not a recording.
+ * mhaq_fq_od_decode (one launch), per image and anchor at cell (x, y) of a level with stride s:
+ *  1. Per side, p = softmax of its reg_max logits, E = sum_j p_j * j (:263-265).
+ *  2. pd_bboxes[b][a] = ((x + .5 - E_l) * s, (y + .5 - E_t) * s, (x + .5 + E_r) * s, (y + .5 + E_b) * s) (:266-269, :318), fp32.
+ *  3. pd_scores[b][a][c] = 1 / (1 + exp(-logit)) (:317), fp32.
+ *  4. anc_points[a] = ((x + .5) * s, (y + .5) * s) (:319).
+ *  These are mhaq_fq_od_assign's inputs (pd_dtype = MHAQ_FQ_DT_F32).  pd_bboxes 16-byte, the others 4-byte aligned.
+ * mhaq_fq_od_loss_fwd (two launches) takes the assignment's public record -- fg_mask, target_gt_idx, target_scores,
+ * scores_sum -- and the ground truth gt_labels [b][g], gt_bboxes [b][g][4] (pixels).  Per image and anchor:
+ *  5. fg = fg_mask != 0 and 0 <= target_gt_idx < g;  label = gt_labels[target_gt_idx] where fg and it lies in [0, nc), else
+ *     none;  w = target_scores[b][a][label] (0 without a label): a row of target_scores has at most one non-zero, so this is
+ *     the reference's target_scores.sum(-1) (:115).  No address is formed from an unchecked label or index.
+ *  6. cls (:324): sum over all anchors and classes of max(x, 0) - x * t + log1p(exp(-|x|)), t = w at (a, label) where fg, else
+ *     0; target_scores is not read otherwise.
+ *  7. Where fg (:332-338): target box tb = gt_bboxes[target_gt_idx] / s;  predicted box in cells pb = (x + .5 - E_l, ...);
+ *     box term = (1 - CIoU(pb, tb)) * w by compute_iou's formula in its order of operations, box1 = the prediction (:116-117).
+ *  8. Where fg (:120-138): per side the target d = clamp(x + .5 - tb.x1 | y + .5 - tb.y1 | tb.x2 - x - .5 | tb.y2 - y - .5, 0,
+ *     reg_max - 1 - 0.01) (a NaN counts as 0), tl = floor(d), wl = tl + 1 - d, wr = 1 - wl;  dfl term = mean over the four
+ *     sides of -(wl * logp[tl] + wr * logp[tl + 1]), times w, logp = log-softmax of the side's logits.
+ *  9. denom = max(scores_sum, 1) (:322; a NaN stays);  loss = (box, cls, dfl) sums / denom * (gain_box, gain_cls, gain_dfl)
+ *     (:340-342), each rounded once to fp32.
+ * mhaq_fq_od_loss_bwd (one launch) recomputes from the same inputs and writes d(sum_k grad_out[k] * loss[k]) / d(level l) into
+ * grad_level_ptr[l], in the level's layout and dtype (one rounding); EVERY element is written exactly once, so no fill precedes
+ * the call.  grad_out [3] and denom [1] are DEVICE pointers.  With g_k = grad_out[k] * gain_k / denom:
+ * 10. class channels: g_cls * (sigmoid(x) - t).
+ * 11. distribution channels of a side, where fg: g_dfl * w / 4 * (p_j - wl[j == tl] - wr[j == tl + 1])
+ *     + g_box * dL/dE * p_j * (j - E), dL/dE the analytic gradient of the box term through pb; elsewhere 0.  alpha of CIoU is a
+ *     constant (:44-45).  At non-smooth points torch's conventions: equal operands of minimum / maximum share the gradient in
+ *     halves, clamp(0) passes it at the bound.  Nothing flows through the assignment or scores_sum.
+ * Deviations from the reference: no host read -- `if fg_mask.sum()` (:331) is gone, the sums are zero without a foreground
+ * anchor; pd_scores and pd_bboxes are fp32 for 16-bit heads too (the reference rounds them to the head's dtype); the three
+ * losses are fp32 whatever the head's dtype; the BCE target comes from the record's one non-zero element per row; a label
+ * outside [0, nc) counts as no target.  There is no flag word: a non-finite logit gives a non-finite loss.
+ *   loss [3] fp32 (box, cls, dfl);  denom [1] fp32;  scores_sum [1] fp32 as mhaq_fq_od_assign writes it
+ *   workspace     mhaq_fq_od_loss_workspace_bytes(b, a, levels) bytes, 8-byte aligned: three fp64 partial sums per (image,
+ *                 tile of 64 anchors of one level).  0 for arguments the call would refuse and for b * a == 0.
+ * g == 0: gt_labels / gt_bboxes may be NULL, every anchor is background, cls is still computed.  b * a == 0: decode and bwd
+ * launch nothing, fwd writes three zeros and denom, and every array pointer but scores_sum, loss and denom may be NULL.
+ * Errors, before any launch: a NULL host array, levels < 1, an unknown dtype, b < 0, nc or reg_max < 1, H_l or W_l < 0, a stride
+ * not > 0 or not finite, g < 0, NULL loss / denom / scores_sum / grad_out; with b * a > 0 a NULL level, output, record (gt_*
+ * only if g > 0) or workspace (MHAQ_FQ_EINVAL); levels > 4, reg_max != 16, b or nc > 65535, a > 24576 (MHAQ_FQ_EUNSUPPORTED); a
+ * short workspace (MHAQ_FQ_EWORKSPACE); a level not aligned to its element size, pd_bboxes not 16-byte, workspace not 8-byte or
+ * another pointer not 4-byte aligned (MHAQ_FQ_EALIGN).
+ * Stream-ordered, capture-safe, stateless, no host synchronisation, no global atomics, no workgroup waits for another; the
+ * same inputs give the same bits at every call.
+ * ---------------------------------------------------------------------- */
+int mhaq_fq_od_decode(const void* const* level_ptr, const int32_t* level_h, const int32_t* level_w, const float* level_stride,
+                      int levels, int dtype, int64_t b, int64_t nc, int reg_max, float* pd_bboxes /* [b][a][4] */,
+                      float* pd_scores /* [b][a][nc] */, float* anc_points /* [a][2] */, void* stream);
+size_t mhaq_fq_od_loss_workspace_bytes(int64_t b, int64_t a, int levels);
+int mhaq_fq_od_loss_fwd(const void* const* level_ptr, const int32_t* level_h, const int32_t* level_w, const float* level_stride,
+                        int levels, int dtype, int64_t b, int64_t nc, int reg_max, const uint8_t* fg_mask /* [b][a] */,
+                        const int32_t* target_gt_idx /* [b][a] */, const float* target_scores /* [b][a][nc] */,
+                        const float* scores_sum /* [1] */, const float* gt_labels /* [b][g] */,
+                        const float* gt_bboxes /* [b][g][4] */, int64_t g, float gain_box, float gain_cls, float gain_dfl,
+                        float* loss /* [3] */, float* denom /* [1] */, void* workspace, size_t workspace_bytes, void* stream);
+int mhaq_fq_od_loss_bwd(const void* const* level_ptr, const int32_t* level_h, const int32_t* level_w, const float* level_stride,
+                        int levels, int dtype, int64_t b, int64_t nc, int reg_max, const uint8_t* fg_mask,
+                        const int32_t* target_gt_idx, const float* target_scores, const float* gt_labels, const float* gt_bboxes,
+                        int64_t g, const float* grad_out /* [3], device */, const float* denom /* [1], device */,
+                        float gain_box, float gain_cls, float gain_dfl, void* const* grad_level_ptr /* host [levels] */,
+                        void* stream);
+
+/* ------------------------------------------------------------------------
  * Super-resolution validation metrics: per-image PSNR and SSIM of the clamped prediction against the target and the L1
  * criterion on the unclamped one, in three launches.  Additive to ABI v4 -- MHAQ_FQ_ABI_VERSION stays 4; a caller discovers
  * these entry points by symbol.

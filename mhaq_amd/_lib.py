@@ -117,6 +117,16 @@ SIGNATURES = {
     "mhaq_fq_od_assign_workspace_bytes": (_sz, [_i64, _i64, _i64, _int]),
     "mhaq_fq_od_assign": (_int, [_p, _p, _int, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _int, C.c_float, C.c_float, C.c_float,
                                  _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    # ... and the criterion around it (additive, ABI v4 kept).  All three start with the level table -- host arrays level_ptr,
+    # level_h, level_w, level_stride, then levels, dtype, b, nc, reg_max.  decode: pd_bboxes, pd_scores, anc_points.  fwd:
+    # fg_mask, target_gt_idx, target_scores, scores_sum, gt_labels, gt_bboxes, g, three gains, loss, denom, workspace.  bwd:
+    # the record without scores_sum, g, grad_out, denom, three gains, grad_level_ptr
+    "mhaq_fq_od_decode": (_int, [_p, _p, _p, _p, _int, _int, _i64, _i64, _int, _p, _p, _p, _p]),
+    "mhaq_fq_od_loss_workspace_bytes": (_sz, [_i64, _i64, _int]),
+    "mhaq_fq_od_loss_fwd": (_int, [_p, _p, _p, _p, _int, _int, _i64, _i64, _int, _p, _p, _p, _p, _p, _p, _i64, C.c_float,
+                                   C.c_float, C.c_float, _p, _p, _p, _sz, _p]),
+    "mhaq_fq_od_loss_bwd": (_int, [_p, _p, _p, _p, _int, _int, _i64, _i64, _int, _p, _p, _p, _p, _p, _i64, _p, _p, C.c_float,
+                                   C.c_float, C.c_float, _p, _p]),
     # super-resolution validation metrics: sr, sr_dtype, hr, hr_dtype, n, c, h, w, sr_div, to_luminance, pool, psnr, ssim,
     # l1, mean, flags, workspace (additive, ABI v4 kept)
     "mhaq_fq_sr_metrics_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _int, _int]),

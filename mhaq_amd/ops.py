@@ -1187,3 +1187,111 @@ def od_assign(pd_scores, pd_bboxes, anc_points, gt_labels, gt_bboxes, mask_gt, t
                          "(include/mhaq_fq.h has the ranges)")
     _lib.check(rc, "mhaq_fq_od_assign")
     return tb, ts, fg.view(torch.bool), gi, ssum, flags
+
+
+# the criterion around the assignment: decode, loss forward, loss backward on the head's outputs where they are
+def _od_levels(outputs, strides, nc, reg_max, what):
+    """The level table of a head's outputs -- a list of dense [B, 4 * reg_max + nc, H, W] tensors of one dtype on one device --
+    as the C ABI takes it: -> (host arrays ptr, h, w, stride; levels, dtype code, B, A)."""
+    outputs = list(outputs)
+    if not outputs or not all(isinstance(t, torch.Tensor) for t in outputs) or len(outputs) != len(strides):
+        raise ValueError("outputs must be a non-empty list of tensors with one stride each")
+    x0, nc, reg_max = outputs[0], int(nc), int(reg_max)
+    if not x0.is_cuda:
+        raise _lib.MhaqFqError(f"the head's outputs are on {x0.device}: {what} runs only as HIP kernels on an MI355X (no CPU "
+                               "fallback by design)")
+    if x0.dtype not in _SR_DT:
+        raise TypeError(f"the head's outputs must be float32, bfloat16 or float16, got {x0.dtype}")
+    if reg_max != 16 or len(outputs) > 4 or nc < 1:
+        raise ValueError(f"{what} serves reg_max = 16, up to 4 levels and nc >= 1, got reg_max = {reg_max}, {len(outputs)} "
+                         f"levels, nc = {nc} (include/mhaq_fq.h has the ranges)")
+    b = x0.shape[0] if x0.dim() == 4 else -1
+    for t in outputs:
+        if t.dim() != 4 or t.shape[0] != b or t.shape[1] != 4 * reg_max + nc or t.dtype != x0.dtype or t.device != x0.device \
+                or not t.is_contiguous():
+            raise ValueError(f"every level must be a contiguous {x0.dtype} [{b}, {4 * reg_max + nc}, H, W] tensor on {x0.device}")
+    n = len(outputs)
+    ptr = (ctypes.c_void_p * n)(*[t.data_ptr() if t.numel() else None for t in outputs])
+    h = (ctypes.c_int32 * n)(*[t.shape[2] for t in outputs])
+    w = (ctypes.c_int32 * n)(*[t.shape[3] for t in outputs])
+    s = (ctypes.c_float * n)(*[float(v) for v in strides])
+    return (ptr, h, w, s, n, _SR_DT[x0.dtype], b, nc, reg_max), sum(t.shape[2] * t.shape[3] for t in outputs)
+
+
+def _od_rc(rc, what):
+    if rc == -4:                                                     # MHAQ_FQ_EUNSUPPORTED
+        raise ValueError(f"{what} does not serve these shapes (include/mhaq_fq.h has the ranges)")
+    _lib.check(rc, what)
+
+
+def _od_record(rec, b, a, nc, dev):
+    """(fg_mask, target_gt_idx, target_scores, gt_labels, gt_bboxes) checked -> their pointers and G."""
+    fg, gi, ts, gl, gb = rec
+    if gb.dim() != 3 or gb.shape[0] != b or gb.shape[2] != 4:
+        raise ValueError(f"gt_bboxes must be [{b}, G, 4]")
+    g = gb.shape[1]
+    if fg.dtype == torch.bool:
+        fg = fg.view(torch.uint8)
+    for t, name, dt, shape in ((fg, "fg_mask", torch.uint8, (b, a)), (gi, "target_gt_idx", torch.int32, (b, a)),
+                               (ts, "target_scores", torch.float32, (b, a, nc)), (gl, "gt_labels", torch.float32, (b, g)),
+                               (gb, "gt_bboxes", torch.float32, (b, g, 4))):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{name} must be a contiguous {dt} {list(shape)} tensor on {dev}")
+    return [t.data_ptr() if t.numel() else None for t in (fg, gi, ts, gl, gb)], g
+
+
+def od_decode(outputs, strides, nc, reg_max=16):
+    """mhaq_fq_od_decode: one launch, no host synchronisation.  `outputs`: the head's levels, dense [B, 4 * reg_max + nc, H, W]
+    tensors of one dtype (float32 / bfloat16 / float16).  Returns float32 (pd_bboxes [B, A, 4] xyxy in pixels, pd_scores
+    [B, A, nc] sigmoided, anc_points [A, 2] in pixels): the inputs of od_assign."""
+    lv, a = _od_levels(outputs, strides, nc, reg_max, "the box decode")
+    b, nc, dev = lv[6], lv[7], outputs[0].device
+    pb = torch.empty((b, a, 4), dtype=torch.float32, device=dev)
+    sc = torch.empty((b, a, nc), dtype=torch.float32, device=dev)
+    anc = torch.empty((a, 2), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):                                     # no tensor among the arguments for _on_device to find
+        _od_rc(_lib.lib().mhaq_fq_od_decode(*lv, pb.data_ptr(), sc.data_ptr(), anc.data_ptr(), _stream()), "mhaq_fq_od_decode")
+    return pb, sc, anc
+
+
+@_on_device
+def od_loss_fwd(outputs, strides, nc, reg_max, fg_mask, target_gt_idx, target_scores, scores_sum, gt_labels, gt_bboxes, gains):
+    """mhaq_fq_od_loss_fwd: two launches, no host synchronisation.  The record is od_assign's (fg_mask bool or uint8 [B, A],
+    target_gt_idx int32 [B, A], target_scores float32 [B, A, nc], scores_sum float32 [1]); gt_labels [B, G] and gt_bboxes
+    [B, G, 4] float32.  Returns (loss [3] float32 = box, cls, dfl times `gains`; denom [1] float32 for od_loss_bwd)."""
+    lv, a = _od_levels(outputs, strides, nc, reg_max, "the detection loss")
+    b, nc, dev = lv[6], lv[7], outputs[0].device
+    rec, g = _od_record((fg_mask, target_gt_idx, target_scores, gt_labels, gt_bboxes), b, a, nc, dev)
+    if scores_sum.dtype != torch.float32 or scores_sum.numel() != 1 or scores_sum.device != dev:
+        raise ValueError(f"scores_sum must be one float32 element on {dev}")
+    loss = torch.empty(3, dtype=torch.float32, device=dev)
+    denom = torch.empty(1, dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    nb = L.mhaq_fq_od_loss_workspace_bytes(b, a, lv[4])
+    ws = _workspace(max(nb, 8), dev)
+    _od_rc(L.mhaq_fq_od_loss_fwd(*lv, *rec[:3], scores_sum.data_ptr(), *rec[3:], g, *(float(v) for v in gains), loss.data_ptr(),
+                                 denom.data_ptr(), ws.data_ptr(), nb, _stream()), "mhaq_fq_od_loss_fwd")
+    return loss, denom
+
+
+@_on_device
+def od_loss_bwd(outputs, strides, nc, reg_max, fg_mask, target_gt_idx, target_scores, gt_labels, gt_bboxes, grad_out, denom,
+                gains, out=None):
+    """mhaq_fq_od_loss_bwd: one launch, no host synchronisation.  `grad_out` [3] float32 (device) are the upstream gradients
+    of the three losses, `denom` what od_loss_fwd returned.  Returns the gradient of every level in its shape and dtype; every
+    element is written, so `out` (a list of such tensors to write into) needs no fill."""
+    lv, a = _od_levels(outputs, strides, nc, reg_max, "the detection loss")
+    b, nc, dev = lv[6], lv[7], outputs[0].device
+    rec, g = _od_record((fg_mask, target_gt_idx, target_scores, gt_labels, gt_bboxes), b, a, nc, dev)
+    for t, name in ((grad_out, "grad_out"), (denom, "denom")):
+        if t.dtype != torch.float32 or t.numel() != (3 if t is grad_out else 1) or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{name} must be a contiguous float32 tensor of {3 if t is grad_out else 1} element(s) on {dev}")
+    if out is None:
+        out = [torch.empty_like(t) for t in outputs]
+    for t, x in zip(out, outputs):
+        if t.shape != x.shape or t.dtype != x.dtype or t.device != dev or not t.is_contiguous():
+            raise ValueError("every gradient tensor must match its level in shape, dtype and device and be contiguous")
+    gptr = (ctypes.c_void_p * len(out))(*[t.data_ptr() if t.numel() else None for t in out])
+    _od_rc(_lib.lib().mhaq_fq_od_loss_bwd(*lv, *rec, g, grad_out.data_ptr(), denom.data_ptr(), *(float(v) for v in gains), gptr,
+                                          _stream()), "mhaq_fq_od_loss_bwd")
+    return list(out)
