@@ -87,10 +87,9 @@ struct IoF32 {
 };
 template <int DT>
 struct Io16 {
-  typedef uint32_t vu2 __attribute__((ext_vector_type(2)));
   using T = uint16_t;
   using Vec = io16::vu4;
-  using Code = vu2;
+  using Code = io16::vu2;
   static constexpr int kW = 8;
   static constexpr uint32_t kNegInfBits = DT == MHAQ_FQ_DT_BF16 ? 0xFF80u : 0xFC00u;
   template <bool NT>

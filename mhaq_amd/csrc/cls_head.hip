@@ -16,11 +16,9 @@
 // No atomics, no NaN screening: a NaN or infinite logit turns its own row's nll to NaN (or inf) by plain IEEE arithmetic.
 #include <hip/hip_runtime.h>
 
-#include <type_traits>
-
 #include "../../include/mhaq_fq.h"
 #include "fq_common.hpp"
-#include "fq_io16.hpp"
+#include "fq_iox.hpp"
 
 namespace mhaq {
 
@@ -29,26 +27,6 @@ constexpr int kClsRegCols = kBlock * kClsPer;      // 4096
 
 // status word of a row (workspace): what the finalize counts
 enum { kClsValid = 1, kClsNonFinite = 2, kClsBadTarget = 4 };
-
-template <int DT>
-__device__ __forceinline__ float cls_ld1(const void* row, int64_t i) {
-  if constexpr (DT == MHAQ_FQ_DT_F32) return ldg(static_cast<const float*>(row) + i);
-  else return io16::up1<DT>(*gptr(static_cast<const uint16_t*>(row) + i));
-}
-// elements 4 * g .. 4 * g + 3 of a row whose base is aligned to 4 elements
-template <int DT>
-__device__ __forceinline__ void cls_ld4(const void* row, int g, float (&v)[4]) {
-  if constexpr (DT == MHAQ_FQ_DT_F32) {
-    ldvg<4>(static_cast<const float*>(row) + 4 * g, v);
-  } else {
-    typedef uint32_t vu2 __attribute__((ext_vector_type(2)));
-    const vu2 w = *gptr(reinterpret_cast<const vu2*>(static_cast<const uint16_t*>(row) + 4 * g));
-    io16::up2<DT>(w.x, v[0], v[1]);
-    io16::up2<DT>(w.y, v[2], v[3]);
-  }
-}
-template <int DT>
-__host__ __device__ constexpr int cls_esize() { return DT == MHAQ_FQ_DT_F32 ? 4 : 2; }
 
 __device__ __forceinline__ bool cls_target_valid(int64_t y, int64_t cols, int64_t ignore_index) {
   return y != ignore_index && y >= 0 && y < cols;
@@ -113,7 +91,7 @@ __device__ __forceinline__ ClsRowOut cls_row_regs(const void* __restrict__ xr, i
       const int g = tid + u * kBlock;
       if (4 * g < cols) {
         float v[4];
-        cls_ld4<DT>(xr, g, v);
+        iox::ld4<DT>(xr, g, v);
 #pragma unroll
         for (int j = 0; j < 4; ++j) a[4 * u + j] = v[j];
       }
@@ -122,7 +100,7 @@ __device__ __forceinline__ ClsRowOut cls_row_regs(const void* __restrict__ xr, i
 #pragma unroll
     for (int k = 0; k < kClsPer; ++k) {
       const int i = tid + k * kBlock;
-      if (i < cols) a[k] = cls_ld1<DT>(xr, i);
+      if (i < cols) a[k] = iox::ld1<DT>(xr, i);
     }
   }
   const ClsOrder ord(xy);
@@ -178,19 +156,19 @@ __device__ __forceinline__ ClsRowOut cls_row_walk(const void* __restrict__ xr, i
   float m = -INFINITY;
   int above = 0, same = 0;
   for (int64_t i = tid; i < cols; i += kBlock) {
-    const float v = cls_ld1<DT>(xr, i);
+    const float v = iox::ld1<DT>(xr, i);
     m = fmaxf(m, v);
     above += ord.above(v) ? 1 : 0;
     same += (i < y && ord.same(v)) ? 1 : 0;
   }
   block_max_tally3_all(m, above, same, vshare, smf, smi);
   double s[1] = {0.0};
-  for (int64_t i = tid; i < cols; i += kBlock) s[0] += (double)expf(cls_ld1<DT>(xr, i) - m);
+  for (int64_t i = tid; i < cols; i += kBlock) s[0] += (double)expf(iox::ld1<DT>(xr, i) - m);
   block_sum_all<1>(s, smd);
   const float S = (float)s[0];
   if (gr) {
     const double inv_v = 1.0 / (double)vshare;
-    for (int64_t i = tid; i < cols; i += kBlock) stg(gr + i, cls_g(expf(cls_ld1<DT>(xr, i) - m), S, i == y, inv_v));
+    for (int64_t i = tid; i < cols; i += kBlock) stg(gr + i, cls_g(expf(iox::ld1<DT>(xr, i) - m), S, i == y, inv_v));
   }
   return ClsRowOut{cls_nll(xy, m, S), above + same};
 }
@@ -206,7 +184,7 @@ __global__ __launch_bounds__(kBlock) void cls_head_row_kernel(const void* __rest
   __shared__ double smd[kBlock / kWave];
   const int tid = (int)threadIdx.x;
   const int64_t row = blockIdx.x, e0 = row * cols;
-  const void* xr = static_cast<const char*>(x) + e0 * cls_esize<DT>();
+  const void* xr = static_cast<const char*>(x) + e0 * iox::esize<DT>();
   float* gr = gunit ? gunit + e0 : nullptr;
   const int64_t y = *gptr(target + row);
   if (!cls_target_valid(y, cols, ignore_index)) {          // block-uniform: no address is ever formed from this y
@@ -221,13 +199,13 @@ __global__ __launch_bounds__(kBlock) void cls_head_row_kernel(const void* __rest
     }
     return;
   }
-  const float xy = cls_ld1<DT>(xr, y);
+  const float xy = iox::ld1<DT>(xr, y);
   const int vshare = gr ? cls_count_valid(target, rows, cols, ignore_index) : 0;
   ClsRowOut o;
   if (cols > kClsRegCols) {
     o = cls_row_walk<DT>(xr, cols, y, xy, vshare, gr, smf, smi, smd);
   } else {
-    const bool vec = (cols & 3) == 0 && ((uintptr_t)xr & (4 * cls_esize<DT>() - 1)) == 0 && ((uintptr_t)gr & 15) == 0;
+    const bool vec = (cols & 3) == 0 && ((uintptr_t)xr & (4 * iox::esize<DT>() - 1)) == 0 && ((uintptr_t)gr & 15) == 0;
     if (vec) o = cls_row_regs<DT, true>(xr, (int)cols, (int)y, xy, vshare, gr, smf, smi, smd);
     else o = cls_row_regs<DT, false>(xr, (int)cols, (int)y, xy, vshare, gr, smf, smi, smd);
   }
@@ -288,25 +266,21 @@ int mhaq_fq_cls_head_fwd(const void* x, int x_dtype, const int64_t* target, int6
                          uint32_t* flags, void* workspace, size_t workspace_bytes, void* stream) {
   if (!x || !target || !loss || !acc || !counts || !flags || !workspace || rows < 1 || cols < 1 || topk < 1)
     return MHAQ_FQ_EINVAL;
-  if (x_dtype != MHAQ_FQ_DT_F32 && x_dtype != MHAQ_FQ_DT_BF16 && x_dtype != MHAQ_FQ_DT_F16) return MHAQ_FQ_EINVAL;
+  if (!iox::known_dtype(x_dtype)) return MHAQ_FQ_EINVAL;
   if (workspace_bytes < mhaq_fq_cls_head_workspace_bytes(rows)) return MHAQ_FQ_EWORKSPACE;
-  const int esize = x_dtype == MHAQ_FQ_DT_F32 ? 4 : 2;
-  if (((uintptr_t)x & (esize - 1)) || ((uintptr_t)target & 7) || ((uintptr_t)loss & 3) || ((uintptr_t)acc & 3) ||
-      ((uintptr_t)counts & 7) || ((uintptr_t)nll & 3) || ((uintptr_t)rank & 3) || ((uintptr_t)gunit & 3) ||
-      ((uintptr_t)flags & 3) || ((uintptr_t)workspace & 7))
+  if (((uintptr_t)x & (iox::esize(x_dtype) - 1)) || ((uintptr_t)target & 7) || ((uintptr_t)loss & 3) ||
+      ((uintptr_t)acc & 3) || ((uintptr_t)counts & 7) || ((uintptr_t)nll & 3) || ((uintptr_t)rank & 3) ||
+      ((uintptr_t)gunit & 3) || ((uintptr_t)flags & 3) || ((uintptr_t)workspace & 7))
     return MHAQ_FQ_EALIGN;
   if (rows > 0x7fffffff || cols > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
   double* partials = static_cast<double*>(workspace);
   int32_t* ws_rank = reinterpret_cast<int32_t*>(partials + rows);
   int32_t* ws_status = ws_rank + rows;
   const hipStream_t st = (hipStream_t)stream;
-  auto row_launch = [&](auto dt) {
+  iox::with_dtype(x_dtype, [&](auto dt) {
     MHAQ_LAUNCH(cls_head_row_kernel<decltype(dt)::value>, dim3((unsigned)rows), dim3(kBlock), 0, st, x, target, rows, cols,
                 ignore_index, partials, ws_rank, ws_status, nll, rank, gunit);
-  };
-  if (x_dtype == MHAQ_FQ_DT_F32) row_launch(std::integral_constant<int, MHAQ_FQ_DT_F32>{});
-  else if (x_dtype == MHAQ_FQ_DT_BF16) row_launch(std::integral_constant<int, MHAQ_FQ_DT_BF16>{});
-  else row_launch(std::integral_constant<int, MHAQ_FQ_DT_F16>{});
+  });
   if (launch_status() != 0) return launch_status();
   MHAQ_LAUNCH(cls_head_finalize_kernel, dim3(1), dim3(kBlock), 0, st, (const double*)partials, (const int32_t*)ws_rank,
               (const int32_t*)ws_status, rows, topk, loss, acc, counts, flags);

@@ -19,33 +19,12 @@
 
 #include "../../include/mhaq_fq.h"
 #include "fq_common.hpp"
-#include "fq_io16.hpp"
+#include "fq_iox.hpp"
 
 namespace mhaq {
 
 constexpr int kDistillPer = 16;                          // elements of a row per lane and tensor, register path
 constexpr int kDistillRegCols = kBlock * kDistillPer;    // 4096
-
-// ---- element access: DT = MHAQ_FQ_DT_F32 / _BF16 / _F16, converted up exactly
-template <int DT>
-__device__ __forceinline__ float distill_ld1(const void* row, int64_t i) {
-  if constexpr (DT == MHAQ_FQ_DT_F32) return ldg(static_cast<const float*>(row) + i);
-  else return io16::up1<DT>(*gptr(static_cast<const uint16_t*>(row) + i));
-}
-// elements 4 * g .. 4 * g + 3 of a row whose base is aligned to 4 elements
-template <int DT>
-__device__ __forceinline__ void distill_ld4(const void* row, int g, float (&v)[4]) {
-  if constexpr (DT == MHAQ_FQ_DT_F32) {
-    ldvg<4>(static_cast<const float*>(row) + 4 * g, v);
-  } else {
-    typedef uint32_t vu2 __attribute__((ext_vector_type(2)));
-    const vu2 w = *gptr(reinterpret_cast<const vu2*>(static_cast<const uint16_t*>(row) + 4 * g));
-    io16::up2<DT>(w.x, v[0], v[1]);
-    io16::up2<DT>(w.y, v[2], v[3]);
-  }
-}
-template <int DT>
-__host__ __device__ constexpr int distill_esize() { return DT == MHAQ_FQ_DT_F32 ? 4 : 2; }
 
 // ---- the two maxima / K fp64 sums of a block, in every thread after one barrier (own LDS buffer per call site)
 __device__ inline void block_max2_all(float& a, float& b, float* sm) {
@@ -120,8 +99,8 @@ __device__ __forceinline__ void distill_row_regs(const void* __restrict__ xr, co
       const int g = tid + u * kBlock;
       if (4 * g < cols) {
         float v[4], w[4];
-        distill_ld4<XDT>(xr, g, v);
-        distill_ld4<TDT>(tr, g, w);
+        iox::ld4<XDT>(xr, g, v);
+        iox::ld4<TDT>(tr, g, w);
 #pragma unroll
         for (int j = 0; j < 4; ++j) { ax[4 * u + j] = v[j]; at[4 * u + j] = w[j]; }
       }
@@ -130,7 +109,7 @@ __device__ __forceinline__ void distill_row_regs(const void* __restrict__ xr, co
 #pragma unroll
     for (int k = 0; k < kDistillPer; ++k) {
       const int i = tid + k * kBlock;
-      if (i < cols) { ax[k] = distill_ld1<XDT>(xr, i); at[k] = distill_ld1<TDT>(tr, i); }
+      if (i < cols) { ax[k] = iox::ld1<XDT>(xr, i); at[k] = iox::ld1<TDT>(tr, i); }
     }
   }
   float mx = -INFINITY, mt = -INFINITY;
@@ -194,20 +173,20 @@ __device__ __forceinline__ void distill_row_walk(const void* __restrict__ xr, co
   const int tid = (int)threadIdx.x;
   float mx = -INFINITY, mt = -INFINITY;
   for (int64_t i = tid; i < cols; i += kBlock) {
-    mx = fmaxf(mx, distill_ld1<XDT>(xr, i));
-    mt = fmaxf(mt, distill_ld1<TDT>(tr, i));
+    mx = fmaxf(mx, iox::ld1<XDT>(xr, i));
+    mt = fmaxf(mt, iox::ld1<TDT>(tr, i));
   }
   block_max2_all(mx, mt, smf);
   double s[2] = {0.0, 0.0};
   for (int64_t i = tid; i < cols; i += kBlock) {
-    s[0] += (double)expf(distill_ld1<XDT>(xr, i) - mx);
-    s[1] += (double)expf(distill_ld1<TDT>(tr, i) - mt);
+    s[0] += (double)expf(iox::ld1<XDT>(xr, i) - mx);
+    s[1] += (double)expf(iox::ld1<TDT>(tr, i) - mt);
   }
   block_sum_all<2>(s, smd1);
   const float Sx = (float)s[0], St = (float)s[1];
   const float lSx = logf(Sx), lSt = logf(St);
   auto probs = [&](int64_t i) {
-    const float bx = distill_ld1<XDT>(xr, i) - mx, bt = distill_ld1<TDT>(tr, i) - mt;
+    const float bx = iox::ld1<XDT>(xr, i) - mx, bt = iox::ld1<TDT>(tr, i) - mt;
     return distill_probs(bx, expf(bx), bt, expf(bt), Sx, St, lSx, lSt);
   };
   double a[2] = {0.0, 0.0};
@@ -230,16 +209,16 @@ __global__ __launch_bounds__(kBlock) void distill_row_kernel(const void* __restr
   __shared__ float smf[2 * (kBlock / kWave)];
   __shared__ double smd1[2 * (kBlock / kWave)], smd2[2 * (kBlock / kWave)];
   const int64_t row = blockIdx.x, e0 = row * cols;
-  const void* xr = static_cast<const char*>(x) + e0 * distill_esize<XDT>();
-  const void* tr = static_cast<const char*>(t) + e0 * distill_esize<TDT>();
+  const void* xr = static_cast<const char*>(x) + e0 * iox::esize<XDT>();
+  const void* tr = static_cast<const char*>(t) + e0 * iox::esize<TDT>();
   float* gr = gunit ? gunit + e0 : nullptr;
   double* partial = partials + row;
   if (cols > kDistillRegCols) {
     distill_row_walk<XDT, TDT>(xr, tr, cols, kind, inv_denom, partial, gr, smf, smd1, smd2);
     return;
   }
-  const bool vec = (cols & 3) == 0 && ((uintptr_t)xr & (4 * distill_esize<XDT>() - 1)) == 0 &&
-                   ((uintptr_t)tr & (4 * distill_esize<TDT>() - 1)) == 0 && ((uintptr_t)gr & 15) == 0;
+  const bool vec = (cols & 3) == 0 && ((uintptr_t)xr & (4 * iox::esize<XDT>() - 1)) == 0 &&
+                   ((uintptr_t)tr & (4 * iox::esize<TDT>() - 1)) == 0 && ((uintptr_t)gr & 15) == 0;
   if (vec) distill_row_regs<XDT, TDT, true>(xr, tr, (int)cols, kind, inv_denom, partial, gr, smf, smd1, smd2);
   else distill_row_regs<XDT, TDT, false>(xr, tr, (int)cols, kind, inv_denom, partial, gr, smf, smd1, smd2);
 }
@@ -256,11 +235,6 @@ __global__ __launch_bounds__(kBlock) void distill_finalize_kernel(const double* 
 
 // ---- backward: gx = gunit * g[0], rounded once
 template <int DT>
-__device__ __forceinline__ void distill_st1(void* gx, int64_t i, float v) {
-  if constexpr (DT == MHAQ_FQ_DT_F32) stg(static_cast<float*>(gx) + i, v);
-  else *gptr(static_cast<uint16_t*>(gx) + i) = io16::down1<DT>(v);
-}
-template <int DT>
 __global__ __launch_bounds__(kBlock) void distill_bwd_kernel(const float* __restrict__ gunit, const float* __restrict__ g,
                                                              void* __restrict__ gx, int64_t n, int vec) {
   const float gv = *g;
@@ -272,29 +246,13 @@ __global__ __launch_bounds__(kBlock) void distill_bwd_kernel(const float* __rest
       ldvg<4>(gunit + 4 * v, u);
 #pragma unroll
       for (int j = 0; j < 4; ++j) u[j] = u[j] * gv;
-      if constexpr (DT == MHAQ_FQ_DT_F32) {
-        stvg<4>(static_cast<float*>(gx) + 4 * v, u);
-      } else {
-        typedef uint32_t vu2 __attribute__((ext_vector_type(2)));
-        const vu2 w = {io16::down2<DT>(u[0], u[1]), io16::down2<DT>(u[2], u[3])};
-        *gptr(reinterpret_cast<vu2*>(static_cast<uint16_t*>(gx) + 4 * v)) = w;
-      }
+      iox::st4<DT>(gx, v, u);
     }
     const int64_t i = (nv << 2) + tid;             // the n % 4 tail
-    if (i < n) distill_st1<DT>(gx, i, ldg(gunit + i) * gv);
+    if (i < n) iox::st1<DT>(gx, i, ldg(gunit + i) * gv);
   } else {
-    for (int64_t i = tid; i < n; i += nth) distill_st1<DT>(gx, i, ldg(gunit + i) * gv);
+    for (int64_t i = tid; i < n; i += nth) iox::st1<DT>(gx, i, ldg(gunit + i) * gv);
   }
-}
-
-inline bool distill_dtype_ok(int dt) { return dt == MHAQ_FQ_DT_F32 || dt == MHAQ_FQ_DT_BF16 || dt == MHAQ_FQ_DT_F16; }
-inline int distill_esize_of(int dt) { return dt == MHAQ_FQ_DT_F32 ? 4 : 2; }
-// f receives the dtype as a std::integral_constant (the entry points have checked it)
-template <class F>
-auto distill_with_dtype(int dt, F f) {
-  if (dt == MHAQ_FQ_DT_F32) return f(std::integral_constant<int, MHAQ_FQ_DT_F32>{});
-  if (dt == MHAQ_FQ_DT_BF16) return f(std::integral_constant<int, MHAQ_FQ_DT_BF16>{});
-  return f(std::integral_constant<int, MHAQ_FQ_DT_F16>{});
 }
 
 }  // namespace mhaq
@@ -309,9 +267,9 @@ int mhaq_fq_distill_loss_fwd(const void* x, int x_dtype, const void* t, int t_dt
                              float* loss, float* gunit, void* workspace, size_t workspace_bytes, void* stream) {
   if (!x || !t || !loss || !workspace || rows <= 0 || cols <= 0) return MHAQ_FQ_EINVAL;
   if (kind < MHAQ_FQ_DISTILL_CE || kind > MHAQ_FQ_DISTILL_HELLINGER) return MHAQ_FQ_EINVAL;
-  if (!distill_dtype_ok(x_dtype) || !distill_dtype_ok(t_dtype)) return MHAQ_FQ_EINVAL;
+  if (!iox::known_dtype(x_dtype) || !iox::known_dtype(t_dtype)) return MHAQ_FQ_EINVAL;
   if (workspace_bytes < mhaq_fq_distill_loss_workspace_bytes(rows)) return MHAQ_FQ_EWORKSPACE;
-  if (((uintptr_t)x & (distill_esize_of(x_dtype) - 1)) || ((uintptr_t)t & (distill_esize_of(t_dtype) - 1)) ||
+  if (((uintptr_t)x & (iox::esize(x_dtype) - 1)) || ((uintptr_t)t & (iox::esize(t_dtype) - 1)) ||
       ((uintptr_t)loss & 3) || ((uintptr_t)gunit & 3) || ((uintptr_t)workspace & 7))
     return MHAQ_FQ_EALIGN;
   if (rows > 0x7fffffff) return MHAQ_FQ_EUNSUPPORTED;
@@ -321,13 +279,11 @@ int mhaq_fq_distill_loss_fwd(const void* x, int x_dtype, const void* t, int t_dt
                                                                                          : (double)rows;
   double* partials = static_cast<double*>(workspace);
   const hipStream_t st = (hipStream_t)stream;
-  distill_with_dtype(x_dtype, [&](auto xdt) {
-    distill_with_dtype(t_dtype, [&](auto tdt) {
+  iox::with_dtype(x_dtype, [&](auto xdt) {
+    iox::with_dtype(t_dtype, [&](auto tdt) {
       MHAQ_LAUNCH((distill_row_kernel<decltype(xdt)::value, decltype(tdt)::value>), dim3((unsigned)rows), dim3(kBlock), 0,
                   st, x, t, cols, kind, 1.0 / denom, partials, gunit);
-      return 0;
     });
-    return 0;
   });
   if (launch_status() != 0) return launch_status();
   MHAQ_LAUNCH(distill_finalize_kernel, dim3(1), dim3(kBlock), 0, st, partials, rows, denom, loss);
@@ -335,16 +291,15 @@ int mhaq_fq_distill_loss_fwd(const void* x, int x_dtype, const void* t, int t_dt
 }
 
 int mhaq_fq_distill_loss_bwd(const float* gunit, const float* g, void* gx, int gx_dtype, int64_t n, void* stream) {
-  if (!gunit || !g || !gx || n <= 0 || !distill_dtype_ok(gx_dtype)) return MHAQ_FQ_EINVAL;
-  if (((uintptr_t)gunit & 3) || ((uintptr_t)g & 3) || ((uintptr_t)gx & (distill_esize_of(gx_dtype) - 1))) return MHAQ_FQ_EALIGN;
-  const int vec = ((uintptr_t)gunit & 15) == 0 && ((uintptr_t)gx & (4 * distill_esize_of(gx_dtype) - 1)) == 0;
+  if (!gunit || !g || !gx || n <= 0 || !iox::known_dtype(gx_dtype)) return MHAQ_FQ_EINVAL;
+  if (((uintptr_t)gunit & 3) || ((uintptr_t)g & 3) || ((uintptr_t)gx & (iox::esize(gx_dtype) - 1))) return MHAQ_FQ_EALIGN;
+  const int vec = ((uintptr_t)gunit & 15) == 0 && ((uintptr_t)gx & (4 * iox::esize(gx_dtype) - 1)) == 0;
   const int64_t per = (int64_t)kBlock * 4;
   int64_t blocks = (n + per - 1) / per;
   if (blocks > kMaxBlocks) blocks = kMaxBlocks;
-  distill_with_dtype(gx_dtype, [&](auto dt) {
+  iox::with_dtype(gx_dtype, [&](auto dt) {
     MHAQ_LAUNCH(distill_bwd_kernel<decltype(dt)::value>, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, gunit,
                 g, gx, n, vec);
-    return 0;
   });
   return launch_status();
 }

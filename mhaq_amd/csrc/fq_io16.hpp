@@ -10,6 +10,7 @@ namespace mhaq {
 namespace io16 {
 
 typedef uint32_t vu4 __attribute__((ext_vector_type(4)));
+typedef uint32_t vu2 __attribute__((ext_vector_type(2)));      // 4 elements (fq_iox.hpp's ld4 / st4), 8 byte codes (bn_bwd.hip)
 typedef float vf2 __attribute__((ext_vector_type(2)));
 typedef __bf16 vbf2 __attribute__((ext_vector_type(2)));
 typedef _Float16 vh2 __attribute__((ext_vector_type(2)));

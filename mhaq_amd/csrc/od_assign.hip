@@ -30,8 +30,6 @@ constexpr int kOdResolveBlock = 1024;
 constexpr int kOdExpandRows = 64;         // anchors per workgroup of the expand kernel
 constexpr uint32_t kOdTaken = 0xffffffffu;        // in place of a metric's bits (a NaN pattern no metric has)
 
-typedef float od_f4 __attribute__((ext_vector_type(4)));      // x1, y1, x2, y2
-
 // how the two exponents are taken: n >= 1 by multiplications (1 = identity), kOdExpSqrt by sqrtf, kOdExpPow by powf
 constexpr int kOdExpPow = -1, kOdExpSqrt = -2;
 struct OdAssignExp { float alpha, beta; int alpha_mode, beta_mode; };
@@ -57,13 +55,14 @@ __device__ __forceinline__ bool od_assign_in(od_f4 g, float ax, float ay, float 
 
 template <int DT>
 __device__ __forceinline__ od_f4 od_assign_box(const void* __restrict__ p, int64_t row) {
-  return od_f4{od_ld<DT>(p, row * 4), od_ld<DT>(p, row * 4 + 1), od_ld<DT>(p, row * 4 + 2), od_ld<DT>(p, row * 4 + 3)};
+  return od_f4{iox::ld1<DT>(p, row * 4), iox::ld1<DT>(p, row * 4 + 1), iox::ld1<DT>(p, row * 4 + 2),
+               iox::ld1<DT>(p, row * 4 + 3)};
 }
 
 struct OdPair { float ov, m; int bad; };
 
 // The overlap and the metric of one (ground truth, anchor) pair that is in-box and valid: the reference's compute_iou with
-// box1 = ground truth, box2 = prediction, in its order of operations.  Both kernels call this one function.
+// box1 = ground truth, box2 = prediction (od_ciou, od_common.hpp).  Both kernels call this one function.
 __device__ __forceinline__ OdPair od_assign_pair(od_f4 g, od_f4 p, float sc, OdAssignExp e) {
   OdPair r = {0.f, 0.f, 0};
   if (!(od_finite(g.x) && od_finite(g.y) && od_finite(g.z) && od_finite(g.w) && od_finite(p.x) && od_finite(p.y) &&
@@ -71,21 +70,7 @@ __device__ __forceinline__ OdPair od_assign_pair(od_f4 g, od_f4 p, float sc, OdA
     r.bad = 1;
     return r;
   }
-  const float eps = 1e-7f;
-  const float w1 = g.z - g.x, h1 = (g.w - g.y) + eps;
-  const float w2 = p.z - p.x, h2 = (p.w - p.y) + eps;
-  const float iw = fmaxf(fminf(g.z, p.z) - fmaxf(g.x, p.x), 0.f), ih = fmaxf(fminf(g.w, p.w) - fmaxf(g.y, p.y), 0.f);
-  const float inter = iw * ih;
-  const float uni = ((w1 * h1 + w2 * h2) - inter) + eps;
-  const float iou = inter / uni;
-  const float cw = fmaxf(g.z, p.z) - fminf(g.x, p.x), ch = fmaxf(g.w, p.w) - fminf(g.y, p.y);
-  const float c2 = (cw * cw + ch * ch) + eps;
-  const float dx = ((p.x + p.z) - g.x) - g.z, dy = ((p.y + p.w) - g.y) - g.w;
-  const float rho2 = (dx * dx + dy * dy) / 4.f;
-  const float da = atanf(w2 / h2) - atanf(w1 / h1);
-  const float v = 0.40528473456935109f * (da * da);           // 4 / pi^2
-  const float al = v / ((v - iou) + 1.0000001f);
-  const float ciou = iou - (rho2 / c2 + v * al);
+  const float ciou = od_ciou(g, p).ciou;
   r.ov = ciou > 0.f ? ciou : 0.f;                             // clamp_(0); a NaN (an overflow on the way) counts as 0
   const float m = od_assign_pow(sc, e.alpha, e.alpha_mode) * od_assign_pow(r.ov, e.beta, e.beta_mode);
   r.m = m > 0.f ? m : 0.f;                                    // the key needs a non-negative metric: -0 and NaN count as 0
@@ -142,7 +127,7 @@ __global__ __launch_bounds__(kBlock) void od_assign_topk_kernel(
     uint32_t mb = 0;
     if (od_assign_in(gb, ldg(anc + 2 * (int64_t)a), ldg(anc + 2 * (int64_t)a + 1), eps)) {
       const int64_t row = b * A + a;
-      const OdPair r = od_assign_pair(gb, od_assign_box<DT>(pd_bboxes, row), od_ld<DT>(pd_scores, row * nc + label), e);
+      const OdPair r = od_assign_pair(gb, od_assign_box<DT>(pd_bboxes, row), iox::ld1<DT>(pd_scores, row * nc + label), e);
       bad |= r.bad;
       mb = __float_as_uint(r.m);
     }
@@ -229,14 +214,14 @@ __global__ __launch_bounds__(kOdResolveBlock) void od_assign_resolve_kernel(
           const int lab = s_lab[g];
           const od_f4 gb = od_f4{s_box[4 * g], s_box[4 * g + 1], s_box[4 * g + 2], s_box[4 * g + 3]};
           float ov = 0.f;
-          if (lab >= 0 && od_assign_in(gb, ax, ay, eps)) ov = od_assign_pair(gb, p, od_ld<DT>(pd_scores, row * nc + lab), e).ov;
+          if (lab >= 0 && od_assign_in(gb, ax, ay, eps)) ov = od_assign_pair(gb, p, iox::ld1<DT>(pd_scores, row * nc + lab), e).ov;
           if (ov > bo) { bo = ov; gi = g; }
         }
       }
       const int lab = s_lab[gi];
       const od_f4 gb = od_f4{s_box[4 * gi], s_box[4 * gi + 1], s_box[4 * gi + 2], s_box[4 * gi + 3]};
       if (lab >= 0 && od_assign_in(gb, ax, ay, eps)) {        // the winner of an arg-max over zeros need not hold the anchor
-        const OdPair r = od_assign_pair(gb, p, od_ld<DT>(pd_scores, row * nc + lab), e);
+        const OdPair r = od_assign_pair(gb, p, iox::ld1<DT>(pd_scores, row * nc + lab), e);
         mb = __float_as_uint(r.m);
         atomicMax(&s_pam[gi], mb);
         atomicMax(&s_pov[gi], __float_as_uint(r.ov));
@@ -328,8 +313,6 @@ __global__ __launch_bounds__(kBlock) void od_assign_expand_kernel(
   }
 }
 
-inline size_t od_r8(size_t n) { return (n + 7) & ~(size_t)7; }
-
 static int od_exp_mode(float e) {
   if (e == 0.5f) return kOdExpSqrt;
   if (e >= 1.f && e <= 64.f && e == (float)(int)e) return (int)e;
@@ -354,7 +337,7 @@ int mhaq_fq_od_assign(const void* pd_scores, const void* pd_bboxes, int pd_dtype
                       int64_t g, int top_k, float alpha, float beta, float eps, float* target_bboxes, float* target_scores,
                       uint8_t* fg_mask, int32_t* target_gt_idx, float* scores_sum, uint32_t* flags, void* workspace,
                       size_t workspace_bytes, void* stream) {
-  if (!scores_sum || !flags || b < 0 || a < 0 || g < 0 || nc < 1 || top_k < 1 || !od_dtype_known(pd_dtype))
+  if (!scores_sum || !flags || b < 0 || a < 0 || g < 0 || nc < 1 || top_k < 1 || !iox::known_dtype(pd_dtype))
     return MHAQ_FQ_EINVAL;
   if (!(alpha >= 0.f) || !(beta >= 0.f) || !od_finite(alpha) || !od_finite(beta) || !(eps >= 0.f) || !od_finite(eps))
     return MHAQ_FQ_EINVAL;
@@ -391,7 +374,7 @@ int mhaq_fq_od_assign(const void* pd_scores, const void* pd_bboxes, int pd_dtype
     const OdAssignExp e = {alpha, beta, od_exp_mode(alpha), od_exp_mode(beta)};
     const size_t lds_topk = sA * 4, lds_resolve = sA * 4 + sG * 28;
     int rc = 0;
-    od_with_dtype(pd_dtype, [&](auto dt) {
+    iox::with_dtype(pd_dtype, [&](auto dt) {
       constexpr int DT = decltype(dt)::value;
       if (G > 0) {
         MHAQ_LAUNCH(od_assign_topk_kernel<DT>, dim3((unsigned)G, (unsigned)B), dim3(kBlock), lds_topk, st, pd_scores,

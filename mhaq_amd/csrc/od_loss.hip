@@ -25,8 +25,6 @@ constexpr int kOdLossMaxLevels = 4;
 constexpr int kOdLossMaxA = 24576;        // od_assign's range
 constexpr int kOdLossDist = 4 * kOdLossR; // distribution channels, in front of the class channels
 
-typedef float od_v4 __attribute__((ext_vector_type(4)));      // x1, y1, x2, y2
-
 struct OdLevel {
   const void* p;          // [B][no][H * W]
   void* g;                // the gradient in the same layout (backward only)
@@ -44,12 +42,6 @@ __device__ __forceinline__ OdLevel od_level_of(const OdLevels& lv, int tile) {
   return L;
 }
 
-template <int DT>
-__device__ __forceinline__ void od_st(void* p, int64_t i, float v) {
-  if constexpr (DT == MHAQ_FQ_DT_F32) stg(static_cast<float*>(p) + i, v);
-  else *gptr(static_cast<uint16_t*>(p) + i) = io16::down1<DT>(v);
-}
-
 __device__ __forceinline__ float od_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
 // One side's 16 logits of one anchor (element base + j * hw): softmax p[], its expectation sum p_j * j (returned) and, if LOGP,
@@ -59,7 +51,7 @@ __device__ __forceinline__ float od_side_softmax(const void* __restrict__ src, i
                                                  float (&p)[kOdLossR], float (&lp)[kOdLossR]) {
   float x[kOdLossR];
 #pragma unroll
-  for (int j = 0; j < kOdLossR; ++j) x[j] = valid ? od_ld<DT>(src, base + j * hw) : 0.f;
+  for (int j = 0; j < kOdLossR; ++j) x[j] = valid ? iox::ld1<DT>(src, base + j * hw) : 0.f;
   float m = x[0];
 #pragma unroll
   for (int j = 1; j < kOdLossR; ++j) m = fmaxf(m, x[j]);
@@ -84,13 +76,13 @@ __device__ __forceinline__ float od_side_softmax(const void* __restrict__ src, i
 // The per-anchor record of the loss kernels, as every wavefront reads it for its own lane's anchor.  fg: a foreground anchor
 // with a ground-truth index inside [0, G).  label: -1 unless it lies in [0, nc) -- no address is formed from an unchecked one.
 // w: target_scores[b][a][label], the row's one non-zero (0 without a label).  tb: gt_bboxes[gt_idx] / stride.
-struct OdTarget { bool fg; int label; float w; od_v4 tb; };
+struct OdTarget { bool fg; int label; float w; od_f4 tb; };
 
 __device__ __forceinline__ OdTarget od_target(const uint8_t* __restrict__ fg_mask, const int32_t* __restrict__ gt_idx,
                                               const float* __restrict__ ts, const float* __restrict__ gt_labels,
                                               const float* __restrict__ gt_bboxes, int64_t row, int64_t b, int nc, int G,
                                               float stride, bool valid) {
-  OdTarget t = {false, -1, 0.f, od_v4{0.f, 0.f, 0.f, 0.f}};
+  OdTarget t = {false, -1, 0.f, od_f4{0.f, 0.f, 0.f, 0.f}};
   if (!valid || G <= 0 || !*gptr(fg_mask + row)) return t;
   const int gi = *gptr(gt_idx + row);
   if ((uint32_t)gi >= (uint32_t)G) return t;
@@ -101,7 +93,7 @@ __device__ __forceinline__ OdTarget od_target(const uint8_t* __restrict__ fg_mas
     t.label = (int)labf;
     t.w = ldg(ts + row * nc + t.label);
   }
-  t.tb = od_v4{ldg(gt_bboxes + bg * 4) / stride, ldg(gt_bboxes + bg * 4 + 1) / stride, ldg(gt_bboxes + bg * 4 + 2) / stride,
+  t.tb = od_f4{ldg(gt_bboxes + bg * 4) / stride, ldg(gt_bboxes + bg * 4 + 1) / stride, ldg(gt_bboxes + bg * 4 + 2) / stride,
                ldg(gt_bboxes + bg * 4 + 3) / stride};
   return t;
 }
@@ -109,7 +101,7 @@ __device__ __forceinline__ OdTarget od_target(const uint8_t* __restrict__ fg_mas
 // The DFL target of side `side` (0..3 = l, t, r, b) of an anchor at (ax, ay): clamp(distance, 0, R - 1 - 0.01) by fmaxf / fminf,
 // so a NaN becomes 0 and never an index.  -> tl in [0, R - 2], wl = tl + 1 - target, wr = 1 - wl.
 struct OdDfl { int tl; float wl, wr; };
-__device__ __forceinline__ OdDfl od_dfl_target(int side, float ax, float ay, od_v4 tb) {
+__device__ __forceinline__ OdDfl od_dfl_target(int side, float ax, float ay, od_f4 tb) {
   const float d = side == 0 ? ax - tb.x : (side == 1 ? ay - tb.y : (side == 2 ? tb.z - ax : tb.w - ay));
   const float tg = fminf(fmaxf(d, 0.f), (float)(kOdLossR - 1) - 0.01f);
   OdDfl r;
@@ -119,41 +111,12 @@ __device__ __forceinline__ OdDfl od_dfl_target(int side, float ax, float ay, od_
   return r;
 }
 
-// compute_iou of the reference with box1 = the prediction p, box2 = the target g, in its order of operations; the
-// intermediates the analytic gradient needs stay in the struct.
-struct OdCiou { float w1, h1, iw, ih, ix, iy, uni, iou, cw, ch, c2, dx, dy, rho2, da, al, ciou; };
-__device__ __forceinline__ OdCiou od_ciou(od_v4 p, od_v4 g) {
-  OdCiou c;
-  const float eps = 1e-7f;
-  c.w1 = p.z - p.x;
-  c.h1 = (p.w - p.y) + eps;
-  const float w2 = g.z - g.x, h2 = (g.w - g.y) + eps;
-  c.ix = fminf(p.z, g.z) - fmaxf(p.x, g.x);
-  c.iy = fminf(p.w, g.w) - fmaxf(p.y, g.y);
-  c.iw = fmaxf(c.ix, 0.f);
-  c.ih = fmaxf(c.iy, 0.f);
-  const float inter = c.iw * c.ih;
-  c.uni = ((c.w1 * c.h1 + w2 * h2) - inter) + eps;
-  c.iou = inter / c.uni;
-  c.cw = fmaxf(p.z, g.z) - fminf(p.x, g.x);
-  c.ch = fmaxf(p.w, g.w) - fminf(p.y, g.y);
-  c.c2 = (c.cw * c.cw + c.ch * c.ch) + eps;
-  c.dx = ((g.x + g.z) - p.x) - p.z;
-  c.dy = ((g.y + g.w) - p.y) - p.w;
-  c.rho2 = (c.dx * c.dx + c.dy * c.dy) / 4.f;
-  c.da = atanf(w2 / h2) - atanf(c.w1 / c.h1);
-  const float v = 0.40528473456935109f * (c.da * c.da);        // 4 / pi^2
-  c.al = v / ((v - c.iou) + 1.0000001f);
-  c.ciou = c.iou - (c.rho2 / c.c2 + v * c.al);
-  return c;
-}
-
 // torch's gradient share of one operand of minimum / maximum: all of it where it wins, half where the two are equal
 __device__ __forceinline__ float od_share(bool wins, bool equal) { return wins ? 1.f : (equal ? 0.5f : 0.f); }
 
-// d ciou / d p[coord], coord = 0..3 = x1, y1, x2, y2 (wave-uniform in the caller); alpha is a constant, clamp(0) passes the
-// gradient at the bound.
-__device__ __forceinline__ float od_ciou_grad(const OdCiou& c, od_v4 p, od_v4 g, int coord) {
+// d ciou / d p[coord] of c = od_ciou(p, g) (od_common.hpp; box1 = the prediction p, box2 = the target g), coord = 0..3 =
+// x1, y1, x2, y2 (wave-uniform in the caller); alpha is a constant, clamp(0) passes the gradient at the bound.
+__device__ __forceinline__ float od_ciou_grad(const OdCiou& c, od_f4 p, od_f4 g, int coord) {
   const bool isx = (coord & 1) == 0, lo = coord < 2;
   const float pl = isx ? p.x : p.y, ph = isx ? p.z : p.w, gl = isx ? g.x : g.y, gh = isx ? g.z : g.w;
   const float pass = (isx ? c.ix : c.iy) >= 0.f ? 1.f : 0.f;
@@ -215,7 +178,7 @@ __global__ __launch_bounds__(kBlock) void od_decode_kernel(OdLevels lv, int no, 
   for (int c0 = 0; c0 < nc; c0 += kOdLossTile) {
     const int ncl = nc - c0 < kOdLossTile ? nc - c0 : kOdLossTile;
     if (c.valid)
-      for (int cl = c.wave; cl < ncl; cl += kBlock / kWave) s_t[cl][c.lane] = od_sigmoid(od_ld<DT>(c.L.p, cbase + (c0 + cl) * c.hw));
+      for (int cl = c.wave; cl < ncl; cl += kBlock / kWave) s_t[cl][c.lane] = od_sigmoid(iox::ld1<DT>(c.L.p, cbase + (c0 + cl) * c.hw));
     __syncthreads();
     if (c.lane < ncl)
       for (int al = c.wave; al < nvalid; al += kBlock / kWave) stg(dst + (int64_t)al * nc + c0 + c.lane, s_t[c.lane][al]);
@@ -238,7 +201,7 @@ __global__ __launch_bounds__(kBlock) void od_loss_fwd_kernel(
   if (c.valid) {
     const int64_t cbase = (c.b * no + kOdLossDist) * c.hw + c.i;
     for (int k = c.wave; k < nc; k += kBlock / kWave) {
-      const float x = od_ld<DT>(c.L.p, cbase + k * c.hw);
+      const float x = iox::ld1<DT>(c.L.p, cbase + k * c.hw);
       const float tt = k == t.label ? t.w : 0.f;
       acc[1] += (double)((fmaxf(x, 0.f) - x * tt) + log1pf(expf(-fabsf(x))));
     }
@@ -256,7 +219,7 @@ __global__ __launch_bounds__(kBlock) void od_loss_fwd_kernel(
     s_dfl[c.lane][c.wave] = (-ll) * d.wl + (-lr) * d.wr;
     __syncthreads();
     if (c.wave == 0 && t.fg) {
-      const od_v4 pb = od_v4{c.ax - s_side[c.lane][0], c.ay - s_side[c.lane][1], c.ax + s_side[c.lane][2],
+      const od_f4 pb = od_f4{c.ax - s_side[c.lane][0], c.ay - s_side[c.lane][1], c.ax + s_side[c.lane][2],
                              c.ay + s_side[c.lane][3]};
       acc[0] = (double)((1.f - od_ciou(pb, t.tb).ciou) * t.w);
       const float dfl = (((s_dfl[c.lane][0] + s_dfl[c.lane][1]) + s_dfl[c.lane][2]) + s_dfl[c.lane][3]) / 4.f;
@@ -308,8 +271,8 @@ __global__ __launch_bounds__(kBlock) void od_loss_bwd_kernel(
   if (c.valid) {
     const int64_t cbase = (c.b * no + kOdLossDist) * c.hw + c.i;
     for (int k = c.wave; k < nc; k += kBlock / kWave) {
-      const float x = od_ld<DT>(c.L.p, cbase + k * c.hw);
-      od_st<DT>(c.L.g, cbase + k * c.hw, g_cls * (od_sigmoid(x) - (k == t.label ? t.w : 0.f)));
+      const float x = iox::ld1<DT>(c.L.p, cbase + k * c.hw);
+      iox::st1<DT>(c.L.g, cbase + k * c.hw, g_cls * (od_sigmoid(x) - (k == t.label ? t.w : 0.f)));
     }
   }
   const int64_t dbase = (c.b * no + c.wave * kOdLossR) * c.hw + c.i;
@@ -322,7 +285,7 @@ __global__ __launch_bounds__(kBlock) void od_loss_bwd_kernel(
     s_side[c.lane][c.wave] = e;
     __syncthreads();
     if (t.fg) {
-      const od_v4 pb = od_v4{c.ax - s_side[c.lane][0], c.ay - s_side[c.lane][1], c.ax + s_side[c.lane][2],
+      const od_f4 pb = od_f4{c.ax - s_side[c.lane][0], c.ay - s_side[c.lane][1], c.ax + s_side[c.lane][2],
                              c.ay + s_side[c.lane][3]};
       const float dc = od_ciou_grad(od_ciou(pb, t.tb), pb, t.tb, c.wave);
       // box term (1 - ciou) * w;  x1 = ax - l, y1 = ay - t, x2 = ax + r, y2 = ay + b
@@ -338,7 +301,7 @@ __global__ __launch_bounds__(kBlock) void od_loss_bwd_kernel(
   }
   if (c.valid) {
 #pragma unroll
-    for (int j = 0; j < kOdLossR; ++j) od_st<DT>(c.L.g, dbase + j * c.hw, gj[j]);
+    for (int j = 0; j < kOdLossR; ++j) iox::st1<DT>(c.L.g, dbase + j * c.hw, gj[j]);
   }
 }
 
@@ -347,7 +310,7 @@ __global__ __launch_bounds__(kBlock) void od_loss_bwd_kernel(
 static int od_levels_build(const void* const* ptr, void* const* grad, bool want_grad, const int32_t* h, const int32_t* w,
                            const float* stride, int levels, int dtype, int64_t b, int64_t nc, int reg_max, OdLevels* out,
                            int64_t* A, int* tiles) {
-  if (!ptr || !h || !w || !stride || (want_grad && !grad) || levels < 1 || !od_dtype_known(dtype) || b < 0 || nc < 1 ||
+  if (!ptr || !h || !w || !stride || (want_grad && !grad) || levels < 1 || !iox::known_dtype(dtype) || b < 0 || nc < 1 ||
       reg_max < 1)
     return MHAQ_FQ_EINVAL;
   if (levels > kOdLossMaxLevels || reg_max != kOdLossR || b > 65535 || nc > 65535) return MHAQ_FQ_EUNSUPPORTED;
@@ -401,7 +364,7 @@ int mhaq_fq_od_decode(const void* const* level_ptr, const int32_t* level_h, cons
   if (!pd_bboxes || !pd_scores || !anc_points) return MHAQ_FQ_EINVAL;
   if (((uintptr_t)pd_bboxes & 15) || ((uintptr_t)pd_scores & 3) || ((uintptr_t)anc_points & 3)) return MHAQ_FQ_EALIGN;
   const int NO = kOdLossDist + (int)nc;
-  od_with_dtype(dtype, [&](auto dt) {
+  iox::with_dtype(dtype, [&](auto dt) {
     constexpr int DT = decltype(dt)::value;
     MHAQ_LAUNCH(od_decode_kernel<DT>, dim3((unsigned)tiles, (unsigned)b), dim3(kBlock), 0, (hipStream_t)stream, lv, NO, (int)nc,
                 (int)A, pd_bboxes, pd_scores, anc_points);
@@ -436,7 +399,7 @@ int mhaq_fq_od_loss_fwd(const void* const* level_ptr, const int32_t* level_h, co
   double* partial = static_cast<double*>(workspace);
   if (!empty) {
     const int NO = kOdLossDist + (int)nc;
-    od_with_dtype(dtype, [&](auto dt) {
+    iox::with_dtype(dtype, [&](auto dt) {
       constexpr int DT = decltype(dt)::value;
       MHAQ_LAUNCH(od_loss_fwd_kernel<DT>, dim3((unsigned)tiles, (unsigned)b), dim3(kBlock), 0, st, lv, NO, (int)nc, (int)A,
                   (int)g, fg_mask, target_gt_idx, target_scores, gt_labels, gt_bboxes, partial);
@@ -465,7 +428,7 @@ int mhaq_fq_od_loss_bwd(const void* const* level_ptr, const int32_t* level_h, co
   if (((uintptr_t)grad_out & 3) || ((uintptr_t)denom & 3)) return MHAQ_FQ_EALIGN;
   if (empty) return 0;
   const int NO = kOdLossDist + (int)nc;
-  od_with_dtype(dtype, [&](auto dt) {
+  iox::with_dtype(dtype, [&](auto dt) {
     constexpr int DT = decltype(dt)::value;
     MHAQ_LAUNCH(od_loss_bwd_kernel<DT>, dim3((unsigned)tiles, (unsigned)b), dim3(kBlock), 0, (hipStream_t)stream, lv, NO,
                 (int)nc, (int)A, (int)g, fg_mask, target_gt_idx, target_scores, gt_labels, gt_bboxes, grad_out, denom, gain_box,

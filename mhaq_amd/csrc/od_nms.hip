@@ -30,8 +30,6 @@ constexpr int kOdMatchBlock = kOdThr * kWave;
 __device__ __forceinline__ float od_min(float a, float b) { return b < a ? b : a; }
 __device__ __forceinline__ float od_max(float a, float b) { return a < b ? b : a; }
 
-typedef float od_f4 __attribute__((ext_vector_type(4)));      // x1, y1, x2, y2
-
 __device__ __forceinline__ float od_iou(od_f4 a, float area_a, od_f4 b, float area_b) {
   const float iw = od_max(0.f, od_min(a.z, b.z) - od_max(a.x, b.x));
   const float ih = od_max(0.f, od_min(a.w, b.w) - od_max(a.y, b.y));
@@ -46,7 +44,7 @@ __global__ __launch_bounds__(kBlock) void od_keys_kernel(const void* __restrict_
   const int a = (int)(blockIdx.x * kBlock + threadIdx.x), c = (int)blockIdx.y;
   if (a >= A) return;
   const int64_t b = blockIdx.z;
-  const float s = od_ld<DT>(pred, (b * (4 + nc) + 4 + c) * A + a);
+  const float s = iox::ld1<DT>(pred, (b * (4 + nc) + 4 + c) * A + a);
   int64_t key = kOdNoKey;
   if (s > conf_thr)                                           // false for a NaN; conf_thr >= 0, so the bits are a positive int32
     key = od_key(s, a, nc, c);
@@ -72,8 +70,8 @@ __device__ __forceinline__ OdCand od_gather(const void* __restrict__ img, const 
   const uint32_t idx = (uint32_t)key;
   if (idx >= (uint32_t)A * (uint32_t)nc) return k;           // not a key of mhaq_fq_od_keys: skipped, no address is formed
   const int a = (int)(idx / (uint32_t)nc), c = (int)(idx - (uint32_t)a * (uint32_t)nc);
-  const float cx = od_ld<DT>(img, a), cy = od_ld<DT>(img, (int64_t)A + a);
-  const float w = od_ld<DT>(img, 2 * (int64_t)A + a), h = od_ld<DT>(img, 3 * (int64_t)A + a);
+  const float cx = iox::ld1<DT>(img, a), cy = iox::ld1<DT>(img, (int64_t)A + a);
+  const float w = iox::ld1<DT>(img, 2 * (int64_t)A + a), h = iox::ld1<DT>(img, 3 * (int64_t)A + a);
   const float hw = w / 2.f, hh = h / 2.f;
   k.box = od_f4{cx - hw, cy - hh, cx + hw, cy + hh};
   k.cls = (float)c;
@@ -247,12 +245,12 @@ int mhaq_fq_od_nms_chunk(void) { return kOdChunk; }
 
 int mhaq_fq_od_keys(const void* pred, int pred_dtype, int64_t B, int64_t nc, int64_t A, float conf_thr, int64_t* keys,
                     void* stream) {
-  if (!pred || !keys || !od_dtype_known(pred_dtype) || B < 1 || nc < 1 || A < 1) return MHAQ_FQ_EINVAL;
+  if (!pred || !keys || !iox::known_dtype(pred_dtype) || B < 1 || nc < 1 || A < 1) return MHAQ_FQ_EINVAL;
   if (!(conf_thr >= 0.f) || !od_finite(conf_thr)) return MHAQ_FQ_EINVAL;
   if (((uintptr_t)pred & (pred_dtype == MHAQ_FQ_DT_F32 ? 3 : 1)) || ((uintptr_t)keys & 7)) return MHAQ_FQ_EALIGN;
   if (!od_shape_supported(B, nc, A)) return MHAQ_FQ_EUNSUPPORTED;
   const dim3 grid((unsigned)((A + kBlock - 1) / kBlock), (unsigned)nc, (unsigned)B);
-  od_with_dtype(pred_dtype, [&](auto dt) {
+  iox::with_dtype(pred_dtype, [&](auto dt) {
     MHAQ_LAUNCH(od_keys_kernel<decltype(dt)::value>, grid, dim3(kBlock), 0, (hipStream_t)stream, pred, (int)A, (int)nc,
                 conf_thr, keys);
   });
@@ -266,7 +264,7 @@ static int od_nms_launch(const void* pred, int pred_dtype, const int64_t* keys, 
                          bool rows, int64_t B, int64_t nc, int64_t A, float iou_thr, float max_wh, int max_nms, int max_det,
                          float* det, int32_t* count, int32_t* n_cand, uint32_t* flags, void* workspace,
                          size_t workspace_bytes, void* stream) {
-  if (!pred || !keys || !det || !count || !n_cand || !flags || !workspace || !od_dtype_known(pred_dtype) || B < 1 ||
+  if (!pred || !keys || !det || !count || !n_cand || !flags || !workspace || !iox::known_dtype(pred_dtype) || B < 1 ||
       nc < 1 || A < 1 || max_nms < 1 || max_det < 1 || (rows && (!n_cand_in || key_stride < 1)))
     return MHAQ_FQ_EINVAL;
   if (iou_thr != iou_thr || !od_finite(max_wh)) return MHAQ_FQ_EINVAL;
@@ -278,7 +276,7 @@ static int od_nms_launch(const void* pred, int pred_dtype, const int64_t* keys, 
   if (!od_shape_supported(B, nc, A) || max_det > kOdMaxDet) return MHAQ_FQ_EUNSUPPORTED;
   uint32_t* img_flags = static_cast<uint32_t*>(workspace);
   const hipStream_t st = (hipStream_t)stream;
-  od_with_dtype(pred_dtype, [&](auto dt) {
+  iox::with_dtype(pred_dtype, [&](auto dt) {
     constexpr int DT = decltype(dt)::value;
     if (rows)
       MHAQ_LAUNCH((od_nms_kernel<DT, true>), dim3((unsigned)B), dim3(kOdChunk), 0, st, pred, keys, (int)A, (int)nc, iou_thr,

@@ -69,7 +69,7 @@ __global__ __launch_bounds__(kBlock) void od_count_kernel(const void* __restrict
   if (a < A) {
     const int64_t row0 = (b * (4 + nc) + 4) * A + a;
 #pragma unroll 8                                              // eight rows' loads in flight: the walk is latency-bound
-    for (int c = 0; c < nc; ++c) n += od_ld<DT>(pred, row0 + (int64_t)c * A) > conf_thr ? 1 : 0;      // false for a NaN
+    for (int c = 0; c < nc; ++c) n += iox::ld1<DT>(pred, row0 + (int64_t)c * A) > conf_thr ? 1 : 0;      // false for a NaN
     *gptr(thread_cnt + b * A + a) = n;
   }
   int total;
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(kBlock) void od_emit_kernel(const void* __restrict_
   for (int c0 = 0; c0 < nc && out < end; c0 += 4) {           // four rows' loads in flight, then their keys in class order
     float s[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) s[k] = c0 + k < nc ? od_ld<DT>(pred, row0 + (int64_t)(c0 + k) * A) : -1.f;
+    for (int k = 0; k < 4; ++k) s[k] = c0 + k < nc ? iox::ld1<DT>(pred, row0 + (int64_t)(c0 + k) * A) : -1.f;
 #pragma unroll
     for (int k = 0; k < 4; ++k)
       if (s[k] > conf_thr && out < end) *gptr(out++) = od_key(s[k], a, nc, c0 + k);
@@ -236,7 +236,6 @@ __global__ __launch_bounds__(kBlock) void od_sort_scatter_kernel(const int64_t* 
   }
 }
 
-inline size_t od_round8(size_t v) { return (v + 7) & ~(size_t)7; }
 struct OdSortLayout {
   int64_t N, K;
   int nat, nst;                          // anchor tiles and sort tiles per image (worst case)
@@ -249,8 +248,8 @@ inline OdSortLayout od_sort_layout(int64_t B, int64_t nc, int64_t A, int max_nms
   l.nat = (int)((A + kBlock - 1) / kBlock);
   l.nst = (int)((l.N + kSortTile - 1) / kSortTile);
   l.keys = (size_t)B * l.N * 8;
-  l.thread_cnt = od_round8((size_t)B * A * 4);
-  l.tile_cnt = od_round8((size_t)B * l.nat * 4);
+  l.thread_cnt = od_r8((size_t)B * A * 4);
+  l.tile_cnt = od_r8((size_t)B * l.nat * 4);
   l.hist = (size_t)B * l.nst * kRadix * 4;
   l.total = 2 * l.keys + l.thread_cnt + l.tile_cnt + l.hist;
   return l;
@@ -271,7 +270,7 @@ size_t mhaq_fq_od_sorted_keys_workspace_bytes(int64_t B, int64_t nc, int64_t A, 
 
 int mhaq_fq_od_sorted_keys(const void* pred, int pred_dtype, int64_t B, int64_t nc, int64_t A, float conf_thr, int max_nms,
                            int64_t* skeys, int32_t* n_cand, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!pred || !skeys || !n_cand || !workspace || !od_dtype_known(pred_dtype) || B < 1 || nc < 1 || A < 1 || max_nms < 1)
+  if (!pred || !skeys || !n_cand || !workspace || !iox::known_dtype(pred_dtype) || B < 1 || nc < 1 || A < 1 || max_nms < 1)
     return MHAQ_FQ_EINVAL;
   if (!(conf_thr >= 0.f) || !od_finite(conf_thr)) return MHAQ_FQ_EINVAL;
   if (((uintptr_t)pred & (pred_dtype == MHAQ_FQ_DT_F32 ? 3 : 1)) || ((uintptr_t)skeys & 7) || ((uintptr_t)n_cand & 3) ||
@@ -288,7 +287,7 @@ int mhaq_fq_od_sorted_keys(const void* pred, int pred_dtype, int64_t B, int64_t 
   const hipStream_t st = (hipStream_t)stream;
   const dim3 agrid((unsigned)l.nat, (unsigned)B), sgrid((unsigned)l.nst, (unsigned)B);
   int rc = 0;
-  od_with_dtype(pred_dtype, [&](auto dt) {
+  iox::with_dtype(pred_dtype, [&](auto dt) {
     constexpr int DT = decltype(dt)::value;
     MHAQ_LAUNCH(od_count_kernel<DT>, agrid, dim3(kBlock), 0, st, pred, (int)A, (int)nc, conf_thr, thread_cnt, tile_cnt);
     if ((rc = launch_status()) != 0) return;

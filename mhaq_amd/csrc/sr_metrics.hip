@@ -20,7 +20,7 @@
 
 #include "../../include/mhaq_fq.h"
 #include "fq_common.hpp"
-#include "fq_io16.hpp"
+#include "fq_iox.hpp"
 
 namespace mhaq {
 
@@ -40,8 +40,6 @@ constexpr int kSrIn = kSrTile + kSrWin - 1;       // 42 inputs per tile side
 
 // 11-tap Gaussian, sigma 1.5, normalised to sum 1: computed in fp64, rounded to fp32 once; tap k and tap 10 - k share w[k]
 struct SrTaps { float w[6]; };
-
-__host__ __device__ constexpr int sr_esize(int dt) { return dt == MHAQ_FQ_DT_F32 ? 4 : 2; }
 
 struct SrGeom {
   int64_t n, c, h, w;
@@ -101,28 +99,7 @@ inline int sr_geometry(int64_t n, int64_t c, int64_t h, int64_t w, int to_lumina
 }
 
 // ---------------------------------------------------------------- launch 1: prepare
-template <int DT>
-__device__ __forceinline__ float sr_ld1(const void* row, int64_t i) {
-  if constexpr (DT == MHAQ_FQ_DT_F32) return ldg(static_cast<const float*>(row) + i);
-  else return io16::up1<DT>(*gptr(static_cast<const uint16_t*>(row) + i));
-}
-// pixels i .. i + 7 of a row whose address at i is 16-byte aligned
-template <int DT>
-__device__ __forceinline__ void sr_ld8(const void* row, int64_t i, float (&v)[kSrPx]) {
-  if constexpr (DT == MHAQ_FQ_DT_F32) {
-    float a[4], b[4];
-    ldvg<4>(static_cast<const float*>(row) + i, a);
-    ldvg<4>(static_cast<const float*>(row) + i + 4, b);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { v[j] = a[j]; v[4 + j] = b[j]; }
-  } else {
-    const io16::vu4 q = *gptr(reinterpret_cast<const io16::vu4*>(static_cast<const uint16_t*>(row) + i));
-    io16::up2<DT>(q.x, v[0], v[1]);
-    io16::up2<DT>(q.y, v[2], v[3]);
-    io16::up2<DT>(q.z, v[4], v[5]);
-    io16::up2<DT>(q.w, v[6], v[7]);
-  }
-}
+static_assert(kSrPx == 8, "a lane's pixels of a row are one iox::ld8");
 __device__ __forceinline__ bool sr_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
 // torch.clamp(v, 0, 1): a NaN stays
 __device__ __forceinline__ float sr_clamp01(float v) {
@@ -154,8 +131,8 @@ __global__ __launch_bounds__(kBlock) void sr_prepare_kernel(const SrPrepArgs a) 
   const bool lum = (C == 3 && P == 1);
   const int items = (cw + kSrPx - 1) / kSrPx;              // 8-pixel items per row of the chunk
   const int64_t plane_in = a.H * a.W;
-  const char* sb = static_cast<const char*>(a.s) + img * C * plane_in * sr_esize(SDT);
-  const char* hb = static_cast<const char*>(a.h) + img * C * plane_in * sr_esize(HDT);
+  const char* sb = static_cast<const char*>(a.s) + img * C * plane_in * iox::esize(SDT);
+  const char* hb = static_cast<const char*>(a.h) + img * C * plane_in * iox::esize(HDT);
   double acc[2] = {0.0, 0.0};
   uint32_t fl = 0;
   const float k0 = MHAQ_SR_K0, k1 = MHAQ_SR_K1, k2 = MHAQ_SR_K2;
@@ -180,14 +157,15 @@ __global__ __launch_bounds__(kBlock) void sr_prepare_kernel(const SrPrepArgs a) 
 #pragma unroll
       for (int c = 0; c < C; ++c) {
         const int64_t e = (c * a.H + row) * a.W + px;
-        vec = vec && (((uintptr_t)(sb + e * sr_esize(SDT)) & 15) == 0) && (((uintptr_t)(hb + e * sr_esize(HDT)) & 15) == 0);
+        vec = vec && (((uintptr_t)(sb + e * iox::esize(SDT)) & 15) == 0) &&
+              (((uintptr_t)(hb + e * iox::esize(HDT)) & 15) == 0);
       }
       if (vec) {
 #pragma unroll
         for (int c = 0; c < C; ++c) {
           const int64_t e = (c * a.H + row) * a.W + px;
-          sr_ld8<SDT>(sb, e, sv[c]);
-          sr_ld8<HDT>(hb, e, hv[c]);
+          iox::ld8<SDT>(sb, e, sv[c]);
+          iox::ld8<HDT>(hb, e, hv[c]);
         }
       } else {
 #pragma unroll
@@ -195,8 +173,8 @@ __global__ __launch_bounds__(kBlock) void sr_prepare_kernel(const SrPrepArgs a) 
           const int64_t e = (c * a.H + row) * a.W + px;
 #pragma unroll
           for (int j = 0; j < kSrPx; ++j) {
-            sv[c][j] = (j < npx) ? sr_ld1<SDT>(sb, e + j) : 0.f;
-            hv[c][j] = (j < npx) ? sr_ld1<HDT>(hb, e + j) : 0.f;
+            sv[c][j] = (j < npx) ? iox::ld1<SDT>(sb, e + j) : 0.f;
+            hv[c][j] = (j < npx) ? iox::ld1<HDT>(hb, e + j) : 0.f;
           }
         }
       }
@@ -456,14 +434,6 @@ __global__ __launch_bounds__(kBlock) void sr_finalize_kernel(const SrFinArgs a) 
   }
 }
 
-inline bool sr_dtype_ok(int dt) { return dt == MHAQ_FQ_DT_F32 || dt == MHAQ_FQ_DT_BF16 || dt == MHAQ_FQ_DT_F16; }
-template <class F>
-auto sr_with_dtype(int dt, F f) {
-  if (dt == MHAQ_FQ_DT_F32) return f(std::integral_constant<int, MHAQ_FQ_DT_F32>{});
-  if (dt == MHAQ_FQ_DT_BF16) return f(std::integral_constant<int, MHAQ_FQ_DT_BF16>{});
-  return f(std::integral_constant<int, MHAQ_FQ_DT_F16>{});
-}
-
 inline SrTaps sr_make_taps() {
   double g[kSrWin], sum = 0.0;
   for (int k = 0; k < kSrWin; ++k) { const double d = k - 5; g[k] = std::exp(-(d * d) / (2.0 * 1.5 * 1.5)); sum += g[k]; }
@@ -487,14 +457,14 @@ int mhaq_fq_sr_metrics(const void* sr, int sr_dtype, const void* hr, int hr_dtyp
                        int64_t w, float sr_div, int to_luminance, int pool, float* psnr, float* ssim, float* l1,
                        float* mean, uint32_t* flags, void* workspace, size_t workspace_bytes, void* stream) {
   if (!sr || !hr || !psnr || !ssim || !l1 || !mean || !flags || !workspace) return MHAQ_FQ_EINVAL;
-  if (!sr_dtype_ok(sr_dtype) || !sr_dtype_ok(hr_dtype)) return MHAQ_FQ_EINVAL;
+  if (!iox::known_dtype(sr_dtype) || !iox::known_dtype(hr_dtype)) return MHAQ_FQ_EINVAL;
   if (n <= 0 || c <= 0 || h <= 0 || w <= 0 || pool < 1 || !std::isfinite(sr_div) || sr_div == 0.f) return MHAQ_FQ_EINVAL;
   if (to_luminance && c != 3) return MHAQ_FQ_EINVAL;
   SrGeom g;
   const int grc = sr_geometry(n, c, h, w, to_luminance, pool, g);
   if (grc == MHAQ_FQ_EINVAL) return grc;
   if (grc == 0 && workspace_bytes < g.total) return MHAQ_FQ_EWORKSPACE;
-  if (((uintptr_t)sr & (sr_esize(sr_dtype) - 1)) || ((uintptr_t)hr & (sr_esize(hr_dtype) - 1)) || ((uintptr_t)psnr & 7) ||
+  if (((uintptr_t)sr & (iox::esize(sr_dtype) - 1)) || ((uintptr_t)hr & (iox::esize(hr_dtype) - 1)) || ((uintptr_t)psnr & 7) ||
       ((uintptr_t)ssim & 7) || ((uintptr_t)l1 & 7) || ((uintptr_t)mean & 7) || ((uintptr_t)flags & 7) ||
       ((uintptr_t)workspace & 7))
     return MHAQ_FQ_EALIGN;
@@ -513,15 +483,13 @@ int mhaq_fq_sr_metrics(const void* sr, int sr_dtype, const void* hr, int hr_dtyp
   pa.C = (int)c; pa.P = g.p; pa.f = pool; pa.chunk = g.chunk; pa.band = g.band;
   const size_t lds = pool > 1 ? (size_t)2 * g.p * pool * g.chunk * sizeof(float) : 0;
   const dim3 grid1((unsigned)g.nchunk, (unsigned)g.nband, (unsigned)n);
-  sr_with_dtype(sr_dtype, [&](auto sdt) {
-    sr_with_dtype(hr_dtype, [&](auto hdt) {
+  iox::with_dtype(sr_dtype, [&](auto sdt) {
+    iox::with_dtype(hr_dtype, [&](auto hdt) {
       if (c == 3)
         MHAQ_LAUNCH((sr_prepare_kernel<decltype(sdt)::value, decltype(hdt)::value, 3>), grid1, dim3(kBlock), lds, st, pa);
       else
         MHAQ_LAUNCH((sr_prepare_kernel<decltype(sdt)::value, decltype(hdt)::value, 1>), grid1, dim3(kBlock), lds, st, pa);
-      return 0;
     });
-    return 0;
   });
   if (launch_status() != 0) return launch_status();
 

@@ -918,7 +918,7 @@ def potential_loss(base, las, laq, lws, lwq, state, a_bits, w_bits, p=1, lossles
 
 
 # ------------------------------------------------------------------ SR validation metrics (cold: no gradient, plain ctypes)
-_SR_DT = {torch.float32: _lib.DT_F32, torch.bfloat16: _lib.DT_BF16, torch.float16: _lib.DT_F16}
+_DT = {torch.float32: _lib.DT_F32, torch.bfloat16: _lib.DT_BF16, torch.float16: _lib.DT_F16}
 
 
 @_on_device
@@ -930,7 +930,7 @@ def sr_metrics(sr, hr, sr_div, to_luminance, pool):
         if not t.is_cuda:
             raise _lib.MhaqFqError(f"{name} is on {t.device}: the SR metrics run only as HIP kernels on an MI355X "
                                    "(no CPU fallback by design)")
-        if t.dtype not in _SR_DT:
+        if t.dtype not in _DT:
             raise TypeError(f"{name} must be float32, bfloat16 or float16, got {t.dtype}")
         if t.dim() != 4 or not t.is_contiguous():
             raise ValueError(f"{name} must be a contiguous [N, C, H, W] tensor")
@@ -946,7 +946,7 @@ def sr_metrics(sr, hr, sr_div, to_luminance, pool):
     flags = torch.zeros(2, dtype=torch.int32, device=sr.device)
     psnr, ssim = out[:n], out[npad:npad + n]
     l1, mean = out[2 * npad:2 * npad + 1], out[2 * npad + 2:2 * npad + 4]
-    _lib.check(L.mhaq_fq_sr_metrics(sr.data_ptr(), _SR_DT[sr.dtype], hr.data_ptr(), _SR_DT[hr.dtype], n, c, h, w,
+    _lib.check(L.mhaq_fq_sr_metrics(sr.data_ptr(), _DT[sr.dtype], hr.data_ptr(), _DT[hr.dtype], n, c, h, w,
                                     float(sr_div), lum, int(pool), psnr.data_ptr(), ssim.data_ptr(), l1.data_ptr(),
                                     mean.data_ptr(), flags.data_ptr(), ws.data_ptr(), nb, _stream()),
                "mhaq_fq_sr_metrics")
@@ -964,7 +964,7 @@ def cls_head(x, target, topk=5, ignore_index=-100, want_nll_rank=True):
         if not t.is_cuda:
             raise _lib.MhaqFqError(f"{name} is on {t.device}: the classification head runs only as HIP kernels on an "
                                    "MI355X (no CPU fallback by design)")
-    if x.dtype not in _SR_DT:
+    if x.dtype not in _DT:
         raise TypeError(f"logits must be float32, bfloat16 or float16, got {x.dtype}")
     if x.dim() != 2 or not x.is_contiguous() or x.numel() == 0:
         raise ValueError("logits must be a non-empty contiguous [rows, cols] tensor")
@@ -984,7 +984,7 @@ def cls_head(x, target, topk=5, ignore_index=-100, want_nll_rank=True):
     nll = out[4:] if want_nll_rank else None
     flags = words[:1]
     rank = words[1:] if want_nll_rank else None
-    _lib.check(L.mhaq_fq_cls_head_fwd(x.data_ptr(), _SR_DT[x.dtype], target.data_ptr(), rows, cols, int(ignore_index),
+    _lib.check(L.mhaq_fq_cls_head_fwd(x.data_ptr(), _DT[x.dtype], target.data_ptr(), rows, cols, int(ignore_index),
                                       int(topk), loss.data_ptr(), acc.data_ptr(), counts.data_ptr(),
                                       nll.data_ptr() if want_nll_rank else None,
                                       rank.data_ptr() if want_nll_rank else None, None, flags.data_ptr(), ws.data_ptr(), nb,
@@ -998,7 +998,7 @@ def _od_pred(pred):
     if not pred.is_cuda:
         raise _lib.MhaqFqError(f"pred is on {pred.device}: the detection head's NMS runs only as HIP kernels on an MI355X "
                                "(no CPU fallback by design)")
-    if pred.dtype not in _SR_DT:
+    if pred.dtype not in _DT:
         raise TypeError(f"pred must be float32, bfloat16 or float16, got {pred.dtype}")
     if pred.dim() != 3 or pred.shape[1] < 5 or pred.numel() == 0 or not pred.is_contiguous():
         raise ValueError("pred must be a non-empty contiguous [B, 4 + nc, A] tensor")
@@ -1017,7 +1017,7 @@ def od_keys(pred, conf_thr):
     unsorted int64 keys [B, A * nc]."""
     b, nc, a = _od_pred(pred)
     keys = torch.empty((b, a * nc), dtype=torch.int64, device=pred.device)
-    _lib.check(_lib.lib().mhaq_fq_od_keys(pred.data_ptr(), _SR_DT[pred.dtype], b, nc, a, float(conf_thr), keys.data_ptr(),
+    _lib.check(_lib.lib().mhaq_fq_od_keys(pred.data_ptr(), _DT[pred.dtype], b, nc, a, float(conf_thr), keys.data_ptr(),
                                           _stream()), "mhaq_fq_od_keys")
     return keys
 
@@ -1044,9 +1044,9 @@ def _od_nms_launch(pred, keys, n_cand_in, iou_thr, max_wh, max_nms, max_det):
     tail = (b, nc, a, float(iou_thr), float(max_wh), int(max_nms), int(max_det), det.data_ptr(), count.data_ptr(),
             n_cand.data_ptr(), flags.data_ptr(), ws.data_ptr(), nb, _stream())
     if n_cand_in is None:
-        _lib.check(L.mhaq_fq_od_nms(pred.data_ptr(), _SR_DT[pred.dtype], keys.data_ptr(), *tail), "mhaq_fq_od_nms")
+        _lib.check(L.mhaq_fq_od_nms(pred.data_ptr(), _DT[pred.dtype], keys.data_ptr(), *tail), "mhaq_fq_od_nms")
     else:
-        _lib.check(L.mhaq_fq_od_nms_rows(pred.data_ptr(), _SR_DT[pred.dtype], keys.data_ptr(), keys.shape[1],
+        _lib.check(L.mhaq_fq_od_nms_rows(pred.data_ptr(), _DT[pred.dtype], keys.data_ptr(), keys.shape[1],
                                          n_cand_in.data_ptr(), *tail), "mhaq_fq_od_nms_rows")
     return det, count, n_cand, flags
 
@@ -1068,7 +1068,7 @@ def od_sorted_keys(pred, conf_thr, max_nms):
     n_cand = torch.empty(b, dtype=torch.int32, device=pred.device)
     nb = L.mhaq_fq_od_sorted_keys_workspace_bytes(b, nc, a, max_nms)
     ws = _workspace(max(nb, 8), pred.device)
-    _lib.check(L.mhaq_fq_od_sorted_keys(pred.data_ptr(), _SR_DT[pred.dtype], b, nc, a, float(conf_thr), max_nms,
+    _lib.check(L.mhaq_fq_od_sorted_keys(pred.data_ptr(), _DT[pred.dtype], b, nc, a, float(conf_thr), max_nms,
                                         skeys.data_ptr(), n_cand.data_ptr(), ws.data_ptr(), nb, _stream()),
                "mhaq_fq_od_sorted_keys")
     return skeys, n_cand
@@ -1146,7 +1146,7 @@ def od_assign(pd_scores, pd_bboxes, anc_points, gt_labels, gt_bboxes, mask_gt, t
     if not pd_scores.is_cuda:
         raise _lib.MhaqFqError(f"pd_scores is on {pd_scores.device}: the target assignment runs only as HIP kernels on an "
                                "MI355X (no CPU fallback by design)")
-    if pd_scores.dtype not in _SR_DT or pd_bboxes.dtype != pd_scores.dtype:
+    if pd_scores.dtype not in _DT or pd_bboxes.dtype != pd_scores.dtype:
         raise TypeError(f"pd_scores and pd_bboxes must both be float32, bfloat16 or float16, got {pd_scores.dtype} and "
                         f"{pd_bboxes.dtype}")
     if pd_scores.dim() != 3 or pd_scores.shape[2] < 1:
@@ -1179,7 +1179,7 @@ def od_assign(pd_scores, pd_bboxes, anc_points, gt_labels, gt_bboxes, mask_gt, t
     nb = L.mhaq_fq_od_assign_workspace_bytes(b, g, a, top_k)
     ws = _workspace(max(nb, 8), dev)
     ptr = lambda t: t.data_ptr() if t.numel() else None
-    rc = L.mhaq_fq_od_assign(ptr(pd_scores), ptr(pd_bboxes), _SR_DT[pd_scores.dtype], ptr(anc_points), ptr(gt_labels),
+    rc = L.mhaq_fq_od_assign(ptr(pd_scores), ptr(pd_bboxes), _DT[pd_scores.dtype], ptr(anc_points), ptr(gt_labels),
                              ptr(gt_bboxes), ptr(mask_gt), b, a, nc, g, top_k, float(alpha), float(beta), float(eps), ptr(tb),
                              ptr(ts), ptr(fg), ptr(gi), ssum.data_ptr(), flags.data_ptr(), ws.data_ptr(), nb, _stream())
     if rc == -4:                                                     # MHAQ_FQ_EUNSUPPORTED
@@ -1200,7 +1200,7 @@ def _od_levels(outputs, strides, nc, reg_max, what):
     if not x0.is_cuda:
         raise _lib.MhaqFqError(f"the head's outputs are on {x0.device}: {what} runs only as HIP kernels on an MI355X (no CPU "
                                "fallback by design)")
-    if x0.dtype not in _SR_DT:
+    if x0.dtype not in _DT:
         raise TypeError(f"the head's outputs must be float32, bfloat16 or float16, got {x0.dtype}")
     if reg_max != 16 or len(outputs) > 4 or nc < 1:
         raise ValueError(f"{what} serves reg_max = 16, up to 4 levels and nc >= 1, got reg_max = {reg_max}, {len(outputs)} "
@@ -1215,7 +1215,7 @@ def _od_levels(outputs, strides, nc, reg_max, what):
     h = (ctypes.c_int32 * n)(*[t.shape[2] for t in outputs])
     w = (ctypes.c_int32 * n)(*[t.shape[3] for t in outputs])
     s = (ctypes.c_float * n)(*[float(v) for v in strides])
-    return (ptr, h, w, s, n, _SR_DT[x0.dtype], b, nc, reg_max), sum(t.shape[2] * t.shape[3] for t in outputs)
+    return (ptr, h, w, s, n, _DT[x0.dtype], b, nc, reg_max), sum(t.shape[2] * t.shape[3] for t in outputs)
 
 
 def _od_rc(rc, what):
