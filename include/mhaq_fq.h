@@ -935,6 +935,52 @@ int mhaq_fq_od_loss_bwd(const void* const* level_ptr, const int32_t* level_h, co
                         void* stream);
 
 /* ------------------------------------------------------------------------
+ * Detection model: the attention core of YOLOv11's PSA block (the reference's Attention.forward,
+ * src/models/od/yolo_v11.py:121-133, its three tensor statements :129-132) on the qkv convolution's output where it is.
+ * Additive to ABI v4 -- MHAQ_FQ_ABI_VERSION stays 4; a caller discovers these entry points by symbol.
+ *   qkv           dense [b][nh][2 * dk + dh][n], n = H * W: per head dk rows of q, dk rows of k, dh rows of v (the view and
+ *                 split of :125-127), every row n contiguous elements of the type named by dtype (MHAQ_FQ_DT_F32,
+ *                 MHAQ_FQ_DT_BF16 or MHAQ_FQ_DT_F16), aligned to its size.  dk = 32 and dh = 64 are the only compiled sizes
+ *                 (PSABlock(ch // 2, ch // 128) gives them at every YOLOv11 width).
+ *   addend        NULL or [b][nh][dh][n] in the same dtype: the positional branch conv1(v) of :132.
+ *   out           [b][nh][dh][n] in the same dtype;  lse NULL or [b][nh][n] fp32 (the backward needs it).
+ * mhaq_fq_od_attn_fwd (one launch), per image, head and query i, with scale = fp32(dk ** -0.5) (:114):
+ *  1. s_ij = (sum_d q[d][i] * k[d][j]) * scale (:129), the products and the sum in fp32 on the matrix units: 16-bit inputs
+ *     enter exactly, fp32 inputs take the fp32 instruction and are never rounded to 16 bits.
+ *  2. p_ij = exp(s_ij - m_i) / l_i, m_i = max_j s_ij, l_i = sum_j exp(s_ij - m_i) (:130), online over key blocks of 64: running
+ *     maximum and sum in fp32, the accumulator rescaled by exp(m_old - m_new); exponentials in fp32, not approximated.
+ *  3. out[e][i] = (sum_j v[e][j] * exp(s_ij - m_i)) / l_i + addend[e][i] (:132), rounded once to dtype.  For 16-bit inputs the
+ *     un-normalised exp(s_ij - m_i) is rounded once to dtype as the second product's operand; for fp32 it is not rounded.
+ *  4. lse[i] = m_i + log(l_i).
+ * mhaq_fq_od_attn_bwd (two launches) takes the upstream gradient grad_out [b][nh][dh][n] (dtype) and the forward's lse and
+ * writes grad_qkv in the layout and dtype of qkv, EVERY element exactly once (no fill precedes the call).  With
+ * p_ij = exp(s_ij - lse[i]) recomputed as in 1.:
+ *  5. dp_ij = sum_e v[e][j] * grad_out[e][i];  D_i = sum_j p_ij * dp_ij (a first sweep over the keys, fp32);
+ *     ds_ij = p_ij * (dp_ij - D_i).
+ *  6. d q[d][i] = scale * sum_j k[d][j] * ds_ij (first launch, per tile of 64 queries; it writes D to the workspace).
+ *  7. d k[d][j] = scale * sum_i q[d][i] * ds_ij and d v[e][j] = sum_i grad_out[e][i] * p_ij (second launch, per tile of 64
+ *     keys).  For 16-bit inputs p and ds are rounded once to dtype as operands, as in 3.
+ *  The gradient of addend is grad_out itself; no launch computes it.
+ * Deviations from the reference: no [n][n] array is ever stored (the reference writes three and autograd keeps one); a 16-bit
+ * chain rounds s, p and the products' results to 16 bits between its statements, here only the operands named above and the
+ * stored results are; the sums over j, i and d follow the matrix instruction's order, not a BLAS kernel's.
+ *   workspace     mhaq_fq_od_attn_bwd_workspace_bytes(b, nh, n) bytes, 4-byte aligned: D [b][nh][n] fp32.  0 for arguments
+ *                 the call would refuse and for b * n == 0.
+ * b * n == 0: nothing is launched and every pointer may be NULL.
+ * Errors, before any launch: an unknown dtype, b or n < 0, nh, dk or dh < 1; with b * n > 0 a NULL qkv, out, grad_out, lse (bwd),
+ * grad_qkv or workspace (MHAQ_FQ_EINVAL); dk != 32, dh != 64, n > 16384, b or nh > 65535 (MHAQ_FQ_EUNSUPPORTED); a short
+ * workspace (MHAQ_FQ_EWORKSPACE); a tensor not aligned to its element size, lse or workspace not 4-byte aligned
+ * (MHAQ_FQ_EALIGN).
+ * Stream-ordered, capture-safe, stateless, no host synchronisation, no global atomics, no workgroup waits for another; the
+ * same inputs give the same bits at every call.
+ * ---------------------------------------------------------------------- */
+int mhaq_fq_od_attn_fwd(const void* qkv, const void* addend /* nullable */, int dtype, int64_t b, int64_t nh, int64_t n, int dk,
+                        int dh, void* out, float* lse /* nullable */, void* stream);
+size_t mhaq_fq_od_attn_bwd_workspace_bytes(int64_t b, int64_t nh, int64_t n);
+int mhaq_fq_od_attn_bwd(const void* qkv, const void* grad_out, const float* lse, int dtype, int64_t b, int64_t nh, int64_t n,
+                        int dk, int dh, void* grad_qkv, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Super-resolution validation metrics: per-image PSNR and SSIM of the clamped prediction against the target and the L1
  * criterion on the unclamped one, in three launches.  Additive to ABI v4 -- MHAQ_FQ_ABI_VERSION stays 4; a caller discovers
  * these entry points by symbol.

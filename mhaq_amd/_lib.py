@@ -127,6 +127,11 @@ SIGNATURES = {
                                    C.c_float, C.c_float, _p, _p, _p, _sz, _p]),
     "mhaq_fq_od_loss_bwd": (_int, [_p, _p, _p, _p, _int, _int, _i64, _i64, _int, _p, _p, _p, _p, _p, _i64, _p, _p, C.c_float,
                                    C.c_float, C.c_float, _p, _p]),
+    # YOLOv11 PSA attention (additive, ABI v4 kept).  fwd: qkv, addend, dtype, b, nh, n, dk, dh, out, lse.  bwd: qkv, grad_out,
+    # lse, dtype, b, nh, n, dk, dh, grad_qkv, workspace
+    "mhaq_fq_od_attn_fwd": (_int, [_p, _p, _int, _i64, _i64, _i64, _int, _int, _p, _p, _p]),
+    "mhaq_fq_od_attn_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "mhaq_fq_od_attn_bwd": (_int, [_p, _p, _p, _int, _i64, _i64, _i64, _int, _int, _p, _p, _sz, _p]),
     # super-resolution validation metrics: sr, sr_dtype, hr, hr_dtype, n, c, h, w, sr_div, to_luminance, pool, psnr, ssim,
     # l1, mean, flags, workspace (additive, ABI v4 kept)
     "mhaq_fq_sr_metrics_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _int, _int]),

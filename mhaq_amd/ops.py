@@ -1295,3 +1295,67 @@ def od_loss_bwd(outputs, strides, nc, reg_max, fg_mask, target_gt_idx, target_sc
     _od_rc(_lib.lib().mhaq_fq_od_loss_bwd(*lv, *rec, g, grad_out.data_ptr(), denom.data_ptr(), *(float(v) for v in gains), gptr,
                                           _stream()), "mhaq_fq_od_loss_bwd")
     return list(out)
+
+
+# YOLOv11 PSA attention: the core of the reference's Attention.forward on the qkv convolution's output where it is
+_OD_ATTN_DK, _OD_ATTN_DH = 32, 64
+
+
+def _od_attn_shape(qkv, num_head, what):
+    """qkv [B, nh * (2 * dk + dh), H, W] with dh = 2 * dk, as the reference's Attention makes it -> (B, nh, N, dk, dh).  The head
+    sizes are checked before the device: they are a property of the model, not of where it runs."""
+    nh = int(num_head)
+    if not isinstance(qkv, torch.Tensor) or qkv.dim() != 4 or nh < 1 or qkv.shape[1] % (4 * nh):
+        raise ValueError(f"{what}: qkv must be [B, num_head * (2 * dim_key + dim_head), H, W] with dim_head = 2 * dim_key")
+    dk = qkv.shape[1] // (4 * nh)
+    if (dk, 2 * dk) != (_OD_ATTN_DK, _OD_ATTN_DH):
+        raise ValueError(f"{what} serves dim_key = {_OD_ATTN_DK} and dim_head = {_OD_ATTN_DH}, got {dk} and {2 * dk} "
+                         "(include/mhaq_fq.h has the ranges)")
+    if not qkv.is_cuda:
+        raise _lib.MhaqFqError(f"qkv is on {qkv.device}: {what} runs only as HIP kernels on an MI355X (no CPU fallback by design)")
+    if qkv.dtype not in _DT:
+        raise TypeError(f"qkv must be float32, bfloat16 or float16, got {qkv.dtype}")
+    if not qkv.is_contiguous():
+        raise ValueError("qkv must be contiguous")
+    return qkv.shape[0], nh, qkv.shape[2] * qkv.shape[3], dk, 2 * dk
+
+
+def _od_attn_like(t, name, shape, dtype, dev):
+    if tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != dev or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {dtype} {list(shape)} tensor on {dev}")
+    return t.data_ptr() if t.numel() else None
+
+
+@_on_device
+def od_attn_fwd(qkv, num_head, addend=None, want_lse=True, out=None, lse=None):
+    """mhaq_fq_od_attn_fwd: one launch, no host synchronisation.  `qkv` [B, nh * 128, H, W] (float32 / bfloat16 / float16),
+    `addend` None or [B, nh * 64, H, W] of the same dtype.  Returns (out [B, nh * 64, H, W] in qkv's dtype, lse [B, nh, H * W]
+    float32 or None); `out` / `lse` are tensors to write into."""
+    b, nh, n, dk, dh = _od_attn_shape(qkv, num_head, "the PSA attention")
+    dev, oshape = qkv.device, (b, nh * dh, qkv.shape[2], qkv.shape[3])
+    out = torch.empty(oshape, dtype=qkv.dtype, device=dev) if out is None else out
+    if lse is None and want_lse:
+        lse = torch.empty((b, nh, n), dtype=torch.float32, device=dev)
+    ptrs = (_od_attn_like(addend, "addend", oshape, qkv.dtype, dev) if addend is not None else None,
+            _od_attn_like(out, "out", oshape, qkv.dtype, dev),
+            _od_attn_like(lse, "lse", (b, nh, n), torch.float32, dev) if lse is not None else None)
+    _od_rc(_lib.lib().mhaq_fq_od_attn_fwd(qkv.data_ptr() if qkv.numel() else None, ptrs[0], _DT[qkv.dtype], b, nh, n, dk, dh,
+                                          ptrs[1], ptrs[2], _stream()), "mhaq_fq_od_attn_fwd")
+    return out, lse
+
+
+@_on_device
+def od_attn_bwd(qkv, grad_out, lse, num_head, out=None):
+    """mhaq_fq_od_attn_bwd: two launches, no host synchronisation.  `grad_out` [B, nh * 64, H, W] in qkv's dtype, `lse` what
+    od_attn_fwd returned.  Returns d qkv in qkv's shape and dtype; every element is written, so `out` needs no fill."""
+    b, nh, n, dk, dh = _od_attn_shape(qkv, num_head, "the PSA attention")
+    dev = qkv.device
+    out = torch.empty_like(qkv) if out is None else out
+    ptrs = (_od_attn_like(grad_out, "grad_out", (b, nh * dh, qkv.shape[2], qkv.shape[3]), qkv.dtype, dev),
+            _od_attn_like(lse, "lse", (b, nh, n), torch.float32, dev), _od_attn_like(out, "out", qkv.shape, qkv.dtype, dev))
+    L = _lib.lib()
+    nb = L.mhaq_fq_od_attn_bwd_workspace_bytes(b, nh, n)
+    ws = _workspace(max(nb, 4), dev)
+    _od_rc(L.mhaq_fq_od_attn_bwd(qkv.data_ptr() if qkv.numel() else None, ptrs[0], ptrs[1], _DT[qkv.dtype], b, nh, n, dk, dh,
+                                 ptrs[2], ws.data_ptr(), nb, _stream()), "mhaq_fq_od_attn_bwd")
+    return out
